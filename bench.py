@@ -2,13 +2,19 @@
 """bench.py -- molecules/sec through the full contrastive + AR training step (forward_dist, InfoNCE + AR loss,
 backward, clip-norm, AdamW, DP collectives) on the grande_closed configuration, synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): whole-job molecules/s with inputs resident in HBM,
-plus `roofline` (dominant kernel, timed live with HIP events on the launch stream) and, at N=1, `cpu_baseline`
-(the oracle's fp32 CPU step on a bounded sample of the same workload, on this box's host cores).
+Prints ONE JSON line on rank 0: whole-job molecules/s with inputs resident in HBM (`value`) and the milliseconds of one timed
+step (`ms_per_step`).  A plain run does only that: set-up, W warm-up steps, K timed steps, the line.  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs below); that step starts again from the seeded
+weights, so what it computes is the same in every run.
+
+--full adds everything else, after the timed steps: `roofline` (dominant kernel, timed live with HIP events on the launch
+stream inside the timed region), `site_roofline`, `step_roofline`, the other row layout, `varying_batches` / `batch_sweep` /
+`host_feed` / `end_to_end`, `comm` at N > 1 and, at N=1, `cpu_baseline` (the oracle's fp32 CPU step on a bounded sample of the
+same workload, on the host's cores).  The --no-* switches, --all-sites and --roofline-site trim or steer that part.
 
 roofline: the dominant kernel of the step -- the top row of the rocprofv3 kernel table (profiles/rNN_bench_kernel_stats.csv) -- is
 `gemm_ring1_kernel<EPI_LNBWD>`: the N = 256 ring GEMM with the LayerNorm backward in its write-out, i.e. the launch sites
@@ -16,14 +22,14 @@ roofline: the dominant kernel of the step -- the top row of the rocprofv3 kernel
 312 flop/B), so the bound is HBM: achieved = algorithmic bytes per launch (bf16 gradient operand + weight in; LayerNorm input and
 f32 residual gradient in; f32 residual gradient + its bf16 copy out) / average launch time, measured with HIP
 events around those launches over the timed region.  `traffic` is the measured HBM bytes per launch of that kernel from the newest
-committed profiles/rNN_pmc_summary.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over THIS command, `bench.py --steps 2
+committed profiles/rNN_pmc_summary.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over THIS command, `bench.py --full --steps 2
 --warmup 1 --no-cpu-baseline`, collected by tools/profile_round.sh; `traffic_source` names the file and the round), null if there
 is none.  `site_roofline` lists every launch site of >= 2 % of the step the same way (the grouped weight gradient `xf_wgrad`, the
 nominated kernel of rounds 1-3, among them).  `step_roofline` prices the whole step: SURVEY 8(d)'s algorithmic FLOPs
 and HBM bytes per molecule evaluated on this batch / measured step time, against 2.5 PFLOP/s and 8 TB/s.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes this script under
-`python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); the line then also carries `comm`: the
+`python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); with --full the line then also carries `comm`: the
 collectives timed alone and the exposed (not hidden underneath the backward) part of the gradient all-reduces."""
 import argparse
 import glob
@@ -129,6 +135,30 @@ def executed_work(cfg, len1, len2, B, A, n_edges=None):
     fwd += B * 5 * 2.0 * d * d + 2.0 * B * B * d * 2
     bytes_ = (s1 + s2) * L * 12.0 * d * 2 * 2 + s2 * d * 2.0
     return 3.0 * fwd, bytes_
+
+
+DUMP_MAX_ELEMS = 1 << 21      # per array: 8 MB of float32; the two embeddings stay below 64 MB in all at any batch
+
+
+def dump_outputs(out_dir, eng, step_out, losses):
+    """--dump-outputs: what the last timed step computed, as a caller of Engine.train_step receives it -- the embeddings and bad-row
+    flags it returns and the loss scalars of Engine.losses() (grad_norm among them) -- as out_dir/<name>.npy in float32 (float64 for
+    the scalars).  That step starts from the seeded weights (restart in main), so these agree from run to run to rounding.  The engine's
+    state after it is not written: the step is AdamW's first update, lr * g / |g| per element, and gradients that are nothing but
+    rounding of the f32 atomic sums flip sign between runs.  An embedding of more than DUMP_MAX_ELEMS elements is written as a fixed
+    sample of them, flattened: the same seeded, sorted flat indices for every array of that size, so two builds compare element for
+    element.  Rank 0's rows only at N > 1."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h_e, h_s, bad = step_out
+    for name, t in {"h_e3gnn": h_e, "h_smiles": h_s, "bad_rows": bad}.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    for name, v in losses.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.array([v], dtype=np.float64))
 
 
 def time_comm(eng, D, batch_size, steps=10):
@@ -291,7 +321,15 @@ def main():
                          "scales, v_mfma_scale_f32_32x32x64_f8f6f4); weight gradients, attention, lm_head and the GNN stay bf16 / f32")
     ap.add_argument("--no-extras", action="store_true", help="skip the varying_batches / batch_sweep extras (profiling runs)")
     ap.add_argument("--gnn-layers", type=int, default=-1, help="experiment only: override the number of E(3)-GNN layers (the line is then NOT the headline metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline (HIP events inside the timed region), per-site and step rooflines, the other row layout, "
+                         "varying batches / batch sweep / host feed, collectives (N > 1), the CPU baseline; without it the run times the steps only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.all_sites and not args.full:
+        ap.error("--all-sites is part of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: become N ranks (one process per GPU over RCCL), same arguments
@@ -355,6 +393,17 @@ def main():
             else:
                 v.zero_()
     eng.refresh_shadows()
+    # the seeded weights: the last timed step starts again from them (restart below), so that its inputs -- weights, AdamW moments, step
+    # count, batch -- are the same in every run.  Chained steps are not: the engine's f32 atomic sums round differently from run to
+    # run, and AdamW's normalisation turns that into weight differences of up to ~ lr per step, which compound over the steps.
+    init_params = eng.params.clone()
+
+    def restart():
+        eng.params.copy_(init_params)
+        eng.adam_m.zero_()
+        eng.adam_v.zero_()
+        eng.step_count = 0
+        eng.refresh_shadows()
     batch_cpu, up_cpu = make_batch(args.batch, args.seq, args.atoms, MODEL["n_tok"], seed=1234 + rank, with_rows=True)
     batch_padded = {k: v.to(dev) for k, v in batch_cpu.items() if k != "rows"}
     batch_packed = dict(batch_padded, rows=batch_cpu["rows"])      # the counts stay on the host (the data loader made them there)
@@ -364,9 +413,8 @@ def main():
     def step(reduce_grads=True, b=None):
         b = batch if b is None else b
         if dist_on:
-            D.distributed_train_step(eng, b, up, lr=5e-4, head=args.head, reduce_grads=reduce_grads)
-        else:
-            eng.train_step(b, up, lr=5e-4, head=args.head)
+            return D.distributed_train_step(eng, b, up, lr=5e-4, head=args.head, reduce_grads=reduce_grads)
+        return eng.train_step(b, up, lr=5e-4, head=args.head)
 
     def sync():
         if dist_on:
@@ -379,12 +427,13 @@ def main():
         args.roofline_site = "xf_wgrad"      # the fused kernel serves the packed grande batch; elsewhere the grouped weight gradient leads
     for _ in range(max(args.warmup, 9) if dist_on else args.warmup):
         step()
-    # HIP events around the nominated site's launches over the timed region; the step itself runs as the product runs it
+    # --full: HIP events around the nominated site's launches over the timed region; the step itself runs as the product runs it
     # (point encoder concurrent on the side stream: keep_overlap)
-    eng.prof_select(args.roofline_site, keep_overlap=True)
+    if args.full:
+        eng.prof_select(args.roofline_site, keep_overlap=True)
     sync()
     smi = None
-    if rank == 0 and not os.environ.get("COATI_BENCH_NO_SMI"):   # one rocm-smi sample taken WHILE the timed steps run (cross-check for a GPU-activity sampler that reads nothing)
+    if args.full and rank == 0 and not os.environ.get("COATI_BENCH_NO_SMI"):   # one rocm-smi sample taken WHILE the timed steps run (cross-check for a GPU-activity sampler that reads nothing)
         try:
             smi = subprocess.Popen(["rocm-smi", "--showuse"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
         except Exception:   # noqa: BLE001
@@ -393,15 +442,19 @@ def main():
     # barrier packet each; 0.48 ms per step for the 64 launches when every step records them, tools/dp_overhead.py)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        eng.prof_pause(i % 4 != 0)
-        step()
+        if args.full:
+            eng.prof_pause(i % 4 != 0)
+        if i == args.steps - 1:
+            restart()
+        step_out = step()
     sync()
     dt = time.perf_counter() - t0
-    site_ms, site_n, site_flops = eng.prof_collect()
-    site_bytes = eng.prof_last_bytes()
-    eng.prof_select(-1)
+    if args.full:
+        site_ms, site_n, site_flops = eng.prof_collect()
+        site_bytes = eng.prof_last_bytes()
+        eng.prof_select(-1)
     per_rank_ms, world_seen = None, None
-    if dist_on:
+    if dist_on and args.full:
         # every rank's own wall time of the timed region (the line's value uses the MAX), and the world size RCCL itself reports: an
         # all_reduce(SUM) of ones over the device communicator -- a launcher that started N processes which did not all join shows here
         mine = torch.zeros(world, device=dev, dtype=torch.float64)
@@ -411,6 +464,7 @@ def main():
         ones = torch.ones(1, device=dev)
         torch.distributed.all_reduce(ones, op=torch.distributed.ReduceOp.SUM)
         world_seen = int(round(float(ones)))
+    if dist_on:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
@@ -418,12 +472,14 @@ def main():
     import math as _math
     if not all(_math.isfinite(float(losses[k])) for k in ("ar_loss", "clip_loss", "loss")):
         raise SystemExit(f"bench.py: the timed steps produced non-finite losses {losses}: the number would be a measurement of garbage")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, step_out, losses)
     # the other row layout, outside the timed region: the same steps on the padded [B, T] matrices (what the reference
     # computes) when the line is the packed one, and vice versa -- so that the line carries both numbers
     other = batch_packed if args.padded else batch_padded
     k_o = max(3, min(args.steps, 10))
     dt_other = None
-    if not args.no_other_layout:
+    if args.full and not args.no_other_layout:
         for _ in range(2):
             step(b=other)
         sync()
@@ -439,7 +495,7 @@ def main():
         for _ in range(2):
             step()          # leave the engine in the timed layout (profiling below)
     comm = None
-    if dist_on:
+    if dist_on and args.full:
         # exposed cost of the gradient all-reduces: the same steps with those four collectives skipped (outside the timed
         # region; the replicas then drift apart, which no longer matters), then every collective alone
         k2 = max(3, min(args.steps, 10))
@@ -476,7 +532,7 @@ def main():
     #   replayed one at a time (every shape-keyed cache of the engine hits in a replay and may miss in the cycle)
     # batch_sweep: the reference's own default batch size is 160 per GPU (examples/training/train_grande.py:45)
     extras = {}
-    if rank == 0 and not dist_on and not args.no_extras and args.config == "grande_closed" and not args.fp8 and args.gnn_layers < 0:
+    if args.full and rank == 0 and not dist_on and not args.no_extras and args.config == "grande_closed" and not args.fp8 and args.gnn_layers < 0:
         def timed_steps(b, u, n):
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -540,7 +596,7 @@ def main():
     # (stderr with --all-sites) and the `site_roofline` list of the JSON line -- every site of >= 2 % of the step with its
     # algorithmic bytes per second against the HBM peak, so that the line shows the whole family, not only the nominated kernel
     site_rows = []
-    if rank == 0 and not dist_on:
+    if args.full and rank == 0 and not dist_on:
         for s in eng.site_names():
             eng.prof_select(s)
             step()
@@ -558,53 +614,6 @@ def main():
 
     if rank == 0:
         mols = args.batch * world * args.steps
-        avg_ms = site_ms / max(site_n, 1)
-        tflops = (site_flops / (avg_ms * 1e-3) / 1e12) if avg_ms > 0 else 0.0
-        gbs = (site_bytes / (avg_ms * 1e-3) / 1e9) if avg_ms > 0 else 0.0
-        # bound by arithmetic intensity against the ridge point (dense bf16 MFMA peak / HBM peak)
-        ridge = PEAK_BF16_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
-        hbm_bound = site_bytes > 0 and (site_flops / site_bytes) < ridge
-        traffic, traffic_source = None, None
-        try:
-            if args.config != "grande_closed" or args.batch != 1024 or args.seq != 80:
-                raise OSError("PMC summaries are collected for the grande_closed B=1024 T=80 shapes only")
-            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")))
-            with open(cands[-1]) as f:
-                ent = json.load(f).get({"fc1_dgrad,qkv_dgrad,lmhead_dgrad": "dgrad_lnbwd"}.get(args.roofline_site, args.roofline_site), {})
-            if ent.get("layout", "padded") != ("padded" if args.padded else "packed"):
-                raise OSError("the newest PMC summary was collected on the other row layout")
-            traffic = ent.get("hbm_bytes_per_launch")
-            traffic_source = f"{os.path.relpath(cands[-1], ROOT)} ({ent.get('command', 'isolated launches, tools/prof_wgrad.py')}); static file, not this run"
-        except (OSError, ValueError, IndexError):
-            pass
-        # the second fraction: the same kernel's average launch in the SERIALISED rocprofv3 kernel trace of this command (static file of
-        # the round's profile run; in the timed region the point encoder's side-stream kernels share the machine, there they do not)
-        frac_rocprof, rocprof_source = None, None
-        try:
-            import csv
-            kkey = {"fc1_dgrad,qkv_dgrad,lmhead_dgrad": "gemm_ring1_kernel<14>", "xf_wgrad": "wgrad256_table_kernel"}.get(args.roofline_site)
-            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_kernel_stats.csv")))
-            if kkey and cands and args.config == "grande_closed" and args.batch == 1024 and args.seq == 80 and not args.padded:
-                with open(cands[-1]) as f:
-                    for row in csv.DictReader(f):
-                        if kkey in row["Name"]:
-                            avg_ns = float(row["AverageNs"])
-                            frac_rocprof = round(site_bytes / (avg_ns * 1e-9) / 1e9 / PEAK_HBM_GBS, 4)
-                            rocprof_source = f"{os.path.relpath(cands[-1], ROOT)}: {row['Calls']} calls, {avg_ns / 1e3:.2f} us average; static file, not this run"
-                            break
-        except (OSError, ValueError, KeyError):
-            pass
-        kname = {"fc1_dgrad,qkv_dgrad,lmhead_dgrad": "gemm_ring1_kernel<EPI_LNBWD> (ring GEMM + LayerNorm backward; sites fc1_dgrad + qkv_dgrad + lmhead_dgrad = every launch of the kernel)",
-                 "xf_wgrad": "wgrad256_table_kernel (site xf_wgrad)"}.get(args.roofline_site, args.roofline_site)
-        if hbm_bound:
-            roof = {"bound": "hbm", "kernel": kname, "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": round(gbs / PEAK_HBM_GBS, 4), "frac_in_region_hip_events": round(gbs / PEAK_HBM_GBS, 4),
-                    "frac_rocprof_serialized": frac_rocprof, "frac_rocprof_source": rocprof_source, "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": round(avg_ms, 5), "launches": site_n,
-                    "bytes_per_launch": site_bytes, "flops_per_launch": site_flops, "tflops": round(tflops, 1)}
-        else:
-            roof = {"bound": "mfma", "kernel": kname, "achieved": round(tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(tflops / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": round(avg_ms, 5), "launches": site_n,
-                    "bytes_per_launch": site_bytes, "flops_per_launch": site_flops}
         out = {
             "metric": "molecules/sec (contrastive+AR train step), " + (args.config if args.config != "grande_closed" else ("grande_closed" if args.head == "infonce" else "barlow_closed"))
                       + (f" [EXPERIMENT: {args.gnn_layers} GNN layers]" if args.gnn_layers >= 0 else ""),
@@ -631,61 +640,109 @@ def main():
                                      "(tests/test_gpu_packed.py); --padded times the padded layout",
                        "rows_rank0": {"packed": [int(x) for x in batch_cpu["rows"].tolist()],
                                       "padded": [args.batch * batch_cpu["raw_tokens"].shape[1], args.batch * batch_cpu["tokens"].shape[1]]}},
-            ("packed_rows" if args.padded else "padded_layout"): (None if dt_other is None else {
-                "ms_per_step": round(1e3 * dt_other, 3), "value": round(args.batch * world / dt_other, 2),
-                "steps": k_o, "note": "same workload on the other row layout, timed after the main region"}),
             "loss": {k: round(v, 4) for k, v in losses.items() if k in ("ar_loss", "clip_loss", "loss")},
-            "roofline": roof,
         }
-        if site_rows:
-            tot_sites = sum(r[0] for r in site_rows)
-            out["site_roofline"] = {
-                "note": "one step per launch site, HIP events around that site's launches, after the timed region; achieved = "
-                        "the site's algorithmic bytes / its time; sites of >= 2 % of the step",
-                "sum_of_sites_ms": round(tot_sites, 3),
-                "sites": [{"site": s_, "ms_per_step": round(ms, 3), "launches": n,
-                           "achieved_GBps": round(by_ * n / (ms * 1e-3) / 1e9, 1) if ms > 0 and by_ > 0 else None,
-                           "hbm_frac": round(by_ * n / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 3) if ms > 0 and by_ > 0 else None,
-                           "tflops": round(fl_ * n / (ms * 1e-3) / 1e12, 1) if ms > 0 and fl_ > 0 else None}
-                          for ms, s_, n, fl_, by_ in sorted(site_rows, reverse=True) if ms >= 0.02 * tot_sites]}
-        T1, T2 = batch["raw_tokens"].shape[1], batch["tokens"].shape[1]
-        fl, by = algorithmic_work(MODEL, args.batch, T1, T2, args.atoms)
-        t_step = dt / args.steps
-        out["step_roofline"] = {"alg_tflop_per_step": round(fl / 1e12, 3), "step_tflops": round(fl / t_step / 1e12, 1),
-                                "mfma_frac": round(fl / t_step / 1e12 / PEAK_BF16_TFLOPS, 4),
-                                "alg_GB_per_step": round(by / 1e9, 2), "alg_GBps": round(by / t_step / 1e9, 1),
-                                "hbm_frac": round(by / t_step / 1e9 / PEAK_HBM_GBS, 4),
-                                "note": "SURVEY 8(d) formulas per rank (padded positions and all A(A-1) pairs counted: the reference-equivalent "
-                                        "work), per-rank step time" + ("" if args.padded else "; the packed layout does NOT execute the padded positions: "
-                                        "`executed` prices the rows it really processes")}
-        if not args.padded:
-            from coati_amd.synthetic import packed_lengths
-            l1, l2 = packed_lengths(batch_cpu["raw_tokens"], batch_cpu["tokens"], batch_cpu["y_next"])
-            fe, be = executed_work(MODEL, l1, l2, args.batch, args.atoms)
-            out["step_roofline"]["executed"] = {
-                "tflop_per_step": round(fe / 1e12, 3), "step_tflops": round(fe / t_step / 1e12, 1),
-                "mfma_frac": round(fe / t_step / 1e12 / PEAK_BF16_TFLOPS, 4),
-                "alg_GB_per_step": round(be / 1e9, 2), "alg_GBps": round(be / t_step / 1e9, 1),
-                "hbm_frac": round(be / t_step / 1e9 / PEAK_HBM_GBS, 4),
-                "note": "same formulas on the rows' real lengths (attention t x t per row, lm_head on the decoder pass's real rows)"}
-            if MODEL["n_hidden_xformer"] // MODEL["n_head"] == 16 and max(T1, T2) <= 128:
-                from coati_amd.synthetic import attention_score_efficiency
-                both = torch.cat([l1, l2])
-                out["attention"] = {"useful_over_computed": round(attention_score_efficiency(both, 16), 4),
-                                    "useful_over_computed_32_row_blocks": round(attention_score_efficiency(both, 32), 4),
-                                    "note": "score elements of the causal triangle / score elements the kernel evaluates, both passes: head size 16 runs on "
-                                            "16-row blocks of v_mfma_f32_16x16x16_bf16 since round 6 (csrc/attention16.hip); rounds 1-5: 32-row blocks"}
-        out.update(extras)
-        if comm is not None:
-            out["comm"] = comm
-        if smi is not None:
+        if args.full:
+            avg_ms = site_ms / max(site_n, 1)
+            tflops = (site_flops / (avg_ms * 1e-3) / 1e12) if avg_ms > 0 else 0.0
+            gbs = (site_bytes / (avg_ms * 1e-3) / 1e9) if avg_ms > 0 else 0.0
+            # bound by arithmetic intensity against the ridge point (dense bf16 MFMA peak / HBM peak)
+            ridge = PEAK_BF16_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
+            hbm_bound = site_bytes > 0 and (site_flops / site_bytes) < ridge
+            traffic, traffic_source = None, None
             try:
-                so, _ = smi.communicate(timeout=30)
-                print("[bench] rocm-smi --showuse sampled during the timed steps: " + " | ".join(l.strip() for l in so.splitlines() if "GPU[" in l), file=sys.stderr)
-            except Exception as ex:   # noqa: BLE001
-                print(f"[bench] rocm-smi sample failed: {ex}", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline and args.config == "grande_closed":
-            out["cpu_baseline"] = cpu_baseline(batch_cpu, up_cpu, args.cpu_mols)
+                if args.config != "grande_closed" or args.batch != 1024 or args.seq != 80:
+                    raise OSError("PMC summaries are collected for the grande_closed B=1024 T=80 shapes only")
+                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")))
+                with open(cands[-1]) as f:
+                    ent = json.load(f).get({"fc1_dgrad,qkv_dgrad,lmhead_dgrad": "dgrad_lnbwd"}.get(args.roofline_site, args.roofline_site), {})
+                if ent.get("layout", "padded") != ("padded" if args.padded else "packed"):
+                    raise OSError("the newest PMC summary was collected on the other row layout")
+                traffic = ent.get("hbm_bytes_per_launch")
+                traffic_source = f"{os.path.relpath(cands[-1], ROOT)} ({ent.get('command', 'isolated launches, tools/prof_wgrad.py')}); static file, not this run"
+            except (OSError, ValueError, IndexError):
+                pass
+            # the second fraction: the same kernel's average launch in the SERIALISED rocprofv3 kernel trace of this command (static file of
+            # the round's profile run; in the timed region the point encoder's side-stream kernels share the machine, there they do not)
+            frac_rocprof, rocprof_source = None, None
+            try:
+                import csv
+                kkey = {"fc1_dgrad,qkv_dgrad,lmhead_dgrad": "gemm_ring1_kernel<14>", "xf_wgrad": "wgrad256_table_kernel"}.get(args.roofline_site)
+                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_kernel_stats.csv")))
+                if kkey and cands and args.config == "grande_closed" and args.batch == 1024 and args.seq == 80 and not args.padded:
+                    with open(cands[-1]) as f:
+                        for row in csv.DictReader(f):
+                            if kkey in row["Name"]:
+                                avg_ns = float(row["AverageNs"])
+                                frac_rocprof = round(site_bytes / (avg_ns * 1e-9) / 1e9 / PEAK_HBM_GBS, 4)
+                                rocprof_source = f"{os.path.relpath(cands[-1], ROOT)}: {row['Calls']} calls, {avg_ns / 1e3:.2f} us average; static file, not this run"
+                                break
+            except (OSError, ValueError, KeyError):
+                pass
+            kname = {"fc1_dgrad,qkv_dgrad,lmhead_dgrad": "gemm_ring1_kernel<EPI_LNBWD> (ring GEMM + LayerNorm backward; sites fc1_dgrad + qkv_dgrad + lmhead_dgrad = every launch of the kernel)",
+                     "xf_wgrad": "wgrad256_table_kernel (site xf_wgrad)"}.get(args.roofline_site, args.roofline_site)
+            if hbm_bound:
+                roof = {"bound": "hbm", "kernel": kname, "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": round(gbs / PEAK_HBM_GBS, 4), "frac_in_region_hip_events": round(gbs / PEAK_HBM_GBS, 4),
+                        "frac_rocprof_serialized": frac_rocprof, "frac_rocprof_source": rocprof_source, "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": round(avg_ms, 5), "launches": site_n,
+                        "bytes_per_launch": site_bytes, "flops_per_launch": site_flops, "tflops": round(tflops, 1)}
+            else:
+                roof = {"bound": "mfma", "kernel": kname, "achieved": round(tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(tflops / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": round(avg_ms, 5), "launches": site_n,
+                        "bytes_per_launch": site_bytes, "flops_per_launch": site_flops}
+            out["packed_rows" if args.padded else "padded_layout"] = (None if dt_other is None else {
+                "ms_per_step": round(1e3 * dt_other, 3), "value": round(args.batch * world / dt_other, 2),
+                "steps": k_o, "note": "same workload on the other row layout, timed after the main region"})
+            out["roofline"] = roof
+            if site_rows:
+                tot_sites = sum(r[0] for r in site_rows)
+                out["site_roofline"] = {
+                    "note": "one step per launch site, HIP events around that site's launches, after the timed region; achieved = "
+                            "the site's algorithmic bytes / its time; sites of >= 2 % of the step",
+                    "sum_of_sites_ms": round(tot_sites, 3),
+                    "sites": [{"site": s_, "ms_per_step": round(ms, 3), "launches": n,
+                               "achieved_GBps": round(by_ * n / (ms * 1e-3) / 1e9, 1) if ms > 0 and by_ > 0 else None,
+                               "hbm_frac": round(by_ * n / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 3) if ms > 0 and by_ > 0 else None,
+                               "tflops": round(fl_ * n / (ms * 1e-3) / 1e12, 1) if ms > 0 and fl_ > 0 else None}
+                              for ms, s_, n, fl_, by_ in sorted(site_rows, reverse=True) if ms >= 0.02 * tot_sites]}
+            T1, T2 = batch["raw_tokens"].shape[1], batch["tokens"].shape[1]
+            fl, by = algorithmic_work(MODEL, args.batch, T1, T2, args.atoms)
+            t_step = dt / args.steps
+            out["step_roofline"] = {"alg_tflop_per_step": round(fl / 1e12, 3), "step_tflops": round(fl / t_step / 1e12, 1),
+                                    "mfma_frac": round(fl / t_step / 1e12 / PEAK_BF16_TFLOPS, 4),
+                                    "alg_GB_per_step": round(by / 1e9, 2), "alg_GBps": round(by / t_step / 1e9, 1),
+                                    "hbm_frac": round(by / t_step / 1e9 / PEAK_HBM_GBS, 4),
+                                    "note": "SURVEY 8(d) formulas per rank (padded positions and all A(A-1) pairs counted: the reference-equivalent "
+                                            "work), per-rank step time" + ("" if args.padded else "; the packed layout does NOT execute the padded positions: "
+                                            "`executed` prices the rows it really processes")}
+            if not args.padded:
+                from coati_amd.synthetic import packed_lengths
+                l1, l2 = packed_lengths(batch_cpu["raw_tokens"], batch_cpu["tokens"], batch_cpu["y_next"])
+                fe, be = executed_work(MODEL, l1, l2, args.batch, args.atoms)
+                out["step_roofline"]["executed"] = {
+                    "tflop_per_step": round(fe / 1e12, 3), "step_tflops": round(fe / t_step / 1e12, 1),
+                    "mfma_frac": round(fe / t_step / 1e12 / PEAK_BF16_TFLOPS, 4),
+                    "alg_GB_per_step": round(be / 1e9, 2), "alg_GBps": round(be / t_step / 1e9, 1),
+                    "hbm_frac": round(be / t_step / 1e9 / PEAK_HBM_GBS, 4),
+                    "note": "same formulas on the rows' real lengths (attention t x t per row, lm_head on the decoder pass's real rows)"}
+                if MODEL["n_hidden_xformer"] // MODEL["n_head"] == 16 and max(T1, T2) <= 128:
+                    from coati_amd.synthetic import attention_score_efficiency
+                    both = torch.cat([l1, l2])
+                    out["attention"] = {"useful_over_computed": round(attention_score_efficiency(both, 16), 4),
+                                        "useful_over_computed_32_row_blocks": round(attention_score_efficiency(both, 32), 4),
+                                        "note": "score elements of the causal triangle / score elements the kernel evaluates, both passes: head size 16 runs on "
+                                                "16-row blocks of v_mfma_f32_16x16x16_bf16 since round 6 (csrc/attention16.hip); rounds 1-5: 32-row blocks"}
+            out.update(extras)
+            if comm is not None:
+                out["comm"] = comm
+            if smi is not None:
+                try:
+                    so, _ = smi.communicate(timeout=30)
+                    print("[bench] rocm-smi --showuse sampled during the timed steps: " + " | ".join(l.strip() for l in so.splitlines() if "GPU[" in l), file=sys.stderr)
+                except Exception as ex:   # noqa: BLE001
+                    print(f"[bench] rocm-smi sample failed: {ex}", file=sys.stderr)
+            if world == 1 and not args.no_cpu_baseline and args.config == "grande_closed":
+                out["cpu_baseline"] = cpu_baseline(batch_cpu, up_cpu, args.cpu_mols)
         print(json.dumps(out), flush=True)
     if dist_on:
         torch.distributed.destroy_process_group()
