@@ -90,6 +90,7 @@ _SIGS = {
     "coati_attn_bwd_varlen": [P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "coati_engine_logits": [P, P, L, P],
     "coati_engine_encode": [P, P, L, I, I, I, P, P, P, P, P, P, P],
+    "coati_engine_score": [P, P, L, I, I, I, P, P, P, P, L, L, P, P, P],
     "coati_engine_infonce": [P, P, P, P, P, P, I, I, I, F, P, P, P, P],
     "coati_engine_backward": [P, P, P, I, P],
     "coati_engine_optimizer_step": [P, F, F, F, F, F, F, I, P, P],

@@ -317,6 +317,34 @@ int launch_bad_rows(const long long* tokens, unsigned char* bad, int B, int T, h
 // cross-entropy finish (lmhead): merge per-tile (max, sumexp) partials into lse[row]; target logit by a
 // direct bf16 dot product (same operands the MFMA saw); accumulate sum(lse - logit_t) and the count.
 // ------------------------------------------------------------------------------------------------------
+// One row, one wave: lse of the row (written to *lse_out by lane 0 when given) and, when the target is in range, lse - logit[target]
+// in every lane (*valid = true).  Shared by ce_finish (batch sums) and ce_seq (per-sequence sums): the two see the same numbers.
+__device__ __forceinline__ float ce_row(const float2* __restrict__ partial, int tiles_n, const bf16_t* __restrict__ a, long long lda,
+                                        const bf16_t* __restrict__ W, long long ldw, long long tgt, long long row, int C, int V,
+                                        float* __restrict__ lse_out, int lane, bool* valid) {
+  float mx = -INFINITY;
+  for (int t = lane; t < tiles_n; t += 64) mx = fmaxf(mx, partial[row * tiles_n + t].x);
+  mx = wave_max(mx);
+  float sm = 0.f;
+  for (int t = lane; t < tiles_n; t += 64) {
+    const float2 p = partial[row * tiles_n + t];
+    sm += p.y * __expf(p.x - mx);
+  }
+  sm = wave_sum(sm);
+  const float l = mx + __logf(sm);
+  if (lse_out != nullptr && lane == 0) *lse_out = l;
+  *valid = tgt >= 0 && tgt < V;
+  if (!*valid) return 0.f;
+  float dot = 0.f;
+  for (int c = lane * 4; c < C; c += 256) {
+    const uint2 ua = *reinterpret_cast<const uint2*>(a + row * lda + c);
+    const uint2 uw = *reinterpret_cast<const uint2*>(W + tgt * ldw + c);
+    dot += bflo(ua.x) * bflo(uw.x) + bfhi(ua.x) * bfhi(uw.x) + bflo(ua.y) * bflo(uw.y) + bfhi(ua.y) * bfhi(uw.y);
+  }
+  dot = wave_sum(dot);
+  return l - dot;
+}
+
 __global__ __launch_bounds__(256) void ce_finish_kernel(const float2* __restrict__ partial, int tiles_n,
                                                         const bf16_t* __restrict__ a, long long lda,
                                                         const bf16_t* __restrict__ W, long long ldw,
@@ -326,27 +354,10 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float2* __restrict
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float loss_acc = 0.f, cnt_acc = 0.f;
   for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
-    float mx = -INFINITY;
-    for (int t = lane; t < tiles_n; t += 64) mx = fmaxf(mx, partial[(long long)row * tiles_n + t].x);
-    mx = wave_max(mx);
-    float sm = 0.f;
-    for (int t = lane; t < tiles_n; t += 64) {
-      const float2 p = partial[(long long)row * tiles_n + t];
-      sm += p.y * __expf(p.x - mx);
-    }
-    sm = wave_sum(sm);
-    const float l = mx + __logf(sm);
-    if (lane == 0) lse[row] = l;
-    const long long tgt = target[row];
-    if (tgt >= 0 && tgt < V) {
-      float dot = 0.f;
-      for (int c = lane * 4; c < C; c += 256) {
-        const uint2 ua = *reinterpret_cast<const uint2*>(a + (long long)row * lda + c);
-        const uint2 uw = *reinterpret_cast<const uint2*>(W + tgt * ldw + c);
-        dot += bflo(ua.x) * bflo(uw.x) + bfhi(ua.x) * bfhi(uw.x) + bflo(ua.y) * bflo(uw.y) + bfhi(ua.y) * bfhi(uw.y);
-      }
-      dot = wave_sum(dot);
-      loss_acc += l - dot;
+    bool valid;
+    const float d = ce_row(partial, tiles_n, a, lda, W, ldw, target[row], row, C, V, lse + row, lane, &valid);
+    if (valid) {
+      loss_acc += d;
       cnt_acc += 1.f;
     }
   }
@@ -367,5 +378,37 @@ int launch_ce_finish(const float2* partial, int tiles_n, const bf16_t* a, long l
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(ce_finish_kernel, dim3(blocks), dim3(256), 0, s, partial, tiles_n, a, lda, W, ldw, target, lse, scal, M, C, V);
   COATI_LAUNCH_CHECK("ce_finish");
+  return COATI_OK;
+}
+
+// Per-sequence cross-entropy (likelihood scoring, clip_e2e.py:634-742): nll[b] = sum over the rows of sequence b of lse - logit[target]
+// (targets < 0 ignored).  One workgroup per sequence: wave w takes rows w, w + 4, ... of the sequence, the four wave sums are added in
+// LDS in a fixed order -- no float atomics, so the same batch always gives the same bits.  Rows: b * T .. b * T + T (padded) or
+// off[b] .. off[b + 1] (packed; target = the packed targets ypk).
+__global__ __launch_bounds__(256) void ce_seq_kernel(const float2* __restrict__ partial, int tiles_n,
+                                                     const bf16_t* __restrict__ a, long long lda,
+                                                     const bf16_t* __restrict__ W, long long ldw,
+                                                     const long long* __restrict__ target, const int* __restrict__ off,
+                                                     float* __restrict__ nll, int T, int C, int V) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
+  const long long r0 = off ? (long long)off[b] : (long long)b * T, r1 = off ? (long long)off[b + 1] : r0 + T;
+  float acc = 0.f;
+  for (long long row = r0 + wave; row < r1; row += 4) {
+    bool valid;
+    const float d = ce_row(partial, tiles_n, a, lda, W, ldw, target[row], row, C, V, nullptr, lane, &valid);
+    if (valid) acc += d;
+  }
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) nll[b] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+int launch_ce_seq(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,
+                  const long long* target, const int* off, float* nll, int B, int T, int C, int V, hipStream_t s) {
+  COATI_CHECK_ARG(partial && a && W && target && nll, "ce_seq: null operand");
+  COATI_CHECK_SHAPE(B > 0 && T > 0 && C % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "ce_seq: shape / alignment");
+  hipLaunchKernelGGL(ce_seq_kernel, dim3(B), dim3(256), 0, s, partial, tiles_n, a, lda, W, ldw, target, off, nll, T, C, V);
+  COATI_LAUNCH_CHECK("ce_seq");
   return COATI_OK;
 }

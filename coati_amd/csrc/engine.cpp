@@ -1553,6 +1553,22 @@ static int refresh_shadows_impl(coati_engine* e, void* stream, bool natural_done
 
 int coati_engine_refresh_shadows(coati_engine* e, void* stream) { return refresh_shadows_impl(e, stream, false); }
 
+// lm_head on the decoder pass's rows as per-(row, 64-column tile) (max, sum exp) partials in ce_partial, logits never materialised
+// (smiles_xformer.py:453); *tiles_v = partial entries per row.  Shared by the training forward (ce_finish) and scoring (ce_seq).
+static int lmhead_ce_partial(coati_engine* e, hipStream_t s, int* tiles_v) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, M2 = e->p2.M;
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = M2; a.N = c.n_tok; a.K = C; a.partial = e->ce_partial;
+  a.partial_tile = 64;   // ce_partial is sized for 64-column entries: the row-block kernel may take the product
+  GemmArgs aw = a;             // (the width is a property of the kernel that runs: with a row split, of a launch's row range)
+  if (const int rows = row_split_plan(a, 0, EPI_CE_PARTIAL)) aw.M = rows;
+  *tiles_v = cdiv(c.n_tok, gemm_ce_tile_width(aw));
+  ProfScope ps(e, SITE_LMHEAD_FWD, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2);   // logits never leave the chip
+  return gemm_rows(a, 0, EPI_CE_PARTIAL, s);
+}
+
 // decoder pass with injection + lm_head / AR cross-entropy: the second half of coati_engine_forward
 static int forward_decoder_impl(coati_engine* e, hipStream_t s) {
   const coati_config& c = e->cfg;
@@ -1562,19 +1578,9 @@ static int forward_decoder_impl(coati_engine* e, hipStream_t s) {
   COATI_TRY(xformer_fwd(e, e->p2, e->cliptok, s));
   // ---- lm_head + AR cross-entropy, logits never materialised (smiles_xformer.py:453, train_coati.py:260-265) ----
   if (e->y_next) {
-    const int M2 = e->p2.M;
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = M2; a.N = c.n_tok; a.K = C; a.partial = e->ce_partial;
-    a.partial_tile = 64;   // ce_partial is sized for 64-column entries: the row-block kernel may take the product
-    GemmArgs aw = a;             // (the width is a property of the kernel that runs: with a row split, of a launch's row range)
-    if (const int rows = row_split_plan(a, 0, EPI_CE_PARTIAL)) aw.M = rows;
-    const int tiles_v = cdiv(c.n_tok, gemm_ce_tile_width(aw));
-    {
-      ProfScope ps(e, SITE_LMHEAD_FWD, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2);   // logits never leave the chip
-      COATI_TRY(gemm_rows(a, 0, EPI_CE_PARTIAL, s));
-    }
-    COATI_TRY(launch_ce_finish(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next, e->ce_lse, scal, M2, C, c.n_tok, s));
+    int tiles_v = 0;
+    COATI_TRY(lmhead_ce_partial(e, s, &tiles_v));
+    COATI_TRY(launch_ce_finish(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next, e->ce_lse, scal, e->p2.M, C, c.n_tok, s));
   }
   if (hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess) {
     coati_set_error("engine_forward: error-word copy failed");
@@ -1732,6 +1738,75 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
     COATI_TRY(smiles_head_fwd(e, h_smiles, s));
     HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
   }
+  return COATI_OK;
+}
+
+// Likelihood scoring (clip_e2e.py:634-665 hclip_and_tokens_to_likelihood, :667-742 batch_smiles_to_s2s_likelihood): the embedding --
+// the caller's h_clip, or smiles_to_clip of the encoder pass over raw_tokens --, the special-token head, the decoder pass with that
+// injection, lm_head as CE partials and their per-sequence sums.  No point encoder, no logits, nothing saved for a backward
+// (have_fwd stays false).  rows2 > 0: the decoder pass on packed rows (rows1 > 0 with it for the encoder pass over raw_tokens).
+int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
+                       const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
+                       float* scal, void* stream) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens && y_next && nll && scal, "engine_score: engine not bound / null argument");
+  COATI_CHECK_ARG((raw_tokens != nullptr) != (h_clip != nullptr), "engine_score: give exactly one of raw_tokens / h_clip");
+  const coati_config& c = e->cfg;
+  if (!raw_tokens) { T1 = 1; rows1 = 0; }
+  COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T2 > 0 && T1 <= c.n_seq && T2 <= c.n_seq, "engine_score: unsupported shape B=%d T1=%d T2=%d (n_seq=%d)",
+                    B, T1, T2, c.n_seq);
+  COATI_CHECK_SHAPE(rows1 >= 0 && rows2 >= 0 && rows1 <= (int64_t)B * T1 && rows2 <= (int64_t)B * T2 && (!raw_tokens || (rows1 > 0) == (rows2 > 0)),
+                    "engine_score: packed row counts %lld / %lld do not fit %d x %d / %d x %d", (long long)rows1, (long long)rows2, B, T1, B, T2);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = c.n_hidden_xformer, E = c.n_embd_common;
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
+  const size_t need = carve(e, ar, B, T1, T2, 1, B);
+  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_score: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
+  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = T1; e->T2 = T2; e->A = 1;
+  e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
+  e->p2.idx = reinterpret_cast<const long long*>(tokens);
+  e->y_next = reinterpret_cast<const long long*>(y_next);
+  e->scal = scal;
+  e->have_fwd = false;
+  e->decoder_pending = false;
+  e->have_ws = true;
+  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
+  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  if (rows1 > 0) {
+    COATI_TRY(launch_seq_pack(e->p1.idx, nullptr, c.pad_token, B, T1, (int)rows1, e->p1.off, e->p1.row_src, e->p1.row_t, nullptr, e->err_flag, s, e->p1.ord));
+    e->p1.packed = true;
+    e->p1.M = (int)rows1;
+  }
+  if (rows2 > 0) {
+    COATI_TRY(launch_seq_pack(e->p2.idx, e->y_next, c.pad_token, B, T2, (int)rows2, e->p2.off, e->p2.row_src, e->p2.row_t, e->p2.ypk, e->err_flag, s, e->p2.ord));
+    e->p2.packed = true;
+    e->p2.M = (int)rows2;
+  }
+  // ---- the embedding: encode_tokens (clip_e2e.py:448-452) or the caller's ----
+  const float* hclip = h_clip;
+  if (raw_tokens) {
+    COATI_TRY(launch_find_stop(e->p1.idx, c.stop_token, e->stop_pos, e->err_flag, B, T1, s));
+    COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
+    COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s, e->p1.packed ? e->p1.off : nullptr));
+    COATI_TRY(smiles_head_fwd(e, e->h_smiles, s));
+    hclip = e->h_smiles;
+  }
+  // ---- special token: point_clip_to_special_tokens = SiLU -> Linear, or nn.Identity (clip_e2e.py:432-437) ----
+  const float* inj = hclip;
+  if (c.token_mlp) {
+    COATI_TRY(launch_silu_fwd(hclip, e->sb, (long long)B * E, s));
+    SgemmBatch sb;
+    COATI_TRY(sgemm_batch_add(sb, e->sb, E, 1, e->P + e->tokw, 1, E, e->stok, E, B, E, E, e->P + e->tokb, 1.f, 0));
+    COATI_TRY(launch_sgemm_batch(sb, s));
+    inj = e->stok;
+  }
+  // ---- decoder pass with the injection, lm_head partials, per-sequence sums (forward_with_replacement + cross_entropy) ----
+  COATI_TRY(xformer_fwd(e, e->p2, inj, s));
+  int tiles_v = 0;
+  COATI_TRY(lmhead_ce_partial(e, s, &tiles_v));
+  COATI_TRY(launch_ce_seq(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next,
+                          e->p2.packed ? e->p2.off : nullptr, nll, B, T2, C, c.n_tok, s));
+  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
   return COATI_OK;
 }
 

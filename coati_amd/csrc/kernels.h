@@ -325,6 +325,10 @@ int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* t
 int launch_ce_finish(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W,
                      long long ldw, const long long* target, float* lse, float* scal, int M, int C, int V,
                      hipStream_t s);
+// per-sequence sums of lse - logit[target] (one workgroup per sequence, fixed-order reduction: deterministic) into nll[B]; rows of sequence
+// b: b * T .. b * T + T, or off[b] .. off[b + 1] when off is given (packed rows, target = the packed targets)
+int launch_ce_seq(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,
+                  const long long* target, const int* off, float* nll, int B, int T, int C, int V, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // E(3)-GNN kernels (gnn.hip)

@@ -268,6 +268,36 @@ class Engine:
         self._shape = None
         return h_s, h_e
 
+    def score(self, tokens, y_next, h_clip=None, raw_tokens=None, rows=None):
+        """Per-sequence autoregressive NLL [B] f32 of `tokens` [B, T2] against `y_next` [B, T2] (-1 = ignored), with the special-token
+        head's image of an embedding injected at the [UNK] positions (clip_e2e.py:634-742): either the caller's `h_clip` [B, E] or
+        encode_tokens(`raw_tokens` [B, T1]).  No point encoder, no logits; the sums are deterministic.  rows = (rows1, rows2) from
+        coati_amd.synthetic.packed_rows on host tensors: the transformer passes on packed rows (rows1 only matters with raw_tokens).
+        Stays on the device (no sync): error_bits() / losses() report a row without [STOP] or a packed-row mismatch."""
+        assert (h_clip is None) != (raw_tokens is None), "score: give exactly one of h_clip / raw_tokens"
+        B, T2 = tokens.shape
+        T1 = raw_tokens.shape[1] if raw_tokens is not None else 1
+        for t in (tokens, y_next) + ((raw_tokens,) if raw_tokens is not None else ()):
+            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.shape[0] == B
+        assert y_next.shape == tokens.shape
+        if h_clip is not None:
+            h_clip = h_clip.to(self.device, torch.float32).contiguous()
+            assert h_clip.shape == (B, self.cfg.n_embd_common)
+        self._ensure_workspace(B, T1, T2, 1)
+        r1 = r2 = 0
+        if rows is not None and PACK_ROWS:
+            r1, r2 = (int(x) for x in (rows.tolist() if isinstance(rows, torch.Tensor) else rows))
+            if raw_tokens is None:
+                r1 = 0
+            if r2 <= 0 or (raw_tokens is not None and r1 <= 0):
+                r1 = r2 = 0
+        nll = torch.empty(B, device=self.device, dtype=torch.float32)
+        self._keep = (raw_tokens, h_clip, tokens, y_next)
+        _lib.check(self.l.coati_engine_score(self.h, ptr(self.workspace), self.workspace.numel(), B, T1, T2, ptr(raw_tokens), ptr(h_clip),
+                                             ptr(tokens), ptr(y_next), r1, r2, ptr(nll), ptr(self.scal), stream()), "coati_engine_score")
+        self._shape = None
+        return nll
+
     def logits(self):
         if getattr(self, "_packed", False):
             raise RuntimeError("logits(): the last forward ran on packed rows; call forward(..., rows=None)")

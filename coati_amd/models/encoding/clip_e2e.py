@@ -3,7 +3,7 @@
 `clip_loss`, and `clip_ar_xform` (augmentation + tokenisation head over the C++ trie tokenizer, tensorisation tail).  All tensor maths runs in libcoati_hip.so through
 coati_amd.engine.Engine; this file only adapts the calling convention."""
 import math
-from typing import Any, Dict
+from typing import Any, Dict, List
 
 import torch
 import torch.nn as nn
@@ -83,6 +83,68 @@ class clip_loss(nn.Module):
         eng.infonce(s, c, s, c, bad, row0=0, gscale=1.0)
         sc = eng.scal
         return (0.5 * (sc[2] + sc[3]) / torch.clamp(sc[4], min=1.0)).unsqueeze(0)
+
+
+def _tokenize_smiles(smi, tokenizer, prefix="[SMILES]", suffix="[STOP]", device="cpu", max_size=None):
+    """clip_e2e.py:333-347: the row prefix + smi + suffix zero-padded to max_size (default n_seq), or None when it does not tokenize
+    or is longer"""
+    if max_size is None:
+        max_size = tokenizer.n_seq
+    try:
+        ttext = tokenizer.tokenize_text(prefix + smi + suffix, pad=False, range_check=False)
+        if len(ttext) <= max_size:
+            t = torch.zeros(max_size, dtype=torch.long, device=device)
+            t[: len(ttext)] = torch.tensor(ttext)
+            return t
+    except KeyError:
+        pass
+
+
+_LIKELIHOOD_PREFIX = "[CLIP][UNK][SMILES][SUFFIX][MIDDLE]"
+
+
+def hclip_likelihood_tokens(smiles: List[str], tokenizer):
+    """Host-side rows of hclip_and_tokens_to_likelihood (clip_e2e.py:638-655) for a list of SMILES: tokens
+    [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smi>[STOP] [B, T] (rows of different length end in [PAD]) and their targets (the next token;
+    [CLIP] / [PAD] / [SMILES] / [UNK] / [SUFFIX] / [MIDDLE] targets are -1).  Tokenizer errors propagate as in the reference."""
+    rows = [tokenizer.tokenize_text(_LIKELIHOOD_PREFIX + smi + "[STOP]", pad=False) for smi in smiles]
+    tokens = torch.full((len(rows), max(len(r) for r in rows)), tokenizer.pad_token, dtype=torch.long)
+    for i, r in enumerate(rows):
+        tokens[i, : len(r)] = torch.tensor(r, dtype=torch.long)
+    y_next = torch.zeros_like(tokens)
+    y_next[:, : (tokens.shape[1] - 1)] = tokens[:, 1:].clone()
+    for t in (tokenizer.clip_token, tokenizer.pad_token, tokenizer.smiles_token, tokenizer.unk_token, tokenizer.suffix_token,
+              tokenizer.middle_token):
+        y_next[y_next == t] = -1
+    return tokens, y_next
+
+
+def s2s_likelihood_tokens(smiles: List[str], tokenizer):
+    """Host-side tensors of batch_smiles_to_s2s_likelihood (clip_e2e.py:670-735): the mask of the SMILES that tokenize into n_seq - 5
+    positions, and for those rows the encoder's [SMILES]<smi>[STOP] [n_ok, n_seq - 4], the decoder's
+    [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smi>[STOP] [n_ok, n_seq] and its targets (positions :4, the last column and [PAD] are -1)."""
+    _tokens = [_tokenize_smiles(smi, tokenizer, prefix="", suffix="[STOP]", max_size=(tokenizer.n_seq - 5)) for smi in smiles]
+    mask = torch.tensor([t is not None for t in _tokens], dtype=torch.bool)
+    _tokens = torch.stack([t for t in _tokens if t is not None])
+    n = _tokens.shape[0]
+    raw_tokens = torch.zeros(n, _tokens.shape[1] + 1, dtype=torch.long)
+    raw_tokens[:, 0] = tokenizer.smiles_token
+    raw_tokens[:, 1:] = _tokens
+    tokens = torch.zeros(n, _tokens.shape[1] + 5, dtype=torch.long)
+    for i, t in enumerate((tokenizer.clip_token, tokenizer.unk_token, tokenizer.smiles_token, tokenizer.suffix_token,
+                           tokenizer.middle_token)):
+        tokens[:, i] = t
+    tokens[:, 5:] = _tokens
+    y_next = torch.zeros_like(tokens)
+    y_next[:, : (tokens.shape[1] - 1)] = tokens[:, 1:].clone()
+    y_next[:, :4] = -1
+    y_next[:, -1] = -1
+    y_next[y_next == tokenizer.pad_token] = -1
+    return raw_tokens, tokens, y_next, mask
+
+
+def _trim_columns(t, n):
+    return t[:, :n].contiguous()
 
 
 class e3gnn_smiles_clip_e2e(nn.Module):
@@ -234,6 +296,47 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         else:
             smiles_list = generation
         return (smiles_list, generation) if return_tokens else smiles_list
+
+    def _score(self, tokens, y_next, h_clip=None, raw_tokens=None):
+        """Engine.score on host-built rows: columns behind every row's last live position are dropped (their targets are -1 and,
+        under causal attention, they change no earlier logit) and the passes run on packed rows."""
+        from ...synthetic import packed_lengths
+        l_raw, l_tok = packed_lengths(raw_tokens if raw_tokens is not None else tokens, tokens, y_next)   # (l_raw unused without raw_tokens)
+        T2 = max(int(l_tok.max()), 1)
+        tokens, y_next = _trim_columns(tokens, T2), _trim_columns(y_next, T2)
+        rows = (int(l_raw.sum()), int(l_tok.sum()))
+        if raw_tokens is not None:
+            raw_tokens = self._tok(_trim_columns(raw_tokens, max(int(l_raw.max()), 1)))
+        eng = self.engine
+        nll = eng.score(self._tok(tokens), self._tok(y_next), h_clip=h_clip, raw_tokens=raw_tokens, rows=rows)
+        err = int(eng.scal[6:7].view(torch.int32).item())
+        if err & 1:
+            raise RuntimeError("Some smiles in the batch do not have stop tokens. Did some tokenizations fail?")
+        if err & 2:
+            raise RuntimeError("packed rows: the row counts passed to score() differ from what the device found in the tokens")
+        return nll
+
+    @torch.no_grad()
+    def hclip_and_tokens_to_likelihood(self, hclip: torch.Tensor, smiles, tokenizer) -> torch.Tensor:
+        """clip_e2e.py:634-665: summed NLL of [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smiles>[STOP] with hclip's special token at [UNK].
+        hclip [E] + one SMILES string -> [1] (the reference's form); hclip [B, E] + a list of B strings -> [B] in one engine call."""
+        self._sync_tokens(tokenizer)
+        single = isinstance(smiles, str)
+        h = hclip.to(self.device, torch.float32)
+        if single:
+            assert h.dim() == 1, "one SMILES string goes with one embedding [E]"
+            smiles, h = [smiles], h.unsqueeze(0)
+        assert h.dim() == 2 and h.shape[0] == len(smiles), "hclip [B, E] needs a list of B SMILES strings"
+        tokens, y_next = hclip_likelihood_tokens(list(smiles), tokenizer)
+        return self._score(tokens, y_next, h_clip=h.contiguous())
+
+    @torch.no_grad()
+    def batch_smiles_to_s2s_likelihood(self, smiles: List[str], tokenizer):
+        """clip_e2e.py:667-742: SMILES -> hclip (encode_tokens of [SMILES]<smi>[STOP]) -> SMILES round-trip NLL per molecule.
+        Returns (nll [n_ok], mask [len(smiles)]): rows that do not tokenize into n_seq - 5 positions are dropped and False in mask."""
+        self._sync_tokens(tokenizer)
+        raw_tokens, tokens, y_next, mask = s2s_likelihood_tokens(smiles, tokenizer)
+        return self._score(tokens, y_next, raw_tokens=raw_tokens), mask.to(self.device)
 
     def _sync_tokens(self, tokenizer):
         if tokenizer is None:

@@ -372,6 +372,18 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
                         const int64_t* raw_tokens, const int64_t* atoms, const float* coords, float* h_smiles,
                         float* h_e3gnn, float* scal, void* stream);
 
+/* Likelihood scoring (e3gnn_smiles_clip_e2e.hclip_and_tokens_to_likelihood / batch_smiles_to_s2s_likelihood, clip_e2e.py:634-742):
+ * nll[b] = sum over t of the autoregressive cross-entropy of tokens [B,T2] against y_next [B,T2] (-1 = ignored), with the
+ * special-token head's image of an embedding injected at the [UNK] positions.  Exactly one of raw_tokens [B,T1] (the embedding is
+ * encode_tokens of it; scal[6] bit 0 as in coati_engine_encode) and h_clip [B,E] f32 (the caller's embeddings; T1 is ignored).
+ * rows2 > 0: the decoder pass on packed rows (counts as in coati_engine_forward; with raw_tokens, rows1 > 0 as well; scal[6] bit 1 on
+ * a mismatch).  No point encoder; works without a gradient buffer; the per-sequence sums are deterministic (no float atomics).
+ * Nothing is kept for coati_engine_backward / coati_engine_logits, which refuse to run after it.  Workspace as for
+ * coati_engine_forward with A = 1. */
+int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
+                       const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
+                       float* scal, void* stream);
+
 /* logits [B*T2, ldl] f32 of the last forward (API parity with forward_dist's third return value) */
 int coati_engine_logits(coati_engine* e, float* logits, int64_t ldl, void* stream);
 
