@@ -57,6 +57,8 @@ _SIGS = {
     "coati_attn_bwd_hs": [P, P, P, P, P, P, P, P, I, I, I, I, P],
     "coati_gemm_qkv_rope_hs": [P, L, P, L, P, I, I, P, L, P, P, I, I, P],
     "coati_topk_sample": [P, L, I, I, I, F, P, P, P, I, I, P],
+    "coati_topk_sample_prompt": [P, L, I, I, I, F, P, P, L, P, I, P, P, I, I, P],
+    "coati_engine_decode_prefill": [P, P, L, P, I, P, P, L, P],
     "coati_engine_decode_begin": [P, P, L, I, I],
     "coati_engine_decode_step": [P, P, P, P, L, P],
     "coati_engine_decode_pos": [P],

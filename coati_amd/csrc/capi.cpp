@@ -229,6 +229,12 @@ int coati_topk_sample(const float* logits, int64_t ldl, int B, int V, int k, flo
                       int64_t* tokens_out, int32_t* stopped, int stop_token, int pad_token, void* stream) {
   return launch_topk_sample(logits, ldl, B, V, k, inv_temp, u, reinterpret_cast<long long*>(tokens_out), stopped, stop_token, pad_token, S_(stream));
 }
+int coati_topk_sample_prompt(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, const int64_t* prompt,
+                             int64_t ldp, const int32_t* plen, int pos, int64_t* tokens_out, int32_t* stopped, int stop_token, int pad_token,
+                             void* stream) {
+  return launch_topk_sample_prompt(logits, ldl, B, V, k, inv_temp, u, LL(prompt), ldp, plen, pos, reinterpret_cast<long long*>(tokens_out),
+                                   stopped, stop_token, pad_token, S_(stream));
+}
 int coati_batch_ncols(const int64_t* tokens, int B, int n_seq, int32_t* ncols, void* stream) {
   return launch_batch_ncols(LL(tokens), B, n_seq, ncols, S_(stream));
 }

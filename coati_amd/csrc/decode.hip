@@ -123,73 +123,73 @@ __device__ __forceinline__ float key2f(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-__global__ __launch_bounds__(256) void topk_sample_kernel(const float* __restrict__ logits, long long ldl, int V, int k,
-                                                          float inv_temp, const float* __restrict__ u,
-                                                          long long* __restrict__ tok_out, int* __restrict__ stopped,
-                                                          int stop_token, int pad_token) {
-  extern __shared__ unsigned keys[];   // [V]
-  __shared__ int hist[256];
-  __shared__ unsigned s_prefix;
-  __shared__ int s_need, s_ngt, s_neq;
-  __shared__ unsigned top_k[TOPK_MAX];
-  __shared__ int top_i[TOPK_MAX];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (stopped && stopped[b]) {
-    if (tid == 0) tok_out[b] = pad_token;
-    return;
-  }
-  for (int i = tid; i < V; i += 256) keys[i] = f2key(logits[(long long)b * ldl + i]);
-  if (tid == 0) { s_prefix = 0u; s_need = k; }
+// LDS of one row's selection (the row's keys themselves live in the kernel's dynamic LDS, [V])
+struct TopkLds {
+  int hist[256];
+  unsigned prefix;
+  int need, ngt, neq;
+  unsigned top_k[TOPK_MAX];
+  int top_i[TOPK_MAX];
+};
+
+// The selection and the draw for ONE row (the workgroup's 256 threads, all of them): returns the token in thread 0 (other
+// threads: unspecified).  Shared by topk_sample_kernel and topk_sample_prompt_kernel, so that an unforced row of the second
+// gives the very bits of the first.
+__device__ __forceinline__ int topk_sample_row(const float* __restrict__ lrow, int V, int k, float inv_temp, float uval,
+                                               unsigned* keys, TopkLds& sm) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < V; i += 256) keys[i] = f2key(lrow[i]);
+  if (tid == 0) { sm.prefix = 0u; sm.need = k; }
   __syncthreads();
   // radix select of the k-th largest key: after pass p the top 8*(p+1) bits of the threshold are known
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
     const unsigned mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    hist[tid] = 0;
+    sm.hist[tid] = 0;
     __syncthreads();
-    const unsigned prefix = s_prefix;
+    const unsigned prefix = sm.prefix;
     for (int i = tid; i < V; i += 256) {
       const unsigned key = keys[i];
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
+      if ((key & mask) == prefix) atomicAdd(&sm.hist[(key >> shift) & 255], 1);
     }
     __syncthreads();
     if (tid == 0) {
-      int need = s_need, bin = 255;
+      int need = sm.need, bin = 255;
       for (; bin > 0; --bin) {
-        if (hist[bin] >= need) break;
-        need -= hist[bin];
+        if (sm.hist[bin] >= need) break;
+        need -= sm.hist[bin];
       }
-      s_need = need;                              // rank of the threshold inside its bin
-      s_prefix = prefix | ((unsigned)bin << shift);
+      sm.need = need;                              // rank of the threshold inside its bin
+      sm.prefix = prefix | ((unsigned)bin << shift);
     }
     __syncthreads();
   }
-  const unsigned tau = s_prefix;                  // the k-th largest key; s_need = how many keys == tau belong to the top k
-  if (tid == 0) { s_ngt = 0; s_neq = 0; }
+  const unsigned tau = sm.prefix;                  // the k-th largest key; sm.need = how many keys == tau belong to the top k
+  if (tid == 0) { sm.ngt = 0; sm.neq = 0; }
   __syncthreads();
-  // survivors: every key > tau (any order), then the first s_need keys == tau in index order
+  // survivors: every key > tau (any order), then the first sm.need keys == tau in index order
   for (int i = tid; i < V; i += 256) {
     if (keys[i] > tau) {
-      const int slot = atomicAdd(&s_ngt, 1);
-      top_k[slot] = keys[i];
-      top_i[slot] = i;
+      const int slot = atomicAdd(&sm.ngt, 1);
+      sm.top_k[slot] = keys[i];
+      sm.top_i[slot] = i;
     }
   }
   __syncthreads();
   {
-    // the first s_need keys == tau in INDEX order: threads own contiguous index segments, exclusive scan of their counts
+    // the first sm.need keys == tau in INDEX order: threads own contiguous index segments, exclusive scan of their counts
     const int seg = (V + 255) / 256, i0 = tid * seg, i1 = (i0 + seg < V) ? i0 + seg : V;
     int cnt = 0;
     for (int i = i0; i < i1; ++i) cnt += (keys[i] == tau) ? 1 : 0;
-    hist[tid] = cnt;
+    sm.hist[tid] = cnt;
     __syncthreads();
     int before = 0;
-    for (int t = 0; t < tid; ++t) before += hist[t];
-    const int base = s_ngt, need = s_need;
+    for (int t = 0; t < tid; ++t) before += sm.hist[t];
+    const int base = sm.ngt, need = sm.need;
     if (cnt > 0 && before < need) {
       int pos = before;
       for (int i = i0; i < i1 && pos < need; ++i)
-        if (keys[i] == tau) { top_k[base + pos] = tau; top_i[base + pos] = i; ++pos; }
+        if (keys[i] == tau) { sm.top_k[base + pos] = tau; sm.top_i[base + pos] = i; ++pos; }
     }
   }
   __syncthreads();
@@ -197,29 +197,78 @@ __global__ __launch_bounds__(256) void topk_sample_kernel(const float* __restric
   unsigned myk = 0;
   int myi = 0, rank = 0;
   if (tid < k) {
-    myk = top_k[tid];
-    myi = top_i[tid];
+    myk = sm.top_k[tid];
+    myi = sm.top_i[tid];
     for (int j = 0; j < k; ++j) {
-      const unsigned kj = top_k[j];
-      const int ij = top_i[j];
+      const unsigned kj = sm.top_k[j];
+      const int ij = sm.top_i[j];
       rank += (kj > myk || (kj == myk && ij < myi)) ? 1 : 0;
     }
   }
   __syncthreads();
-  if (tid < k) { top_k[rank] = myk; top_i[rank] = myi; }
+  if (tid < k) { sm.top_k[rank] = myk; sm.top_i[rank] = myi; }
   __syncthreads();
+  int tok = 0;
   if (tid == 0) {
-    const float mx = key2f(top_k[0]) * inv_temp;
+    const float mx = key2f(sm.top_k[0]) * inv_temp;
     float z = 0.f;
-    for (int r = 0; r < k; ++r) z += __expf(key2f(top_k[r]) * inv_temp - mx);
-    const float target = (u ? u[b] : 0.f) * z;
+    for (int r = 0; r < k; ++r) z += __expf(key2f(sm.top_k[r]) * inv_temp - mx);
+    const float target = uval * z;
     float c = 0.f;
     int pick = k - 1;
     for (int r = 0; r < k; ++r) {
-      c += __expf(key2f(top_k[r]) * inv_temp - mx);
+      c += __expf(key2f(sm.top_k[r]) * inv_temp - mx);
       if (target < c) { pick = r; break; }
     }
-    const int tok = top_i[pick];
+    tok = sm.top_i[pick];
+  }
+  return tok;
+}
+
+__global__ __launch_bounds__(256) void topk_sample_kernel(const float* __restrict__ logits, long long ldl, int V, int k,
+                                                          float inv_temp, const float* __restrict__ u,
+                                                          long long* __restrict__ tok_out, int* __restrict__ stopped,
+                                                          int stop_token, int pad_token) {
+  extern __shared__ unsigned keys[];   // [V]
+  __shared__ TopkLds sm;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (stopped && stopped[b]) {
+    if (tid == 0) tok_out[b] = pad_token;
+    return;
+  }
+  const int tok = topk_sample_row(logits + (long long)b * ldl, V, k, inv_temp, u ? u[b] : 0.f, keys, sm);
+  if (tid == 0) {
+    tok_out[b] = tok;
+    if (stopped && tok == stop_token) stopped[b] = 1;
+  }
+}
+
+// Per-row prompts (completion of prompts of different lengths): at output position pos, row b with pos < plen[b] emits its own
+// prompt token prompt[b, pos] (no draw; a [STOP] in the prompt flags the row); otherwise a stopped row emits pad_token and a live
+// row samples exactly as topk_sample_kernel.
+__global__ __launch_bounds__(256) void topk_sample_prompt_kernel(const float* __restrict__ logits, long long ldl, int V, int k,
+                                                                 float inv_temp, const float* __restrict__ u,
+                                                                 const long long* __restrict__ prompt, long long ldp,
+                                                                 const int* __restrict__ plen, int pos,
+                                                                 long long* __restrict__ tok_out, int* __restrict__ stopped,
+                                                                 int stop_token, int pad_token) {
+  extern __shared__ unsigned keys[];   // [V]
+  __shared__ TopkLds sm;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (pos < plen[b] && pos < ldp) {
+    if (tid == 0) {
+      const long long tok = prompt[(long long)b * ldp + pos];
+      tok_out[b] = tok;
+      if (stopped && tok == stop_token) stopped[b] = 1;
+    }
+    return;
+  }
+  if (stopped && stopped[b]) {
+    if (tid == 0) tok_out[b] = pad_token;
+    return;
+  }
+  const int tok = topk_sample_row(logits + (long long)b * ldl, V, k, inv_temp, u ? u[b] : 0.f, keys, sm);
+  if (tid == 0) {
     tok_out[b] = tok;
     if (stopped && tok == stop_token) stopped[b] = 1;
   }
@@ -241,5 +290,61 @@ int launch_topk_sample(const float* logits, long long ldl, int B, int V, int k, 
   }
   hipLaunchKernelGGL(topk_sample_kernel, dim3(B), dim3(256), (size_t)V * 4, s, logits, ldl, V, k, inv_temp, u, tok_out, stopped, stop_token, pad_token);
   COATI_LAUNCH_CHECK("topk_sample");
+  return COATI_OK;
+}
+
+int launch_topk_sample_prompt(const float* logits, long long ldl, int B, int V, int k, float inv_temp, const float* u,
+                              const long long* prompt, long long ldp, const int* plen, int pos, long long* tok_out, int* stopped,
+                              int stop_token, int pad_token, hipStream_t s) {
+  COATI_CHECK_ARG(logits && tok_out && prompt && plen, "topk_sample_prompt: null operand");
+  COATI_CHECK_SHAPE(B > 0 && V > 0 && k > 0 && k <= TOPK_MAX && k <= V && (size_t)V * 4 <= 120 * 1024 && ldl >= V && ldp > 0 && pos >= 0,
+                    "topk_sample_prompt: unsupported shape B=%d V=%d k=%d ldp=%lld pos=%d", B, V, k, ldp, pos);
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_sample_prompt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
+    if (e != hipSuccess) {
+      coati_set_error("topk_sample_prompt: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+      return COATI_EHIP;
+    }
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(topk_sample_prompt_kernel, dim3(B), dim3(256), (size_t)V * 4, s, logits, ldl, V, k, inv_temp, u, prompt, ldp, plen,
+                     pos, tok_out, stopped, stop_token, pad_token);
+  COATI_LAUNCH_CHECK("topk_sample_prompt");
+  return COATI_OK;
+}
+
+// ---- prompt prefill: the rotated keys and the values of a padded [B, m] pass into the decode cache ----------------------
+// qkv: [B * m, 3C] bf16 (row b * m + t; q | k | v, q and k rotated by the QKV GEMM epilogue); cache: one layer's
+// [B][nh][Tmax][k | v].  One thread per 16-B chunk of a record (2 * hs / 8 chunks), positions 0..m-1.
+template <int DHS>
+__global__ __launch_bounds__(256) void kv_cache_fill_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ cache, int B, int m,
+                                                            int n_head, int Tmax) {
+  constexpr int CH = DHS / 8, REC = 2 * DHS;
+  const long long n = (long long)B * n_head * m * 2 * CH;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % (2 * CH));
+  const long long rec = i / (2 * CH);              // (b, h, t) with t fastest
+  const int t = (int)(rec % m);
+  const long long bh = rec / m;                    // b * n_head + h
+  const int h = (int)(bh % n_head);
+  const long long b = bh / n_head;
+  const int C = n_head * DHS;
+  const bf16_t* src = qkv + (b * m + t) * 3 * C + (c < CH ? C + h * DHS + c * 8 : 2 * C + h * DHS + (c - CH) * 8);
+  *reinterpret_cast<uint4*>(cache + (bh * Tmax + t) * REC + c * 8) = *reinterpret_cast<const uint4*>(src);
+}
+
+int launch_kv_cache_fill(const bf16_t* qkv, bf16_t* cache, int B, int m, int n_head, int head_size, int Tmax, hipStream_t s) {
+  COATI_CHECK_ARG(qkv && cache, "kv_cache_fill: null operand");
+  COATI_CHECK_SHAPE(B > 0 && n_head > 0 && m > 0 && m <= Tmax && Tmax <= 256 && (head_size == 16 || head_size == 32),
+                    "kv_cache_fill: unsupported shape B=%d nh=%d hs=%d m=%d Tmax=%d", B, n_head, head_size, m, Tmax);
+  const long long n = (long long)B * n_head * m * (head_size / 4);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (head_size == 16)
+    hipLaunchKernelGGL(kv_cache_fill_kernel<16>, grid, dim3(256), 0, s, qkv, cache, B, m, n_head, Tmax);
+  else
+    hipLaunchKernelGGL(kv_cache_fill_kernel<32>, grid, dim3(256), 0, s, qkv, cache, B, m, n_head, Tmax);
+  COATI_LAUNCH_CHECK("kv_cache_fill");
   return COATI_OK;
 }

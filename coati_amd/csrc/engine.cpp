@@ -2202,6 +2202,46 @@ int coati_engine_decode_step(coati_engine* e, const int64_t* tokens, const float
   return COATI_OK;
 }
 
+// Prompt prefill (complete_batch's prompts, smiles_xformer.py:157-198): positions 0..m-1 of every sequence as ONE padded [B, m]
+// transformer pass (xformer_fwd: the embedding, norm_embed and [UNK]-injection rules of decode_enqueue) instead of m dependent
+// steps; per layer the pass's rotated k and v go into the cache, and ln_f + the f32 lm_head run on the B rows of position m - 1
+// alone, on the decode step's own buffers.  Like coati_engine_score: nothing is saved for a backward, no training state moves.
+int coati_engine_decode_prefill(coati_engine* e, void* workspace, int64_t ws_bytes, const int64_t* tokens, int m,
+                                const float* injection, float* logits, int64_t ldl, void* stream) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens, "decode_prefill: engine not bound / null argument");
+  COATI_CHECK_ARG(e->dec.active, "decode_prefill: no decode session");
+  auto& d = e->dec;
+  const coati_config& c = e->cfg;
+  COATI_CHECK_ARG(d.pos == 0, "decode_prefill: the session is at position %d (prefill starts a fresh session)", d.pos);
+  COATI_CHECK_ARG(!c.use_fp8, "decode_prefill: not on fp8 engines (the pass would run MXFP8 products, the decode step runs bf16 ones): "
+                              "feed the prompt with decode_step");
+  COATI_CHECK_SHAPE(m >= 1 && m <= d.Tmax, "decode_prefill: unsupported prompt length m=%d (Tmax=%d)", m, d.Tmax);
+  COATI_CHECK_ARG(!logits || ldl >= c.n_tok, "decode_prefill: ldl too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = d.B, C = c.n_hidden_xformer, L = c.n_layer_xformer, hs = C / c.n_head;
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)ws_bytes, false};
+  const size_t need = carve(e, ar, B, 1, m, 1, B);
+  COATI_CHECK_ARG((int64_t)need <= ws_bytes, "decode_prefill: workspace too small (%zu > %lld)", need, (long long)ws_bytes);
+  if (e->nce) e->nce_cap = ((size_t)ws_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = 1; e->T2 = m; e->A = 1;
+  e->p1.idx = nullptr;
+  e->p2.idx = reinterpret_cast<const long long*>(tokens);
+  e->have_fwd = false;
+  e->decoder_pending = false;
+  e->have_ws = true;
+  COATI_TRY(xformer_fwd(e, e->p2, injection, s));
+  for (int l = 0; l < L; ++l)
+    COATI_TRY(launch_kv_cache_fill(e->p2.qkv[l], d.cache + (size_t)l * B * C * d.Tmax * 2, B, m, c.n_head, hs, d.Tmax, s));
+  if (logits) {
+    COATI_TRY(launch_layernorm_fwd(e->p2.x[L] + (size_t)(m - 1) * C, (long long)m * C, e->P + e->lnfw, e->P + e->lnfb, d.af, C, nullptr, 0,
+                                   d.mean, d.rstd, B, C, s));
+    COATI_TRY(gemm(e, SITE_NONE, d.af, 0, C, e->S + e->lmhead, C, B, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
+  }
+  COATI_TRY(launch_add_int(d.pos_dev, m, 1, s));   // a captured decode graph continues from position m
+  d.pos = m;
+  return COATI_OK;
+}
+
 // Capture the decode step (embedding .. logits + position increment, ~115 launches) into two HIP graphs (without / with
 // the [UNK]-slot injection).  The launch-bound small-batch step then costs one hipGraphLaunch.  Call after decode_begin;
 // a dry, un-captured step runs first so that every one-time kernel attribute is set outside the capture (it writes the

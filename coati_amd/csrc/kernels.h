@@ -313,6 +313,12 @@ int launch_attn_decode(const bf16_t* qkv, bf16_t* cache, bf16_t* y, int B, int n
 int launch_add_int(int* x, int v, int set, hipStream_t s);
 int launch_topk_sample(const float* logits, long long ldl, int B, int V, int k, float inv_temp, const float* u,
                        long long* tok_out, int* stopped, int stop_token, int pad_token, hipStream_t s);
+// per-row prompts: rows with pos < plen[b] emit prompt[b * ldp + pos] (no draw), the others sample as launch_topk_sample
+int launch_topk_sample_prompt(const float* logits, long long ldl, int B, int V, int k, float inv_temp, const float* u,
+                              const long long* prompt, long long ldp, const int* plen, int pos, long long* tok_out, int* stopped,
+                              int stop_token, int pad_token, hipStream_t s);
+// prompt prefill: the rotated k and the v of a padded [B, m] pass's qkv into one layer's cache [B][nh][Tmax][k|v], positions 0..m-1
+int launch_kv_cache_fill(const bf16_t* qkv, bf16_t* cache, int B, int m, int n_head, int head_size, int Tmax, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

@@ -5,7 +5,7 @@ shadows, workspace); the C library only borrows pointers while it enqueues kerne
 import ctypes
 import math
 from dataclasses import dataclass, asdict
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 
@@ -47,6 +47,23 @@ import os as _os
 PACK_ROWS = _os.environ.get("COATI_PACK_ROWS", "1") != "0"
 
 SCAL_AR_SUM, SCAL_AR_COUNT, SCAL_CLIP1, SCAL_CLIP2, SCAL_NVALID, SCAL_GRADNORM, SCAL_ERR = 0, 1, 2, 3, 4, 5, 6
+
+
+def pack_prompts(prefix: List[List[int]], n_seq: int):
+    """Host-side packing of per-row prompts for coati_topk_sample_prompt: prompt [B, n_seq] int64 (row b = prefix[b], zero-filled)
+    and plen [B] int32 (the prompt lengths).  Every prompt needs 1 .. n_seq tokens."""
+    B = len(prefix)
+    if B == 0:
+        raise ValueError("no prompts")
+    prompt = torch.zeros(B, n_seq, dtype=torch.long)
+    plen = torch.empty(B, dtype=torch.int32)
+    for b, row in enumerate(prefix):
+        n = len(row)
+        if not 1 <= n <= n_seq:
+            raise ValueError(f"prompt {b} has {n} tokens; 1 .. n_seq = {n_seq} fit")
+        prompt[b, :n] = torch.tensor([int(t) for t in row], dtype=torch.long)
+        plen[b] = n
+    return prompt, plen
 
 
 ERR_Z_MESSAGE = "torch_emb: an atomic number above 83 has no row in nn.Embedding(84, H) (e3gnn_clip.py:113-115)"
@@ -426,6 +443,29 @@ class Engine:
         _lib.check(self.l.coati_engine_decode_step(self.h, ptr(tokens), ptr(inj), ptr(logits), ld, stream()), "decode_step")
         return logits[:, :V] if want_logits else None
 
+    def decode_prefill(self, tokens, injection=None, want_logits=True):
+        """Positions 0..m-1 of a fresh session (decode_begin) in ONE transformer pass over tokens [B, m] int64 instead of m
+        decode_step calls; rows equal to the [UNK] id read `injection` [B, C] as in decode_step.  Returns the logits
+        [B, n_tok] f32 of position m - 1 (or None); the session continues at position m.  Uses the engine's step workspace
+        (nothing is kept for a backward); refused on fp8 engines (the step's products are bf16)."""
+        B = self._dec_B
+        tokens = tokens.to(self.device, torch.long).contiguous()
+        assert tokens.dim() == 2 and tokens.shape[0] == B, tokens.shape
+        m = int(tokens.shape[1])
+        inj = None
+        if injection is not None:
+            inj = injection.to(self.device, torch.float32).contiguous()
+            assert inj.shape == (B, self.cfg.n_hidden_xformer)
+        self._ensure_workspace(B, 1, m, 1)
+        V = self.cfg.n_tok
+        ld = (V + 7) // 8 * 8
+        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
+        self._keep = (tokens, inj)
+        _lib.check(self.l.coati_engine_decode_prefill(self.h, ptr(self.workspace), self.workspace.numel(), ptr(tokens), m, ptr(inj),
+                                                      ptr(logits), ld, stream()), "decode_prefill")
+        self._shape = None
+        return logits[:, :V] if want_logits else None
+
     def decode_graph_build(self):
         """Capture the decode step into HIP graphs (call inside `with torch.cuda.stream(side_stream)`)."""
         _lib.check(self.l.coati_engine_decode_graph_build(self.h, stream()), "decode_graph_build")
@@ -480,6 +520,77 @@ class Engine:
         if as_tensor:
             return torch.cat([torch.tensor(prefix, dtype=torch.long, device=dev).unsqueeze(0).repeat(B, 1), gen], dim=1)
         return [prefix + row for row in gen.tolist()]
+
+    def generate_topk_batch(self, prefix, stop_token, pad_token=0, inv_temp=2, k=10, generator=None, prefill=True):
+        """RotarySmilesTransformer.generate_topk_batch (smiles_xformer.py:157-198): continue B prompts of different lengths
+        (token lists) on the KV-cached decode path.  Returns B lists of n_seq ints: every prompt verbatim, each row sampled
+        from its own prompt end (softmax(top-k logits * inv_temp), uniforms from `generator`), [STOP] and then pad_token,
+        zeros behind the last written column.  The loop ends when every row has stopped or column n_seq - 1 is written.
+        prefill=True runs the shortest prompt's length as one pass (decode_prefill); the longer prompts' remaining tokens,
+        and with prefill=False every prompt token behind the first, are fed through forced steps."""
+        out, _ = self._complete(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, None)
+        return out.tolist()
+
+    def generate_topk_with_inj(self, prefix, stop_token, inv_temp=1, k=50, inj_token=None, inj_payload=None, generator=None,
+                               prefill=True):
+        """RotarySmilesTransformer.generate_topk_with_inj (smiles_xformer.py:215-270): one prompt (token list) whose
+        inj_token slot carries inj_payload ([C], or a scalar that fills all C channels, as the reference's assignment
+        broadcasts it); sampling stops on stop_token or after n_seq - 1 generated tokens.  Returns prefix + generated.
+        A sequence that has not stopped within n_seq positions is returned at n_seq positions (the reference raises)."""
+        prefix = [int(t) for t in prefix]
+        C = self.cfg.n_hidden_xformer
+        inj = None
+        if inj_token is not None:
+            if int(inj_token) != self.cfg.unk_token:
+                raise NotImplementedError("the injection slot must be the engine's [UNK] id")
+            if int(inj_token) not in prefix:
+                raise ValueError(f"{inj_token} is not in the prefix")
+            p = torch.as_tensor(inj_payload).to(self.device, torch.float32).reshape(-1)
+            if p.numel() == 1:
+                p = p.expand(C)
+            assert p.numel() == C, f"inj_payload: {p.numel()} values for {C} channels"
+            inj = p.reshape(1, C).contiguous()
+        out, n = self._complete([prefix], stop_token, 0, inv_temp, k, generator, prefill, inj)
+        return out[0, :n].tolist()
+
+    def _complete(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection):
+        """The decode loop of generate_topk_batch / generate_topk_with_inj on a private stream.  Returns (tokens [B, n_seq] on
+        the host, number of columns written)."""
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            out = self._complete_on_stream(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        return out
+
+    def _complete_on_stream(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection):
+        n_seq = int(self.cfg.n_seq)
+        prompt, plen = pack_prompts(prefix, n_seq)
+        B = prompt.shape[0]
+        m, longest = int(plen.min()), int(plen.max())
+        dev = self.device
+        prompt_d, plen_d = prompt.to(dev), plen.to(dev)
+        out = torch.zeros(B, n_seq, dtype=torch.long, device=dev)
+        out[:, :m] = prompt_d[:, :m]
+        stopped = (prompt[:, :m] == int(stop_token)).any(1).to(torch.int32).to(dev)
+        self.decode_begin(B, n_seq)
+        if prefill and not self.cfg.fp8:
+            logits = self.decode_prefill(prompt_d[:, :m], injection)
+            pos = m
+        else:   # (fp8 engines: the prompt goes through forced steps)
+            logits = self.decode_step(out[:, 0], injection)
+            pos = 1
+        while pos < n_seq:
+            u = torch.rand(B, device=dev, generator=generator) if k > 1 else torch.zeros(B, device=dev)
+            nxt = torch.empty(B, dtype=torch.long, device=dev)
+            _lib.call("coati_topk_sample_prompt", ptr(logits), logits.stride(0), B, self.cfg.n_tok, int(k), float(inv_temp), ptr(u),
+                      ptr(prompt_d), n_seq, ptr(plen_d), pos, ptr(nxt), ptr(stopped), int(stop_token), int(pad_token), stream())
+            out[:, pos] = nxt
+            pos += 1
+            if pos >= n_seq or (pos >= longest and int(stopped.sum().item()) >= B):
+                break
+            logits = self.decode_step(nxt, injection)
+        return out.cpu(), pos
 
     # ---- profiling ---------------------------------------------------------------------------------------------
     def site_names(self):

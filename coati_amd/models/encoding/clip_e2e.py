@@ -183,6 +183,9 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         self.xformer.n_seq, self.xformer.n_tok, self.xformer.n_embd = n_seq, n_tok, n_hidden_xformer
         # generation entry point of the reference's RotarySmilesTransformer (smiles_xformer.py:272-351), KV-cached here
         object.__setattr__(self.xformer, "generate_top_k_with_inj_batch", eng.generate_top_k_with_inj_batch)
+        # prompt completion and one-sequence generation (smiles_xformer.py:157-198, 215-270): prompt prefill + per-row prompts
+        object.__setattr__(self.xformer, "generate_topk_batch", eng.generate_topk_batch)
+        object.__setattr__(self.xformer, "generate_topk_with_inj", eng.generate_topk_with_inj)
         self.point_encoder.hidden_nf = n_hidden_e3nn
         self.use_point_encoder = bool(use_point_encoder)
         if not token_mlp:
@@ -296,6 +299,54 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         else:
             smiles_list = generation
         return (smiles_list, generation) if return_tokens else smiles_list
+
+    @torch.no_grad()
+    def points_to_2d_batch(self, atom_batch, coords_batch, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
+                           do_suffix: bool = False, inv_temp: float = 2, k=100, keep_special=False, generator=None):
+        """clip_e2e.py:590-632: encode_points, then the hclip_to_2d_batch flow (noise added out of place)."""
+        h_clip = self.encode_points(atom_batch, coords_batch)
+        return self.hclip_to_2d_batch(h_clip, tokenizer, fill_in_from=fill_in_from, noise_scale=noise_scale, inv_temp=inv_temp, k=k,
+                                      do_suffix=do_suffix, keep_special=keep_special, generator=generator)
+
+    def _to_2d_one(self, h_clip, tokenizer, fill_in_from, noise_scale, suffix, inv_temp, k, generator):
+        """hclip_to_2d / points_to_2d: the special token of h_clip injected as the reference does it, h_token[0] -- the first row of a
+        [B, E] input, and for a 1-D [E] input its first CHANNEL, a scalar that the reference's assignment spreads over all C."""
+        self._sync_tokens(tokenizer)
+        assert fill_in_from in ("[SMILES]", "[GRAPH]")
+        h = h_clip.to(self.device, torch.float32)
+        if noise_scale > 0:
+            h = h + noise_scale * torch.randn_like(h)
+        h_token = self.special_tokens_from_clip(h if h.dim() == 2 else h.reshape(1, -1))
+        payload = h_token[0] if h.dim() == 2 else h_token[0, 0]
+        prefix = tokenizer.tokenize_text("[CLIP][UNK]" + fill_in_from + suffix, pad=False)
+        generation = self.engine.generate_topk_with_inj(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
+                                                        inj_token=tokenizer.unk_token, inj_payload=payload, generator=generator)
+        return tokenizer.decode(generation, special=False) if fill_in_from == "[SMILES]" else tokenizer.decode(generation)
+
+    @torch.no_grad()
+    def points_to_2d(self, atoms, coords, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0, inv_temp: float = 2,
+                     k: int = 100, generator=None):
+        """clip_e2e.py:465-501: one molecule's atoms / coords -> SMILES (prefix [CLIP][UNK]<fill_in_from>[SUFFIX][MIDDLE])."""
+        h_clip = self.encode_points(atoms, coords)
+        return self._to_2d_one(h_clip, tokenizer, fill_in_from, noise_scale, "[SUFFIX][MIDDLE]", inv_temp, k, generator)
+
+    @torch.no_grad()
+    def hclip_to_2d(self, h_clip, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0, do_suffix: bool = False,
+                    inv_temp: float = 2, k: int = 100, generator=None):
+        """clip_e2e.py:503-542: one embedding ([1, E] or [E]) -> SMILES (prefix [CLIP][UNK]<fill_in_from>, + [SUFFIX][MIDDLE])."""
+        return self._to_2d_one(h_clip, tokenizer, fill_in_from, noise_scale, "[SUFFIX][MIDDLE]" if do_suffix else "", inv_temp, k,
+                               generator)
+
+    @torch.no_grad()
+    def complete_batch(self, prefixes: List[str], tokenizer, inv_temp: float = 2, k: int = 100, keep_special: bool = False,
+                       de_fim: bool = True, generator=None):
+        """clip_e2e.py:744-770: continue text prompts of different lengths (e.g. fill-in-middle [SMILES]..[SUFFIX]..[MIDDLE]);
+        no injection.  Returns the decoded strings."""
+        self._sync_tokens(tokenizer)
+        tokens = [tokenizer.tokenize_text(p, pad=False) for p in prefixes]
+        generation = self.engine.generate_topk_batch(prefix=tokens, stop_token=tokenizer.stop_token, pad_token=tokenizer.pad_token,
+                                                     inv_temp=inv_temp, k=k, generator=generator)
+        return [tokenizer.decode(t, special=keep_special, de_fim=de_fim) for t in generation]
 
     def _score(self, tokens, y_next, h_clip=None, raw_tokens=None):
         """Engine.score on host-built rows: columns behind every row's last live position are dropped (their targets are -1 and,

@@ -217,6 +217,12 @@ int coati_silu(const float* x, float* y, int64_t n, void* stream);
 int coati_attn_decode(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int Tmax, int pos, void* stream);
 int coati_topk_sample(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u,
                       int64_t* tokens_out, int32_t* stopped, int stop_token, int pad_token, void* stream);
+/* the same with a prompt per row (completion of prompts of different lengths): at output position pos, a row with
+   pos < plen[b] emits prompt[b * ldp + pos] without a draw (a stop_token there flags the row), a stopped row emits pad_token,
+   any other row samples exactly as coati_topk_sample (same logits and u -> the same token) */
+int coati_topk_sample_prompt(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, const int64_t* prompt,
+                             int64_t ldp, const int32_t* plen, int pos, int64_t* tokens_out, int32_t* stopped, int stop_token, int pad_token,
+                             void* stream);
 
 /* E(3)-GNN pieces (e3gnn_clip.py:108-137, e_gcl_sparse.py) -- see csrc/gnn.hip for the dense-edge formulation */
 int coati_gnn_embed(const int64_t* atoms, const int32_t* lut_ix, const int32_t* lut_iy, const float* W,
@@ -431,6 +437,14 @@ int coati_engine_decode_begin(coati_engine* e, void* workspace, int64_t ws_bytes
 int coati_engine_decode_step(coati_engine* e, const int64_t* tokens, const float* injection, float* logits, int64_t ldl,
                              void* stream);
 int coati_engine_decode_pos(coati_engine* e);
+/* prompt prefill: positions 0..m-1 of the session (which must be at position 0) in ONE transformer pass over the padded
+   tokens[B, m] (same embedding / norm_embed / [UNK]-injection rules as decode_step) instead of m steps; the rotated keys and
+   the values land in the cache, logits (optional) [B, n_tok] f32 (row stride ldl) are those of position m - 1, and the session
+   continues at position m (the graph replay's device position as well).  workspace / ws_bytes: a training-step workspace for
+   (B, T1 = 1, T2 = m) -- coati_engine_workspace_bytes(e, B, 1, m, 1, B); nothing is kept for a backward.  Refused on fp8
+   engines: the decode step's products run on the bf16 shadows, the pass would run MXFP8 ones. */
+int coati_engine_decode_prefill(coati_engine* e, void* workspace, int64_t ws_bytes, const int64_t* tokens, int m,
+                                const float* injection, float* logits, int64_t ldl, void* stream);
 /* the same step captured into HIP graphs (one hipGraphLaunch instead of ~115 kernel launches; pays off at small batch).
    graph_build: after decode_begin, on an explicit stream.  graph_step: tokens[B] / injection[B, C] (device) are copied
    into the session's fixed input buffers; *logits_out points at the session's logits [B, n_tok] (row stride *ldl_out),
