@@ -51,6 +51,7 @@ _SIGS = {
     "coati_scatter_rows_add": [P, P, P, I, I, I, P],
     "coati_bad_rows": [P, P, I, I, P],
     "coati_silu": [P, P, L, P],
+    "coati_swiglu": [P, L, P, L, I, I, P],
     "coati_attn_decode": [P, P, P, I, I, I, I, P],
     "coati_attn_decode_hs": [P, P, P, I, I, I, I, I, P],
     "coati_attn_fwd_hs": [P, P, P, I, I, I, I, P],
@@ -81,6 +82,8 @@ _SIGS = {
     "coati_grad_sqnorm": [P, L, P, I, P, F, P, P],
     "coati_adamw": [P, P, P, P, P, L, F, F, F, F, F, I, P, F, P],
     "coati_engine_create": [POINTER(CoatiConfig), POINTER(c_void_p)],
+    "coati_engine_create_coati2": [POINTER(CoatiConfig), I, POINTER(c_void_p)],
+    "coati_engine_token_head": [P, P, L, I, P, P, P],
     "coati_engine_entry": [P, I, c_char_p, I, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)],
     "coati_engine_bind": [P, P, P, P, P, P, P, P, P, P],
     "coati_engine_refresh_shadows": [P, P],

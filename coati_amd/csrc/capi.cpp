@@ -219,6 +219,9 @@ int coati_bad_rows(const int64_t* tokens, uint8_t* bad, int B, int T, void* stre
   return launch_bad_rows(LL(tokens), bad, B, T, S_(stream));
 }
 int coati_silu(const float* x, float* y, int64_t n, void* stream) { return launch_silu_fwd(x, y, n, S_(stream)); }
+int coati_swiglu(const float* u, int64_t ldu, float* g, int64_t ldg, int B, int N, void* stream) {
+  return launch_swiglu(u, ldu, g, ldg, B, N, S_(stream));
+}
 int coati_attn_decode(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int Tmax, int pos, void* stream) {
   return launch_attn_decode(qkv, cache, y, B, n_head, 16, Tmax, pos, nullptr, S_(stream));
 }

@@ -125,6 +125,11 @@ struct coati_engine {
   std::vector<GLayerP> gl;
   int64_t gembw = 0, gembb = 0, gd0w = 0, gd0b = 0, gd3w = 0, gd3b = 0, gd0T = 0, gd3T = 0;
   int64_t p2c_lnw = 0, p2c_lnb = 0, p2c_w = 0, p2c_b = 0, s2c_lnw = 0, s2c_lnb = 0, s2c_w = 0, s2c_b = 0, tokw = 0, tokb = 0;
+  // COATI2 (coati_engine_create_coati2): enc_to_coati = 0 linear / 1 swiglu_mlp / 2 swiglu_resnet, -1 = the COATI1 model.  The linear
+  // smiles_to_coati is LayerNorm -> Linear on the s2c_* offsets (smiles_head_fwd); the SwiGLU heads use Coati2Head
+  int enc_to_coati = -1;
+  struct Coati2Head { int64_t lnw = 0, lnb = 0, w1 = 0, b1 = 0, w2 = 0, b2 = 0; bool residual = false; } c2s, c2t;
+  float* c2_u = nullptr;   // [B, 2E] scratch: the first Linear of a SwiGLU head
   // bound buffers
   float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;
   bf16_t* S = nullptr;
@@ -263,9 +268,13 @@ int64_t add_shadow(coati_engine* e, int64_t n) {
   return off;
 }
 
+void build_layout_coati1_heads(coati_engine* e);
+void build_layout_coati2_heads(coati_engine* e);
+void build_layout_shadows(coati_engine* e);
+
 void build_layout(coati_engine* e) {
   const coati_config& c = e->cfg;
-  const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn, E = c.n_embd_common, V = c.n_tok;
+  const int C = c.n_hidden_xformer, V = c.n_tok;
   e->Vpad = (V + 63) & ~63;
   // --- transformer (smiles_xformer.py:71-100, basic_transformer.py:103-169) ---
   if (c.norm_embed) {   // tok_emb = Sequential(Embedding, LayerNorm) (basic_transformer.py:72-76)
@@ -294,6 +303,15 @@ void build_layout(coati_engine* e) {
   }
   e->lnfw = add_entry(e, "xformer.transformer.ln_f.weight", C, 0);
   e->lnfb = add_entry(e, "xformer.transformer.ln_f.bias", C, 0);
+  if (e->enc_to_coati >= 0) build_layout_coati2_heads(e);
+  else build_layout_coati1_heads(e);
+  build_layout_shadows(e);
+}
+
+// COATI1 (clip_e2e.py:381-435): point encoder, lm_head, point_to_clip, smiles_to_clip, point_clip_to_special_tokens
+void build_layout_coati1_heads(coati_engine* e) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn, E = c.n_embd_common, V = c.n_tok;
   // Order of the flat buffers (round 4; entries are found by NAME everywhere, tests/test_host_cpu.py): transformer body | point
   // encoder | lm_head | heads.  The data-parallel step then needs TWO gradient collectives instead of four: lm_head + heads are final
   // behind the decoder stage of the backward and adjacent, transformer body + point encoder behind the encoder stage and adjacent
@@ -384,7 +402,40 @@ void build_layout(coati_engine* e) {
     g.c0b = add_entry(e, p + "coord_mlp.0.bias", H, 0);
     g.c2w = add_entry(e, p + "coord_mlp.2.weight", 1, H);
   }
+}
 
+// COATI2 (simple_coati2/transformer_only.py:71-104): lm_head, smiles_to_coati, coati_to_token; no point encoder
+void build_layout_coati2_heads(coati_engine* e) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, E = c.n_embd_common, V = c.n_tok;
+  e->lmhead = add_entry(e, "xformer.lm_head.weight", V, C);
+  auto swiglu_head = [&](coati_engine::Coati2Head& h, const std::string& p, int i_ln, int i_w1, int i_w2, int d_in, bool residual) {
+    h.lnw = add_entry(e, p + std::to_string(i_ln) + ".weight", d_in, 0);
+    h.lnb = add_entry(e, p + std::to_string(i_ln) + ".bias", d_in, 0);
+    h.w1 = add_entry(e, p + std::to_string(i_w1) + ".weight", 2 * E, d_in);
+    h.b1 = add_entry(e, p + std::to_string(i_w1) + ".bias", 2 * E, 0);
+    h.w2 = add_entry(e, p + std::to_string(i_w2) + ".weight", E, E);
+    h.b2 = add_entry(e, p + std::to_string(i_w2) + ".bias", E, 0);
+    h.residual = residual;
+  };
+  if (e->enc_to_coati == 0) {   // Sequential(LayerNorm(E), Linear(C, E)): the norm_clips head of COATI1 (E == C)
+    e->s2c_lnw = add_entry(e, "smiles_to_coati.0.weight", E, 0);
+    e->s2c_lnb = add_entry(e, "smiles_to_coati.0.bias", E, 0);
+    e->s2c_w = add_entry(e, "smiles_to_coati.1.weight", E, C);
+    e->s2c_b = add_entry(e, "smiles_to_coati.1.bias", E, 0);
+  } else if (e->enc_to_coati == 1) {   // Sequential(LayerNorm(C), Linear(C, 2E), SwiGLU, Linear(E, E))
+    swiglu_head(e->c2s, "smiles_to_coati.", 0, 1, 3, C, false);
+  } else {   // SwiGLUResNet(C, E): net = Sequential(LayerNorm, Dropout, Linear, SwiGLU, Linear), + x
+    swiglu_head(e->c2s, "smiles_to_coati.net.", 0, 2, 4, C, true);
+  }
+  swiglu_head(e->c2t, "coati_to_token.net.", 0, 2, 4, E, true);
+  e->n_trainable = e->n_params;
+}
+
+// hidden zero biases, the shadow extras, the job table of the shadow refresh
+void build_layout_shadows(coati_engine* e) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn, V = c.n_tok;
   // biases = 0 (basic_transformer.py:113-115, 166-168 with config.biases = False): the four Linear layers of a block have no bias
   // PARAMETER -- nothing in the table, nothing in the state_dict -- but every kernel of the path takes a bias pointer: it points at
   // zeros behind n_trainable (never updated, never decayed, outside the clip-norm; the gradient sums written there are ignored)
@@ -414,8 +465,10 @@ void build_layout(coati_engine* e) {
     g.n3T = add_shadow(e, (int64_t)H * H);
     g.n0p = c.residual ? add_shadow(e, (int64_t)2 * H * H) : -1;
   }
-  e->gd0T = add_shadow(e, (int64_t)H * H);
-  e->gd3T = add_shadow(e, (int64_t)H * H);
+  if (e->enc_to_coati < 0) {
+    e->gd0T = add_shadow(e, (int64_t)H * H);
+    e->gd3T = add_shadow(e, (int64_t)H * H);
+  }
 
   // fp8 mode: MXFP8 weight copies.  index 0..3 = natural [N, K] of attn / proj / fc1 / fc2 (forward products), 4..7 = the
   // transposed copies [K_in, N_out] (input-gradient products: the contraction runs over the layer's outputs)
@@ -452,8 +505,10 @@ void build_layout(coati_engine* e) {
     if (c.residual) job(w.n0w, 2 * H + 28, w.n0p, 2 * H, H, 2 * H, 0);   // (rows 2H + 28 apart are not 16-B aligned: the product reads a packed copy)
     job(w.n3w, H, w.n3T, H, H, H, 1);
   }
-  job(e->gd0w, H, e->gd0T, H, H, H, 1);
-  job(e->gd3w, H, e->gd3T, H, H, H, 1);
+  if (e->enc_to_coati < 0) {
+    job(e->gd0w, H, e->gd0T, H, H, H, 1);
+    job(e->gd3w, H, e->gd3T, H, H, H, 1);
+  }
 }
 
 // ---- profiling wrapper ---------------------------------------------------------------------------------
@@ -686,6 +741,7 @@ size_t carve(coati_engine* e, Arena& ar, int B_, int T1_, int T2_, int A_, int B
   e->ones = ar.take<float>(B);
   e->stop_pos = ar.take<int>(B);
   e->err_flag = ar.take<int>(4);
+  if (e->enc_to_coati >= 0) e->c2_u = ar.take<float>((size_t)B * 2 * E);
   // lm head
   const int tiles_v = cdiv(c.n_tok, 64);   // one (max, sum) pair per 64 columns: either GEMM kernel fits
   e->ce_partial = ar.take<float2>(M2 * tiles_v);
@@ -1420,6 +1476,19 @@ int smiles_head_fwd(coati_engine* e, float* out, hipStream_t s) {
   return launch_sgemm(x, C, 1, e->P + e->s2c_w, 1, C, out, E, B, E, C, e->P + e->s2c_b, 1.f, 0, s);
 }
 
+// a SwiGLU head of COATI2 (simple_coati2/transformer_only.py:19-42, 88-101) on [B, K] f32 rows x: LayerNorm -> Linear(K -> 2E) -> SwiGLU ->
+// Linear(E -> E) (+ x).  Every product is the exact-f32 sgemm without accumulation; the residual is a separate axpy (out must not overlap x)
+int coati2_head_fwd(coati_engine* e, const coati_engine::Coati2Head& h, const float* x, float* out, int B, hipStream_t s) {
+  const int C = e->cfg.n_hidden_xformer, E = e->cfg.n_embd_common;   // (E == C: the input width either way)
+  const float* P = e->P;
+  COATI_TRY(launch_layernorm_fwd(x, C, P + h.lnw, P + h.lnb, nullptr, 0, e->hs_ln, C, e->hs_mean, e->hs_rstd, B, C, s));
+  COATI_TRY(launch_sgemm(e->hs_ln, C, 1, P + h.w1, 1, C, e->c2_u, 2 * E, B, 2 * E, C, P + h.b1, 1.f, 0, s));
+  COATI_TRY(launch_swiglu(e->c2_u, 2 * E, e->sa, E, B, E, s));
+  COATI_TRY(launch_sgemm(e->sa, E, 1, P + h.w2, 1, E, out, E, B, E, E, P + h.b2, 1.f, 0, s));
+  if (h.residual) COATI_TRY(launch_axpy(x, out, 1.f, (long long)B * E, s));
+  return COATI_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1440,6 +1509,37 @@ int coati_engine_create(const coati_config* cfg, coati_engine** out) {
   COATI_CHECK_SHAPE(!(cfg->old_architecture && cfg->norm_clips) || H == E, "engine_create: old_architecture needs n_hidden_e3nn == n_embd_common (%d, %d): point_to_clip's LayerNorm is sized by the one and applied to the other (clip_e2e.py:410-413)", H, E);
   coati_engine* e = new coati_engine();
   e->cfg = *cfg;
+  build_layout(e);
+  *out = e;
+  return COATI_OK;
+}
+
+int coati_engine_create_coati2(const coati_config* cfg, int enc_to_coati, coati_engine** out) {
+  COATI_CHECK_ARG(cfg && out, "engine_create_coati2: null argument");
+  COATI_CHECK_ARG(enc_to_coati >= 0 && enc_to_coati <= 2, "engine_create_coati2: enc_to_coati must be 0 (linear), 1 (swiglu_mlp) or 2 (swiglu_resnet), not %d",
+                  enc_to_coati);
+  COATI_CHECK_ARG(!cfg->use_point_encoder, "engine_create_coati2: COATI2 has no point encoder (use_point_encoder must be 0)");
+  COATI_CHECK_ARG(!cfg->use_fp8, "engine_create_coati2: fp8 is not available for COATI2");
+  COATI_CHECK_ARG(!cfg->norm_embed, "engine_create_coati2: the COATI2 transformer has no norm_embed");
+  const int C = cfg->n_hidden_xformer, E = cfg->n_embd_common;
+  COATI_CHECK_SHAPE(E == C, "engine_create_coati2: embed_dim (%d) must equal n_hidden_xformer (%d)", E, C);
+  // the point-encoder and clip-head fields do not apply: the copy the engine keeps has no point encoder (no GNN buffers) and
+  // norm_clips set, which makes smiles_head_fwd the LayerNorm -> Linear of the linear smiles_to_coati
+  coati_config c = *cfg;
+  c.n_layer_e3gnn = 0;
+  c.n_hidden_e3nn = C;
+  c.norm_clips = 1;
+  c.token_mlp = 0;
+  c.torch_emb = 0;
+  c.old_architecture = 0;
+  c.residual = 0;
+  COATI_CHECK_SHAPE(c.n_head > 0 && (C == c.n_head * 16 || C == c.n_head * 32), "engine_create_coati2: head size must be 16 or 32 (C=%d, n_head=%d)", C, c.n_head);
+  COATI_CHECK_SHAPE(C % 64 == 0 && C <= 1024, "engine_create_coati2: n_hidden_xformer=%d must be a multiple of 64 (<=1024)", C);
+  COATI_CHECK_SHAPE(c.n_seq > 0 && c.n_seq <= 256 && c.n_tok > 8, "engine_create_coati2: n_seq must be <= 256");
+  COATI_CHECK_SHAPE(c.n_layer_xformer >= 1, "engine_create_coati2: bad layer count");
+  coati_engine* e = new coati_engine();
+  e->cfg = c;
+  e->enc_to_coati = enc_to_coati;
   build_layout(e);
   *out = e;
   return COATI_OK;
@@ -1596,6 +1696,7 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
                          float* h_smiles, uint8_t* bad_rows, float* scal, int train, int64_t rows1, int64_t rows2, void* stream) {
   COATI_CHECK_ARG(e && e->P && e->S, "engine_forward: engine not bound");
   COATI_CHECK_ARG(workspace && raw_tokens && tokens && atoms && coords && use_point && scal, "engine_forward: null argument");
+  COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_forward: a COATI2 engine is inference-only (no training step)");
   const bool stop_after_heads = (train & 2) != 0;   // train | 2: return behind the heads, coati_engine_forward_decoder runs the rest
   train &= 1;
   COATI_CHECK_ARG(!train || (e->G && y_next), "engine_forward: training needs grads and y_next");
@@ -1692,7 +1793,8 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
 }
 
 int coati_engine_forward_decoder(coati_engine* e, void* stream) {
-  COATI_CHECK_ARG(e && e->decoder_pending, "engine_forward_decoder: no forward stopped behind the heads (train | 2)");
+  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_forward_decoder: a COATI2 engine is inference-only (no training step)");
+  COATI_CHECK_ARG(e->decoder_pending, "engine_forward_decoder: no forward stopped behind the heads (train | 2)");
   e->decoder_pending = false;
   return forward_decoder_impl(e, (hipStream_t)stream);
 }
@@ -1707,6 +1809,7 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
   COATI_CHECK_ARG((raw_tokens && h_smiles) || (atoms && coords && h_e3gnn), "engine_encode: nothing to encode");
   const coati_config& c = e->cfg;
   const bool do_tok = raw_tokens && h_smiles, do_pts = atoms && coords && h_e3gnn;
+  COATI_CHECK_ARG(e->enc_to_coati < 0 || !do_pts, "engine_encode: a COATI2 engine has no point encoder (encode raw_tokens only)");
   if (!do_tok) T1 = 1;
   if (!do_pts) A = 1;
   COATI_CHECK_SHAPE(B > 0 && T1 > 0 && A > 0 && T1 <= c.n_seq, "engine_encode: unsupported shape B=%d T1=%d A=%d", B, T1, A);
@@ -1735,10 +1838,30 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
     COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
     COATI_TRY(launch_find_stop(e->p1.idx, c.stop_token, e->stop_pos, e->err_flag, B, T1, s));
     COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s));
-    COATI_TRY(smiles_head_fwd(e, h_smiles, s));
+    if (e->enc_to_coati > 0) COATI_TRY(coati2_head_fwd(e, e->c2s, e->hstop, h_smiles, B, s));   // COATI2 SwiGLU smiles_to_coati
+    else COATI_TRY(smiles_head_fwd(e, h_smiles, s));
     HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
   }
   return COATI_OK;
+}
+
+// COATI2 coati_to_token (simple_coati2/transformer_only.py:144, 177): SwiGLUResNet(E, E) on the caller's [B, E] rows
+int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, const float* h, float* h_token, void* stream) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && h && h_token, "engine_token_head: engine not bound / null argument");
+  COATI_CHECK_ARG(e->enc_to_coati >= 0, "engine_token_head: not a COATI2 engine (coati_engine_create_coati2)");
+  COATI_CHECK_SHAPE(B > 0, "engine_token_head: B=%d", B);
+  const int E = e->cfg.n_embd_common;
+  const size_t bytes = (size_t)B * E * sizeof(float);
+  const char *ph = reinterpret_cast<const char*>(h), *pt = reinterpret_cast<const char*>(h_token);
+  COATI_CHECK_ARG(ph + bytes <= pt || pt + bytes <= ph, "engine_token_head: h_token must not overlap h");
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
+  const size_t need = carve(e, ar, B, 1, 1, 1, B);
+  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_token_head: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
+  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = 1; e->T2 = 1; e->A = 1;
+  e->have_fwd = false;
+  e->have_ws = true;
+  return coati2_head_fwd(e, e->c2t, h, h_token, B, (hipStream_t)stream);
 }
 
 // Likelihood scoring (clip_e2e.py:634-665 hclip_and_tokens_to_likelihood, :667-742 batch_smiles_to_s2s_likelihood): the embedding --
@@ -1750,6 +1873,7 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
                        float* scal, void* stream) {
   COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens && y_next && nll && scal, "engine_score: engine not bound / null argument");
   COATI_CHECK_ARG((raw_tokens != nullptr) != (h_clip != nullptr), "engine_score: give exactly one of raw_tokens / h_clip");
+  COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_score: a COATI2 engine is inference-only (COATI1's scoring head)");
   const coati_config& c = e->cfg;
   if (!raw_tokens) { T1 = 1; rows1 = 0; }
   COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T2 > 0 && T1 <= c.n_seq && T2 <= c.n_seq, "engine_score: unsupported shape B=%d T1=%d T2=%d (n_seq=%d)",
@@ -1811,7 +1935,8 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
 }
 
 int coati_engine_logits(coati_engine* e, float* logits, int64_t ldl, void* stream) {
-  COATI_CHECK_ARG(e && e->have_fwd && logits, "engine_logits: no forward to read");
+  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_logits: a COATI2 engine is inference-only (no training forward)");
+  COATI_CHECK_ARG(e->have_fwd && logits, "engine_logits: no forward to read");
   const coati_config& c = e->cfg;
   hipStream_t s = (hipStream_t)stream;
   COATI_CHECK_ARG(!e->p2.packed, "engine_logits: the last forward ran on packed rows (logits of padded positions do not exist): run it with rows1 = rows2 = 0");
@@ -1823,6 +1948,7 @@ int coati_engine_infonce(coati_engine* e, const float* S_loc, const float* C_loc
                          const float* C_all, const uint8_t* bad_all, int B, int Bg, int row0, float gscale,
                          float* dS_all, float* dC_all, float* scal, void* stream) {
   COATI_CHECK_ARG(e && S_loc && C_loc && S_all && C_all && bad_all && dS_all && dC_all && scal, "engine_infonce: null argument");
+  COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_infonce: a COATI2 engine is inference-only (no contrastive head)");
   COATI_CHECK_SHAPE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg, "engine_infonce: bad row range");
   hipStream_t s = (hipStream_t)stream;
   const int E = e->cfg.n_embd_common;
@@ -1863,7 +1989,8 @@ int coati_engine_infonce(coati_engine* e, const float* S_loc, const float* C_loc
 }
 
 int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* dh_e3gnn, int stage, void* stream) {
-  COATI_CHECK_ARG(e && e->have_fwd && e->G, "engine_backward: no forward / gradient buffer");
+  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_backward: a COATI2 engine is inference-only (no backward)");
+  COATI_CHECK_ARG(e->have_fwd && e->G, "engine_backward: no forward / gradient buffer");
   COATI_CHECK_ARG(stage >= 0 && stage <= 5, "engine_backward: bad stage");
   hipStream_t s = (hipStream_t)stream;
   const coati_config& c = e->cfg;
@@ -1969,7 +2096,8 @@ int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* 
 
 int coati_engine_optimizer_step(coati_engine* e, float lr, float beta1, float beta2, float eps, float weight_decay,
                                 float max_norm, int step, float* scal, void* stream) {
-  COATI_CHECK_ARG(e && e->P && e->G && e->Mo && e->Vo && scal, "optimizer_step: engine not bound for training");
+  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "optimizer_step: a COATI2 engine is inference-only (no optimizer step)");
+  COATI_CHECK_ARG(e->P && e->G && e->Mo && e->Vo && scal, "optimizer_step: engine not bound for training");
   COATI_CHECK_ARG(e->have_fwd, "optimizer_step: needs the workspace of a forward call");
   hipStream_t s = (hipStream_t)stream;
   {

@@ -14,6 +14,37 @@ int launch_silu_fwd(const float* x, float* y, long long n, hipStream_t s) {
   return COATI_OK;
 }
 
+// SwiGLU gate of the COATI2 heads (simple_coati2/transformer_only.py:38-42): x, gate = u.chunk(2, -1); g = silu(gate) * x, i.e.
+// g[b, j] = u[b, j] * silu(u[b, N + j]) on f32 rows with strides.  V4: four columns per thread with 16-B loads / stores (N, the
+// strides and both base addresses multiples of 4 floats)
+template <bool V4>
+__global__ __launch_bounds__(256) void swiglu_kernel(const float* __restrict__ u, long long ldu, float* __restrict__ g, long long ldg,
+                                                     int B, int N) {
+  const int W = V4 ? N / 4 : N;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * W) return;
+  const long long b = i / W;
+  const int j = (int)(i - b * W);
+  const float* r = u + b * ldu;
+  if constexpr (V4) {
+    const float4 x = *reinterpret_cast<const float4*>(r + 4 * j);
+    const float4 q = *reinterpret_cast<const float4*>(r + N + 4 * j);
+    *reinterpret_cast<float4*>(g + b * ldg + 4 * j) = make_float4(x.x * silu_f(q.x), x.y * silu_f(q.y), x.z * silu_f(q.z), x.w * silu_f(q.w));
+  } else {
+    g[b * ldg + j] = r[j] * silu_f(r[N + j]);
+  }
+}
+int launch_swiglu(const float* u, long long ldu, float* g, long long ldg, int B, int N, hipStream_t s) {
+  COATI_CHECK_ARG(u && g, "swiglu: null operand");
+  COATI_CHECK_SHAPE(B > 0 && N > 0 && ldu >= 2LL * N && ldg >= N, "swiglu: bad shape B=%d N=%d ldu=%lld ldg=%lld", B, N, ldu, ldg);
+  const bool v4 = N % 4 == 0 && ldu % 4 == 0 && ldg % 4 == 0 && reinterpret_cast<uintptr_t>(u) % 16 == 0 && reinterpret_cast<uintptr_t>(g) % 16 == 0;
+  const long long n = (long long)B * (v4 ? N / 4 : N);
+  if (v4) hipLaunchKernelGGL(swiglu_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, ldu, g, ldg, B, N);
+  else hipLaunchKernelGGL(swiglu_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, ldu, g, ldg, B, N);
+  COATI_LAUNCH_CHECK("swiglu");
+  return COATI_OK;
+}
+
 __global__ void silu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
                                 long long n, int accumulate) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

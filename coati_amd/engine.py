@@ -40,6 +40,12 @@ class ModelConfig:
     torch_emb: bool = False   # True: node features = rows of nn.Embedding(84, H) instead of Linear(one-hot group / period) (e3gnn_clip.py:49-56, 113-115)
     old_architecture: bool = False   # True (with norm_clips): the two clip heads are Linear -> LayerNorm instead of LayerNorm -> Linear (clip_e2e.py:409-417)
     residual: bool = False   # True: every node MLP also sees the one-hot node features (e3gnn_clip.py:97-100, e_gcl_sparse.py:141, 282-290)
+    # COATI2 (simple_coati2/transformer_only.py:43-104): "linear" / "swiglu_mlp" / "swiglu_resnet" selects smiles_to_coati, None = COATI1.
+    # A COATI2 engine is inference-only (encode, token_head, decode); the point-encoder and clip-head fields above do not apply
+    enc_to_coati: Optional[str] = None
+
+
+ENC_TO_COATI = {"linear": 0, "swiglu_mlp": 1, "swiglu_resnet": 2}
 
 
 # COATI_PACK_ROWS=0 ignores the batches' packed-row counts: every step then runs on the padded [B, T] layout (A/B switch)
@@ -82,7 +88,13 @@ class Engine:
                              1 if cfg.token_mlp else 0, 1 if cfg.use_point_encoder else 0, 1 if cfg.biases else 0, 1 if cfg.norm_embed else 0,
                              1 if cfg.torch_emb else 0, 1 if cfg.old_architecture else 0, 1 if cfg.residual else 0)
         h = ctypes.c_void_p()
-        _lib.check(self.l.coati_engine_create(ctypes.byref(c), ctypes.byref(h)), "coati_engine_create")
+        if cfg.enc_to_coati is None:
+            _lib.check(self.l.coati_engine_create(ctypes.byref(c), ctypes.byref(h)), "coati_engine_create")
+        else:
+            if cfg.enc_to_coati not in ENC_TO_COATI:
+                raise ValueError(f"enc_to_coati must be one of {sorted(ENC_TO_COATI)}, not {cfg.enc_to_coati!r}")
+            _lib.check(self.l.coati_engine_create_coati2(ctypes.byref(c), ENC_TO_COATI[cfg.enc_to_coati], ctypes.byref(h)),
+                       "coati_engine_create_coati2")
         self.h = h
         self.n_params = int(self.l.coati_engine_param_elems(h))
         self.n_trainable = int(self.l.coati_engine_trainable_elems(h))
@@ -284,6 +296,24 @@ class Engine:
                    "coati_engine_encode")
         self._shape = None
         return h_s, h_e
+
+    def token_head(self, h):
+        """COATI2 coati_to_token (SwiGLUResNet(E, E), simple_coati2/transformer_only.py:19-36) on h [B, E] -> [B, E] f32; scratch from
+        the engine workspace.  COATI2 engines only."""
+        h = h.to(self.device, torch.float32).contiguous()
+        E = self.cfg.n_embd_common
+        assert h.dim() == 2 and h.shape[1] == E, h.shape
+        B = int(h.shape[0])
+        need = int(self.l.coati_engine_workspace_bytes(self.h, B, 1, 1, 1, B))
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None
+            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        out = torch.empty(B, E, device=self.device, dtype=torch.float32)
+        self._keep = (h,)
+        _lib.check(self.l.coati_engine_token_head(self.h, ptr(self.workspace), self.workspace.numel(), B, ptr(h), ptr(out), stream()),
+                   "coati_engine_token_head")
+        self._shape = None
+        return out
 
     def score(self, tokens, y_next, h_clip=None, raw_tokens=None, rows=None):
         """Per-sequence autoregressive NLL [B] f32 of `tokens` [B, T2] against `y_next` [B, T2] (-1 = ignored), with the special-token

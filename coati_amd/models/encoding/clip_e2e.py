@@ -143,6 +143,44 @@ def s2s_likelihood_tokens(smiles: List[str], tokenizer):
     return raw_tokens, tokens, y_next, mask
 
 
+@torch.no_grad()
+def torch_default_init(model: nn.Module, seed, is_layernorm):
+    """torch.nn default initialisers over model.named_parameters() in order, drawn from one CPU generator seeded with `seed`
+    (default torch.initial_seed()): Linear: kaiming-uniform(a=sqrt 5) weight and U(+-1/sqrt(fan_in)) bias; Embedding: N(0,1);
+    LayerNorm (the 1-D parameters `is_layernorm(name)` names): 1/0; coord_mlp.2: xavier-uniform gain 1e-3.  Then the engine's
+    shadows are refreshed."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(torch.initial_seed() if seed is None else seed)
+    for name, p in model.named_parameters():
+        shape = tuple(p.shape)
+        if name.endswith("tok_emb.weight") or name.endswith("tok_emb.0.weight"):
+            v = torch.randn(shape, generator=g)
+        elif name.endswith("coord_mlp.2.weight"):
+            bound = 1e-3 * math.sqrt(6.0 / (shape[0] + shape[1]))
+            v = (torch.rand(shape, generator=g) * 2 - 1) * bound
+        elif len(shape) == 2:
+            bound = 1.0 / math.sqrt(shape[1])
+            v = (torch.rand(shape, generator=g) * 2 - 1) * bound
+        elif is_layernorm(name):
+            v = torch.ones(shape) if name.endswith("weight") else torch.zeros(shape)
+        else:  # Linear bias: fan_in of the matching weight
+            wname = name[: -len("bias")] + "weight"
+            fan_in = dict(model.named_parameters())[wname].shape[1]
+            v = (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(fan_in)
+        p.copy_(v.to(p.device))
+    model.engine.refresh_shadows()
+
+
+def injection_prefix(tokenizer, fill_in_from: str, do_suffix: bool):
+    """The prompt of the [UNK]-injection generators: [CLIP][UNK]<fill_in_from> (+ [SUFFIX][MIDDLE]) as token ids, from the
+    tokenizer's text, or from its *_token attributes for a tokenizer without tokenize_text"""
+    if hasattr(tokenizer, "tokenize_text"):
+        return tokenizer.tokenize_text("[CLIP][UNK]" + fill_in_from + ("[SUFFIX][MIDDLE]" if do_suffix else ""), pad=False)
+    names = ["clip_token", "unk_token", "smiles_token" if fill_in_from == "[SMILES]" else "graph_token"]
+    names += ["suffix_token", "middle_token"] if do_suffix else []
+    return [int(getattr(tokenizer, n)) for n in names]
+
+
 def _trim_columns(t, n):
     return t[:, :n].contiguous()
 
@@ -201,28 +239,8 @@ class e3gnn_smiles_clip_e2e(nn.Module):
 
     @torch.no_grad()
     def reset_parameters(self, seed: int = None):
-        """torch.nn default initialisers for every layer type on the path (Linear: kaiming-uniform(a=sqrt 5) weight and
-        U(+-1/sqrt(fan_in)) bias; Embedding: N(0,1); LayerNorm: 1/0; coord_mlp.2: xavier-uniform gain 1e-3)."""
-        g = torch.Generator(device="cpu")
-        g.manual_seed(torch.initial_seed() if seed is None else seed)
-        for name, p in self.named_parameters():
-            shape = tuple(p.shape)
-            if name.endswith("tok_emb.weight") or name.endswith("tok_emb.0.weight"):
-                v = torch.randn(shape, generator=g)
-            elif name.endswith("coord_mlp.2.weight"):
-                bound = 1e-3 * math.sqrt(6.0 / (shape[0] + shape[1]))
-                v = (torch.rand(shape, generator=g) * 2 - 1) * bound
-            elif len(shape) == 2:
-                bound = 1.0 / math.sqrt(shape[1])
-                v = (torch.rand(shape, generator=g) * 2 - 1) * bound
-            elif (".ln_" in name or name.endswith("_to_clip.0.weight") or name.endswith("_to_clip.0.bias")):
-                v = torch.ones(shape) if name.endswith("weight") else torch.zeros(shape)
-            else:  # Linear bias: fan_in of the matching weight
-                wname = name[: -len("bias")] + "weight"
-                fan_in = dict(self.named_parameters())[wname].shape[1]
-                v = (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(fan_in)
-            p.copy_(v.to(p.device))
-        self.engine.refresh_shadows()
+        """torch.nn default initialisers for every layer type on the path (torch_default_init; coord_mlp.2: xavier-uniform gain 1e-3)."""
+        torch_default_init(self, seed, lambda name: ".ln_" in name or name.endswith("_to_clip.0.weight") or name.endswith("_to_clip.0.bias"))
 
     # ---- reference API ------------------------------------------------------------------------------------------
     def _tok(self, t):
@@ -285,12 +303,7 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         if noise_scale > 0:
             h_clip = h_clip + noise_scale * torch.randn_like(h_clip)
         h_token = self.special_tokens_from_clip(h_clip)
-        if hasattr(tokenizer, "tokenize_text"):
-            prefix = tokenizer.tokenize_text("[CLIP][UNK]" + fill_in_from + ("[SUFFIX][MIDDLE]" if do_suffix else ""), pad=False)
-        else:
-            names = ["clip_token", "unk_token", "smiles_token" if fill_in_from == "[SMILES]" else "graph_token"]
-            names += ["suffix_token", "middle_token"] if do_suffix else []
-            prefix = [int(getattr(tokenizer, n)) for n in names]
+        prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
         generation = self.engine.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp,
                                                                k=k, pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
                                                                inj_payload=h_token, generator=generator)

@@ -1,0 +1,143 @@
+"""COATI2's inference model (simple_coati2/transformer_only.py:19-200) with the reference's constructor, state_dict names and
+methods.  The transformer, both heads and generation run in libcoati_hip.so through coati_amd.engine.Engine; this file adapts the
+calling convention.  SwiGLU / SwiGLUResNet are the reference's torch modules, kept for code that builds them directly."""
+import torch
+import torch.nn as nn
+
+from ...engine import Engine, ModelConfig
+from ..encoding.clip_e2e import _attach, injection_prefix, reference_parameter_order, torch_default_init
+
+
+class SwiGLUResNet(nn.Module):
+    """transformer_only.py:19-36: LayerNorm -> Dropout -> Linear(d_in, 2 d_out) -> SwiGLU -> Linear(d_out, d_out), + x"""
+
+    def __init__(self, d_in, d_out, dropout=0.0):
+        super().__init__()
+        self.net = nn.Sequential(nn.LayerNorm(d_in), nn.Dropout(p=dropout), nn.Linear(d_in, 2 * d_out), SwiGLU(), nn.Linear(d_out, d_out))
+
+    def forward(self, x):
+        return self.net(x) + x
+
+
+class SwiGLU(nn.Module):
+    """transformer_only.py:38-42: x, gate = x.chunk(2, -1); silu(gate) * x, as the HIP kernel coati_swiglu on device f32 tensors."""
+
+    def forward(self, x):
+        from ... import ops
+        return ops.swiglu(x.reshape(-1, x.shape[-1]).contiguous()).view(*x.shape[:-1], x.shape[-1] // 2)
+
+
+def coati2_parameter_order(names):
+    """The reference's parameter order (transformer_only.py:83-104): the xformer (as COATI1's, reference_parameter_order), then
+    smiles_to_coati and coati_to_token, whose entries the engine's table lists in module order already."""
+    names = list(names)
+    return reference_parameter_order([n for n in names if n.startswith("xformer.")]) + [n for n in names if not n.startswith("xformer.")]
+
+
+def _is_layernorm(name):
+    return ".ln_" in name or name.endswith("_to_coati.0.weight") or name.endswith("_to_coati.0.bias") or ".net.0." in name
+
+
+class COATI_Smiles_Inference(nn.Module):
+    """Drop-in for coati.models.simple_coati2.transformer_only.COATI_Smiles_Inference.  Inference only: no dropout (mlp_dropout is
+    recorded), and the model's special ids (default: the coati2_12_12 vocabulary's [PAD] / [STOP] / [UNK]) must be the tokenizer's."""
+
+    def __init__(self, n_layer_xformer=16, n_hidden_xformer=256, embed_dim=256, n_head=16, n_seq=80, mlp_dropout=0.0,
+                 enc_to_coati="linear", n_direct_clr=64, n_tok=4, biases=True, device=torch.device("cuda:0"), dtype=torch.float, *,
+                 pad_token: int = 31, stop_token: int = 40, unk_token: int = 44):
+        super().__init__()
+        if dtype not in (torch.float, torch.float32):
+            raise NotImplementedError("parameters are fp32 (bf16 is an internal operand format)")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NotImplementedError(f"COATI_Smiles_Inference runs on the HIP engine: device must be a GPU, not {device}")
+        self.embed_dim = embed_dim
+        self.enc_to_coati = enc_to_coati
+        self.n_direct_clr = n_direct_clr
+        self.mlp_dropout = mlp_dropout
+        self.device = device
+        cfg = ModelConfig(n_layer_xformer=n_layer_xformer, n_layer_e3gnn=0, n_hidden_xformer=n_hidden_xformer, n_hidden_e3nn=n_hidden_xformer,
+                          n_embd_common=embed_dim, n_head=n_head, n_seq=n_seq, n_tok=n_tok, pad_token=int(pad_token), stop_token=int(stop_token),
+                          unk_token=int(unk_token), use_point_encoder=False, biases=bool(biases), enc_to_coati=enc_to_coati)
+        eng = Engine(cfg, device, train=False)
+        object.__setattr__(self, "engine", eng)
+        views = eng.named_views("params")
+        for name in coati2_parameter_order(views):
+            _attach(self, name, views[name])
+        for l in range(n_layer_xformer):   # causal-mask buffers of the reference state_dict (basic_transformer.py:117-123)
+            _attach(self, f"xformer.transformer.h.{l}.attn.bias",
+                    torch.tril(torch.ones(n_seq, n_seq, device=device)).view(1, 1, n_seq, n_seq), buffer=True)
+        self.xformer.n_seq, self.xformer.n_tok, self.xformer.n_embd = n_seq, n_tok, n_hidden_xformer
+        # generation entry points of the reference's RotarySmilesTransformer (smiles_xformer.py), KV-cached here
+        object.__setattr__(self.xformer, "generate_top_k_with_inj_batch", eng.generate_top_k_with_inj_batch)
+        object.__setattr__(self.xformer, "generate_topk_batch", eng.generate_topk_batch)
+        object.__setattr__(self.xformer, "generate_topk_with_inj", eng.generate_topk_with_inj)
+        # model.coati_to_token(h) as in the reference: SwiGLUResNet(E, E) on [B, E] rows (HIP LayerNorm, exact-f32 products, SwiGLU kernel)
+        object.__setattr__(self.coati_to_token, "forward", eng.token_head)
+        self.reset_parameters()
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module.engine.refresh_shadows())
+        n_x = sum(p.numel() for n, p in self.named_parameters() if n.startswith("xformer."))
+        print(f"number of parameters Total: xformer: {n_x/1e6:.2f}M ")
+
+    @torch.no_grad()
+    def reset_parameters(self, seed: int = None):
+        """torch.nn default initialisers (Linear: kaiming-uniform(a=sqrt 5) weight and U(+-1/sqrt(fan_in)) bias; Embedding: N(0,1);
+        LayerNorm: 1/0)."""
+        torch_default_init(self, seed, _is_layernorm)
+
+    def _sync_tokens(self, tokenizer):
+        if tokenizer is None:
+            return
+        c = self.engine.cfg
+        ids = tuple(int(getattr(tokenizer, n, getattr(c, n))) for n in ("stop_token", "unk_token", "pad_token"))
+        if ids != (c.stop_token, c.unk_token, c.pad_token):
+            raise NotImplementedError(f"tokenizer special ids (stop/unk/pad) {ids} differ from the model's "
+                                      f"{(c.stop_token, c.unk_token, c.pad_token)}; build the model with the tokenizer's ids")
+
+    def encode_tokens(self, token_indices, tokenizer):
+        """transformer_only.py:108-110: smiles_to_coati(xformer.encode(tokens)) -- the [STOP]-row embedding [B, embed_dim]."""
+        assert token_indices.dim() == 2
+        self._sync_tokens(tokenizer)
+        h, _ = self.engine.encode(raw_tokens=token_indices.to(self.device, torch.long).contiguous())
+        if int(self.engine.scal[6:7].view(torch.int32).item()) & 1:
+            raise RuntimeError("Some smiles in the batch do not have stop tokens. Did some tokenizations fail?")
+        return h
+
+    @torch.no_grad()
+    def hcoati_to_2d(self, h_coati, tokenizer, fill_in_from="[SMILES]", noise_scale=0.0, do_suffix=False, inv_temp=2, k=100, generator=None):
+        """transformer_only.py:112-152: one embedding -> SMILES.  The payload is h_token[0]: the first row of a [B, E] input, and for a
+        1-D [E] input its first channel, a scalar the reference's assignment spreads over all C.  Noise is added out of place."""
+        self._sync_tokens(tokenizer)
+        assert fill_in_from == "[SMILES]" or fill_in_from == "[GRAPH]"
+        h = h_coati.to(self.device, torch.float32)
+        if noise_scale > 0:
+            h = h + noise_scale * torch.randn_like(h)
+        h_token = self.engine.token_head(h if h.dim() == 2 else h.reshape(1, -1))
+        payload = h_token[0] if h.dim() == 2 else h_token[0, 0]
+        prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
+        generation = self.xformer.generate_topk_with_inj(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
+                                                         inj_token=tokenizer.unk_token, inj_payload=payload, generator=generator)
+        return tokenizer.decode(generation, special=False) if fill_in_from == "[SMILES]" else tokenizer.decode(generation)
+
+    @torch.no_grad()
+    def hcoati_to_2d_batch(self, h_coati: torch.Tensor, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
+                           inv_temp: float = 2, k: int = 100, do_suffix=False, keep_special: bool = False, return_tokens: bool = False,
+                           generator=None):
+        """transformer_only.py:154-200: decode [B, E] embeddings through coati_to_token at the [UNK] slot of
+        [CLIP][UNK]<fill_in_from> (+ [SUFFIX][MIDDLE]); top-k sampling on the KV-cached decode path.  Noise is added out of place."""
+        assert k > 1
+        self._sync_tokens(tokenizer)
+        h = h_coati.to(self.device, torch.float32)
+        if noise_scale > 0:
+            h = h + noise_scale * torch.randn_like(h)
+        h_token = self.engine.token_head(h)
+        prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
+        assert h_token.dim() == 2
+        assert h_token.shape[-1] == self.xformer.n_embd
+        generation = self.xformer.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
+                                                                pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
+                                                                inj_payload=h_token, generator=generator)
+        smiles_list = [tokenizer.decode(t, special=keep_special) for t in generation]
+        if return_tokens:
+            return smiles_list, generation
+        return smiles_list

@@ -169,6 +169,19 @@ def sgemm(A, Bm, trans_a=False, trans_b=False, bias=None, alpha=1.0, out=None, a
     return out
 
 
+def swiglu(u, out=None):
+    """SwiGLU of the COATI2 heads (simple_coati2/transformer_only.py:38-42): u [B, 2N] f32 (row stride free) -> silu(u[:, N:]) * u[:, :N]
+    [B, N] f32 (coati_swiglu)."""
+    _need_cuda(u)
+    assert u.dtype == torch.float32 and u.dim() == 2 and u.stride(1) == 1 and u.shape[1] % 2 == 0
+    B, N = u.shape[0], u.shape[1] // 2
+    if out is None:
+        out = torch.empty(B, N, device=u.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == (B, N) and out.stride(1) == 1
+    _lib.call("coati_swiglu", ptr(u), u.stride(0), ptr(out), out.stride(0), B, N, stream())
+    return out
+
+
 def layernorm_fwd(x, gamma=None, beta=None, want16=True, want32=False):
     _need_cuda(x)
     M, C = x.shape

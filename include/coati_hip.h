@@ -210,6 +210,9 @@ int coati_batch_tail(const int64_t* tokens, int B, int n_seq, int ncol, int64_t*
 
 /* y = x * sigmoid(x), f32 (point_clip_to_special_tokens = SiLU -> Linear, clip_e2e.py:432-435) */
 int coati_silu(const float* x, float* y, int64_t n, void* stream);
+/* SwiGLU gate of the COATI2 heads (simple_coati2/transformer_only.py:38-42): x, gate = u.chunk(2, -1); g = silu(gate) * x, i.e.
+   g[b * ldg + j] = u[b * ldu + j] * silu(u[b * ldu + N + j]) for b < B, j < N; f32, ldu >= 2N, ldg >= N */
+int coati_swiglu(const float* u, int64_t ldu, float* g, int64_t ldg, int B, int N, void* stream);
 
 /* decode-time operators: one query per (sequence, head) against the KV cache [B, nh, Tmax, k16|v16] (appends position
    pos first), and top-k sampling: token = inds[multinomial(softmax(topk(logits, k) * inv_temp))] with the caller's
@@ -377,6 +380,20 @@ int coati_engine_forward_decoder(coati_engine* e, void* stream);
 int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int A,
                         const int64_t* raw_tokens, const int64_t* atoms, const float* coords, float* h_smiles,
                         float* h_e3gnn, float* scal, void* stream);
+
+/* COATI2 inference model (simple_coati2/transformer_only.py:43-104, COATI_Smiles_Inference): the same transformer and decode path
+ * without a point encoder, and two heads in place of smiles_to_clip / point_clip_to_special_tokens.  enc_to_coati selects
+ * smiles_to_coati: 0 = "linear" (LayerNorm -> Linear, state_dict .0 / .1), 1 = "swiglu_mlp" (LayerNorm -> Linear(C -> 2E) -> SwiGLU ->
+ * Linear(E -> E), .0 / .1 / .3), 2 = "swiglu_resnet" (the same + x, .net.0 / .net.2 / .net.4).  coati_to_token is always the
+ * residual form (coati_to_token.net.0 / .net.2 / .net.4).  The parameter table holds xformer.* (as coati_engine_create), then
+ * smiles_to_coati.* and coati_to_token.net.*.  Needs use_point_encoder = 0, use_fp8 = 0, norm_embed = 0 and
+ * n_embd_common == n_hidden_xformer; the point-encoder and clip-head fields of cfg are ignored.  On such an engine
+ * coati_engine_encode runs smiles_to_coati behind the encoder pass (raw_tokens only); forward, forward_decoder, backward,
+ * optimizer_step, infonce, score and logits refuse to run; the decode entries work unchanged. */
+int coati_engine_create_coati2(const coati_config* cfg, int enc_to_coati, coati_engine** out);
+/* the token head coati_to_token = SwiGLUResNet(E, E) on h [B,E] f32 -> h_token [B,E] f32 (must not overlap h).  Scratch from the workspace:
+ * coati_engine_workspace_bytes(e, B, 1, 1, 1, B) bytes.  Only on a COATI2 engine. */
+int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, const float* h, float* h_token, void* stream);
 
 /* Likelihood scoring (e3gnn_smiles_clip_e2e.hclip_and_tokens_to_likelihood / batch_smiles_to_s2s_likelihood, clip_e2e.py:634-742):
  * nll[b] = sum over t of the autoregressive cross-entropy of tokens [B,T2] against y_next [B,T2] (-1 = ignored), with the
