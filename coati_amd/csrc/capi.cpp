@@ -222,6 +222,10 @@ int coati_silu(const float* x, float* y, int64_t n, void* stream) { return launc
 int coati_swiglu(const float* u, int64_t ldu, float* g, int64_t ldg, int B, int N, void* stream) {
   return launch_swiglu(u, ldu, g, ldg, B, N, S_(stream));
 }
+int coati_group_mean_rows(const float* x, int64_t ldx, const int32_t* off, const float* w, const float* fallback, float* out, int G, int E,
+                          void* stream) {
+  return launch_group_mean_rows(x, ldx, off, w, fallback, out, G, E, S_(stream));
+}
 int coati_attn_decode(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int Tmax, int pos, void* stream) {
   return launch_attn_decode(qkv, cache, y, B, n_head, 16, Tmax, pos, nullptr, S_(stream));
 }

@@ -1934,6 +1934,70 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
   return COATI_OK;
 }
 
+// encode_tokens on packed rows: the encoder pass over the rows' real prefixes only (the encoder half of coati_engine_score), then the
+// [STOP]-row pick and the head of coati_engine_encode (smiles_to_clip, or COATI2's smiles_to_coati).  Under causal attention the
+// positions behind a row's [STOP] change nothing the head reads: h_smiles is that of the padded encode.
+int coati_engine_encode_packed(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, const int64_t* raw_tokens,
+                               int64_t rows1, float* h_smiles, float* scal, void* stream) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && raw_tokens && h_smiles && scal, "engine_encode_packed: engine not bound / null argument");
+  const coati_config& c = e->cfg;
+  COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T1 <= c.n_seq, "engine_encode_packed: unsupported shape B=%d T1=%d (n_seq=%d)", B, T1, c.n_seq);
+  COATI_CHECK_SHAPE(rows1 > 0 && rows1 <= (int64_t)B * T1, "engine_encode_packed: packed row count %lld does not fit %d x %d", (long long)rows1, B, T1);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = c.n_hidden_xformer;
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
+  const size_t need = carve(e, ar, B, T1, 1, 1, B);
+  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_encode_packed: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
+  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = T1; e->T2 = 1; e->A = 1;
+  e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
+  e->scal = scal;
+  e->have_fwd = false;
+  e->decoder_pending = false;
+  e->have_ws = true;
+  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
+  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(launch_seq_pack(e->p1.idx, nullptr, c.pad_token, B, T1, (int)rows1, e->p1.off, e->p1.row_src, e->p1.row_t, nullptr, e->err_flag, s, e->p1.ord));
+  e->p1.packed = true;
+  e->p1.M = (int)rows1;
+  COATI_TRY(launch_find_stop(e->p1.idx, c.stop_token, e->stop_pos, e->err_flag, B, T1, s));
+  COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
+  COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s, e->p1.off));
+  if (e->enc_to_coati > 0) COATI_TRY(coati2_head_fwd(e, e->c2s, e->hstop, h_smiles, B, s));   // COATI2 SwiGLU smiles_to_coati
+  else COATI_TRY(smiles_head_fwd(e, h_smiles, s));
+  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
+  return COATI_OK;
+}
+
+// RotarySmilesTransformer.forward / forward_with_replacement (smiles_xformer.py:375-382, 426-454): the decoder pass over the padded
+// tokens [B, T] -- injection [B, C] (optional) at every [UNK] position of its row, after the embedding LayerNorm on norm_embed models --,
+// ln_f, and the lm_head into f32 logits [B*T, ldl].  Nothing is kept for a backward (have_fwd stays false).
+int coati_engine_decoder_logits(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T, const int64_t* tokens,
+                                const float* injection, float* logits, int64_t ldl, float* scal, void* stream) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens && logits && scal, "engine_decoder_logits: engine not bound / null argument");
+  const coati_config& c = e->cfg;
+  COATI_CHECK_SHAPE(B > 0 && T > 0 && T <= c.n_seq && ldl >= c.n_tok, "engine_decoder_logits: unsupported shape B=%d T=%d ldl=%lld (n_seq=%d, n_tok=%d)",
+                    B, T, (long long)ldl, c.n_seq, c.n_tok);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = c.n_hidden_xformer;
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
+  const size_t need = carve(e, ar, B, 1, T, 1, B);
+  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_decoder_logits: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
+  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = 1; e->T2 = T; e->A = 1;
+  e->p2.idx = reinterpret_cast<const long long*>(tokens);
+  e->scal = scal;
+  e->have_fwd = false;
+  e->decoder_pending = false;
+  e->have_ws = true;
+  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
+  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(xformer_fwd(e, e->p2, injection, s));
+  COATI_TRY(gemm(e, SITE_NONE, e->p2.af, 0, C, e->S + e->lmhead, C, B * T, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
+  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
+  return COATI_OK;
+}
+
 int coati_engine_logits(coati_engine* e, float* logits, int64_t ldl, void* stream) {
   COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_logits: a COATI2 engine is inference-only (no training forward)");
   COATI_CHECK_ARG(e->have_fwd && logits, "engine_logits: no forward to read");

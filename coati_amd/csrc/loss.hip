@@ -45,6 +45,37 @@ int launch_swiglu(const float* u, long long ldu, float* g, long long ldg, int B,
   return COATI_OK;
 }
 
+// Segmented weighted mean (batched purification: the embeddings of a vector's distinct decodes, weighted by multiplicity):
+// out[g] = sum_{i in [off[g], off[g+1])} w[i] x[i] / sum w[i]; an empty group copies fallback[g].  One workgroup per group, each lane
+// owns whole columns and runs through the group's rows in index order: no atomics, no cross-lane reduction, the same bits every call
+__global__ __launch_bounds__(256) void group_mean_rows_kernel(const float* __restrict__ x, long long ldx, const int* __restrict__ off,
+                                                              const float* __restrict__ w, const float* __restrict__ fallback,
+                                                              float* __restrict__ out, int E) {
+  const int g = blockIdx.x;
+  const int lo = off[g], hi = off[g + 1];
+  float* o = out + (long long)g * E;
+  if (hi <= lo) {
+    for (int e = threadIdx.x; e < E; e += blockDim.x) o[e] = fallback[(long long)g * E + e];
+    return;
+  }
+  float ws = 0.f;
+  for (int i = lo; i < hi; ++i) ws += w ? w[i] : 1.f;
+  const float inv = 1.f / ws;
+  for (int e = threadIdx.x; e < E; e += blockDim.x) {
+    float acc = 0.f;
+    for (int i = lo; i < hi; ++i) acc += (w ? w[i] : 1.f) * x[(long long)i * ldx + e];
+    o[e] = acc * inv;
+  }
+}
+int launch_group_mean_rows(const float* x, long long ldx, const int* off, const float* w, const float* fallback, float* out, int G, int E,
+                           hipStream_t s) {
+  COATI_CHECK_ARG(x && off && fallback && out, "group_mean_rows: null operand");
+  COATI_CHECK_SHAPE(G > 0 && E > 0 && ldx >= E, "group_mean_rows: bad shape G=%d E=%d ldx=%lld", G, E, ldx);
+  hipLaunchKernelGGL(group_mean_rows_kernel, dim3(G), dim3(E < 256 ? (E + 63) / 64 * 64 : 256), 0, s, x, ldx, off, w, fallback, out, E);
+  COATI_LAUNCH_CHECK("group_mean_rows");
+  return COATI_OK;
+}
+
 __global__ void silu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
                                 long long n, int accumulate) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

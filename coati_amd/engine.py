@@ -275,8 +275,13 @@ class Engine:
                 t.record_stream(main)               # allocated on the side stream, consumed by the backward on the main one
         return out
 
-    def encode(self, raw_tokens=None, atoms=None, coords=None):
-        """encode_tokens / encode_points: only the requested tower runs.  Returns (h_smiles or None, h_e3gnn or None)."""
+    def encode(self, raw_tokens=None, atoms=None, coords=None, rows=None):
+        """encode_tokens / encode_points: only the requested tower runs.  Returns (h_smiles or None, h_e3gnn or None).
+        rows: rows1 of the packed layout of raw_tokens (host int, coati_amd.synthetic.packed_rows): the token tower alone on packed rows
+        (coati_engine_encode_packed; h_smiles as the padded encode's to bf16 rounding).  None: the padded layout."""
+        if rows is not None:
+            assert atoms is None and coords is None, "encode(rows=...): the packed entry runs the token tower alone"
+            return self._encode_packed(raw_tokens, int(rows)), None
         assert raw_tokens is not None or atoms is not None
         B = (raw_tokens if raw_tokens is not None else atoms).shape[0]
         T1 = raw_tokens.shape[1] if raw_tokens is not None else 1
@@ -296,6 +301,42 @@ class Engine:
                    "coati_engine_encode")
         self._shape = None
         return h_s, h_e
+
+    def _encode_packed(self, raw_tokens, rows1):
+        assert raw_tokens.dtype == torch.int64 and raw_tokens.is_cuda and raw_tokens.is_contiguous() and raw_tokens.dim() == 2
+        B, T1 = raw_tokens.shape
+        need = int(self.l.coati_engine_workspace_bytes(self.h, B, T1, 1, 1, B))
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None
+            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        h_s = torch.empty(B, self.cfg.n_embd_common, device=self.device, dtype=torch.float32)
+        self._keep = (raw_tokens,)
+        _lib.check(self.l.coati_engine_encode_packed(self.h, ptr(self.workspace), self.workspace.numel(), B, T1, ptr(raw_tokens), rows1,
+                                                     ptr(h_s), ptr(self.scal), stream()), "coati_engine_encode_packed")
+        self._shape = None
+        return h_s
+
+    def decoder_logits(self, tokens, injection=None):
+        """RotarySmilesTransformer.forward (injection None) / forward_with_replacement (injection [B, C]: row b's vector at every [UNK]
+        position of row b): the decoder pass over the padded tokens [B, T] and the lm_head -> f32 logits [B, T, n_tok] (a view with a
+        padded row stride).  COATI1 and COATI2 engines; nothing is kept for a backward."""
+        assert tokens.dtype == torch.int64 and tokens.is_cuda and tokens.is_contiguous() and tokens.dim() == 2
+        B, T = tokens.shape
+        C, V = self.cfg.n_hidden_xformer, self.cfg.n_tok
+        if injection is not None:
+            injection = injection.to(self.device, torch.float32).contiguous()
+            assert injection.shape == (B, C), injection.shape
+        need = int(self.l.coati_engine_workspace_bytes(self.h, B, 1, T, 1, B))
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None
+            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        ld = (V + 7) // 8 * 8
+        out = torch.empty(B * T, ld, device=self.device, dtype=torch.float32)
+        self._keep = (tokens, injection)
+        _lib.check(self.l.coati_engine_decoder_logits(self.h, ptr(self.workspace), self.workspace.numel(), B, T, ptr(tokens), ptr(injection),
+                                                      ptr(out), ld, ptr(self.scal), stream()), "coati_engine_decoder_logits")
+        self._shape = None
+        return out[:, :V].view(B, T, V)
 
     def token_head(self, h):
         """COATI2 coati_to_token (SwiGLUResNet(E, E), simple_coati2/transformer_only.py:19-36) on h [B, E] -> [B, E] f32; scratch from

@@ -1,0 +1,2 @@
+"""Mirror of coati.generative: embedding, purification, forced decoding (coati_purifications.py) and the embedding-space density fit
+(coati_density.py).  rdkit is not a dependency: canonicalisation and conformer generation are injected callables."""

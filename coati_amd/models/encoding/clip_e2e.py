@@ -181,6 +181,26 @@ def injection_prefix(tokenizer, fill_in_from: str, do_suffix: bool):
     return [int(getattr(tokenizer, n)) for n in names]
 
 
+def attach_xformer_logits(xformer: nn.Module, engine: Engine):
+    """RotarySmilesTransformer.forward(idx) and .forward_with_replacement(idx, injection, tokenizer, inject_token) (smiles_xformer.py:375-382,
+    426-454; simple_coati2/smiles_xformer.py:388, 439) on `xformer`, so that xformer(idx) works as well: the decoder pass over the padded
+    [B, T] rows and the lm_head as f32 logits [B, T, n_tok] (coati_engine_decoder_logits).  injection [B, C]: row b's vector at every
+    inject_token position of row b.  The engine injects at its [UNK] id only: another inject_token raises NotImplementedError."""
+    def forward(idx):
+        return engine.decoder_logits(idx.to(engine.device, torch.long).contiguous())
+
+    def forward_with_replacement(idx, injection, tokenizer, inject_token="[UNK]"):
+        inj_id = int(tokenizer.vocab[inject_token])
+        if inj_id != engine.cfg.unk_token:
+            raise NotImplementedError(f"forward_with_replacement: the engine injects at its [UNK] id {engine.cfg.unk_token}, not at "
+                                      f"{inject_token!r} ({inj_id})")
+        idx = idx.to(engine.device, torch.long).contiguous()
+        return engine.decoder_logits(idx, injection)
+
+    object.__setattr__(xformer, "forward", forward)
+    object.__setattr__(xformer, "forward_with_replacement", forward_with_replacement)
+
+
 def _trim_columns(t, n):
     return t[:, :n].contiguous()
 
@@ -224,10 +244,13 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         # prompt completion and one-sequence generation (smiles_xformer.py:157-198, 215-270): prompt prefill + per-row prompts
         object.__setattr__(self.xformer, "generate_topk_batch", eng.generate_topk_batch)
         object.__setattr__(self.xformer, "generate_topk_with_inj", eng.generate_topk_with_inj)
+        attach_xformer_logits(self.xformer, eng)
         self.point_encoder.hidden_nf = n_hidden_e3nn
         self.use_point_encoder = bool(use_point_encoder)
         if not token_mlp:
             self.point_clip_to_special_tokens = nn.Identity()   # clip_e2e.py:436-437
+        else:   # point_clip_to_special_tokens(h) as in the reference: SiLU -> Linear on [B, E] rows (special_tokens_from_clip)
+            object.__setattr__(self.point_clip_to_special_tokens, "forward", self.special_tokens_from_clip)
         self.clip_loss = clip_loss(eng)
         self.reset_parameters()
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.engine.refresh_shadows())
@@ -240,7 +263,8 @@ class e3gnn_smiles_clip_e2e(nn.Module):
     @torch.no_grad()
     def reset_parameters(self, seed: int = None):
         """torch.nn default initialisers for every layer type on the path (torch_default_init; coord_mlp.2: xavier-uniform gain 1e-3)."""
-        torch_default_init(self, seed, lambda name: ".ln_" in name or name.endswith("_to_clip.0.weight") or name.endswith("_to_clip.0.bias"))
+        torch_default_init(self, seed, lambda name: ".ln_" in name or ".norm_embed." in name or ".tok_emb.1." in name or name.endswith("_to_clip.0.weight")
+                           or name.endswith("_to_clip.0.bias"))
 
     # ---- reference API ------------------------------------------------------------------------------------------
     def _tok(self, t):

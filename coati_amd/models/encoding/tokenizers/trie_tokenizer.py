@@ -133,6 +133,22 @@ class TrieTokenizer:
             ids = ids + [self.vocab["[PAD]"] for _ in range(self.n_seq - len(ids))]
         return ids
 
+    def encode_rows(self, texts: List[str]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Threaded batch encode of whole texts (no prefix / suffix added): ids [n, n_seq] int64 padded with [PAD], and lengths [n]
+        int32 (-1: a piece with no id, -2: longer than n_seq; such rows hold no ids).  tokenize_text(text, pad=True) of one text gives
+        the same ids, or raises where the length is negative."""
+        arr, _keep = _c_strings(texts)
+        out = torch.zeros(len(texts), self.n_seq, dtype=torch.long)
+        lens = torch.zeros(len(texts), dtype=torch.int32)
+        if texts:
+            _lib.check(self._native.l.coati_tokenizer_encode_batch(self._native.h, arr, len(texts), self.n_seq,
+                                                                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(lens.data_ptr()), 0),
+                       "tokenizer_encode_batch")
+        pad = self.vocab["[PAD]"]
+        if pad != 0:   # the native encoder zero-fills
+            out[torch.arange(self.n_seq) >= lens.clamp(min=0).unsqueeze(1).to(torch.long)] = pad
+        return out, lens
+
     def batch_smiles(self, smiles_batch: List[str], device: str = "cpu", skip_failed: bool = False) -> Tuple[torch.Tensor, List[int]]:
         rows = ["[SMILES]" + smi + "[STOP]" for smi in smiles_batch]
         arr, _keep = _c_strings(rows)

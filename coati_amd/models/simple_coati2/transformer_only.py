@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from ...engine import Engine, ModelConfig
-from ..encoding.clip_e2e import _attach, injection_prefix, reference_parameter_order, torch_default_init
+from ..encoding.clip_e2e import _attach, attach_xformer_logits, injection_prefix, reference_parameter_order, torch_default_init
 
 
 class SwiGLUResNet(nn.Module):
@@ -72,6 +72,8 @@ class COATI_Smiles_Inference(nn.Module):
         object.__setattr__(self.xformer, "generate_top_k_with_inj_batch", eng.generate_top_k_with_inj_batch)
         object.__setattr__(self.xformer, "generate_topk_batch", eng.generate_topk_batch)
         object.__setattr__(self.xformer, "generate_topk_with_inj", eng.generate_topk_with_inj)
+        # xformer(idx) / xformer.forward_with_replacement(idx, injection, tokenizer): f32 logits of the padded rows
+        attach_xformer_logits(self.xformer, eng)
         # model.coati_to_token(h) as in the reference: SwiGLUResNet(E, E) on [B, E] rows (HIP LayerNorm, exact-f32 products, SwiGLU kernel)
         object.__setattr__(self.coati_to_token, "forward", eng.token_head)
         self.reset_parameters()

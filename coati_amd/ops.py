@@ -182,6 +182,36 @@ def swiglu(u, out=None):
     return out
 
 
+def group_mean_rows(x, off, w=None, fallback=None, out=None):
+    """Segmented weighted mean (coati_group_mean_rows): out[g] = sum_{i in [off[g], off[g+1])} w[i] x[i] / sum w[i]; an empty group
+    copies fallback[g].  x [N, E] f32 (row stride free), off [G + 1] int32 on the device, w [N] f32 or None (weights 1), fallback [G, E]
+    f32 (None: zeros).  Rows are summed in index order: the same bits on every call.  `off` is checked on the host when it is a
+    host tensor or list (a device tensor is trusted as given)."""
+    _need_cuda(x)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    N, E = x.shape
+    if not isinstance(off, torch.Tensor) or not off.is_cuda:
+        o = torch.as_tensor(off, dtype=torch.int64)
+        assert o.dim() == 1 and o.numel() >= 2 and int(o[0]) >= 0 and bool((o[1:] >= o[:-1]).all()) and int(o[-1]) <= N, "group_mean_rows: bad off"
+        off = o.to(x.device, torch.int32)
+    assert off.dtype == torch.int32 and off.is_contiguous()
+    G = off.numel() - 1
+    if w is not None:
+        w = w.to(x.device, torch.float32).contiguous()
+        assert w.shape == (N,)
+    if fallback is None:
+        fallback = torch.zeros(G, E, device=x.device, dtype=torch.float32)
+    fallback = fallback.to(x.device, torch.float32).contiguous()
+    assert fallback.shape == (G, E)
+    if out is None:
+        out = torch.empty(G, E, device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == (G, E) and out.is_contiguous()
+    if N == 0:   # every group is empty (and x has no storage to point at)
+        return out.copy_(fallback)
+    _lib.call("coati_group_mean_rows", ptr(x), x.stride(0), ptr(off), ptr(w), ptr(fallback), ptr(out), G, E, stream())
+    return out
+
+
 def layernorm_fwd(x, gamma=None, beta=None, want16=True, want32=False):
     _need_cuda(x)
     M, C = x.shape

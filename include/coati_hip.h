@@ -213,6 +213,12 @@ int coati_silu(const float* x, float* y, int64_t n, void* stream);
 /* SwiGLU gate of the COATI2 heads (simple_coati2/transformer_only.py:38-42): x, gate = u.chunk(2, -1); g = silu(gate) * x, i.e.
    g[b * ldg + j] = u[b * ldu + j] * silu(u[b * ldu + N + j]) for b < B, j < N; f32, ldu >= 2N, ldg >= N */
 int coati_swiglu(const float* u, int64_t ldu, float* g, int64_t ldg, int B, int N, void* stream);
+/* Segmented weighted mean (batched purify_vector, coati/generative/coati_purifications.py:51-97): out[g] = sum over rows i in
+   [off[g], off[g+1]) of w[i] * x[i] / sum w[i] (w null: every weight 1); an empty group copies fallback[g].  x rows of E f32 with
+   stride ldx; off [G + 1] int32 (non-decreasing, off[G] <= rows of x); fallback / out [G, E] f32.  One workgroup per group, the rows
+   summed in index order: repeated calls give the same bits. */
+int coati_group_mean_rows(const float* x, int64_t ldx, const int32_t* off, const float* w, const float* fallback, float* out, int G, int E,
+                          void* stream);
 
 /* decode-time operators: one query per (sequence, head) against the KV cache [B, nh, Tmax, k16|v16] (appends position
    pos first), and top-k sampling: token = inds[multinomial(softmax(topk(logits, k) * inv_temp))] with the caller's
@@ -406,6 +412,20 @@ int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_
 int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
                        const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
                        float* scal, void* stream);
+
+/* encode_tokens on PACKED rows (coati_engine_encode's token tower, COATI1 and COATI2): the encoder pass runs on the concatenation of the
+ * rows' real prefixes, rows1 = sum over rows of (1 + last non-[PAD] position) of raw_tokens [B,T1], counted by the caller on the host.
+ * h_smiles [B,E] f32 equals the padded encode's to bf16 rounding.  scal[6] bit 0: a row without exactly one [STOP]; bit 1: rows1
+ * differs from the count the device finds.  Workspace as for coati_engine_encode (A = 1); nothing is kept for a backward. */
+int coati_engine_encode_packed(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, const int64_t* raw_tokens,
+                               int64_t rows1, float* h_smiles, float* scal, void* stream);
+/* RotarySmilesTransformer.forward / forward_with_replacement (smiles_xformer.py:375-382, 426-454): the decoder pass over the padded
+ * tokens [B,T] int64 and the lm_head, logits [B*T, ldl] f32 (ldl >= n_tok).  injection: null, or [B,C] f32 written over every [UNK]
+ * position of row b (after the embedding LayerNorm on norm_embed engines).  Works on COATI1 and COATI2 engines, without a gradient
+ * buffer; nothing is kept for coati_engine_backward / coati_engine_logits.  Workspace as for coati_engine_forward with (B, T1 = 1, T2 = T,
+ * A = 1).  scal[0..15] is zeroed. */
+int coati_engine_decoder_logits(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T, const int64_t* tokens,
+                                const float* injection, float* logits, int64_t ldl, float* scal, void* stream);
 
 /* logits [B*T2, ldl] f32 of the last forward (API parity with forward_dist's third return value) */
 int coati_engine_logits(coati_engine* e, float* logits, int64_t ldl, void* stream);
