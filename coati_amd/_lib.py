@@ -61,6 +61,10 @@ _SIGS = {
     "coati_topk_sample": [P, L, I, I, I, F, P, P, P, I, I, P],
     "coati_topk_sample_prompt": [P, L, I, I, I, F, P, P, L, P, I, P, P, I, I, P],
     "coati_engine_decode_prefill": [P, P, L, P, I, P, P, L, P],
+    "coati_attn_decode_rows": [P, P, P, I, I, I, I, P, P],
+    "coati_topk_sample_rows": [P, L, I, I, I, F, P, L, P, L, P, P, P, P, L, P, P, I, I, P],
+    "coati_engine_decode_step_rows": [P, P, P, P, P, P, L, P],
+    "coati_engine_decode_prefill_rows": [P, P, L, P, L, P, L, P, P, L, P],
     "coati_engine_decode_begin": [P, P, L, I, I],
     "coati_engine_decode_step": [P, P, P, P, L, P],
     "coati_engine_decode_pos": [P],

@@ -242,6 +242,16 @@ int coati_topk_sample_prompt(const float* logits, int64_t ldl, int B, int V, int
   return launch_topk_sample_prompt(logits, ldl, B, V, k, inv_temp, u, LL(prompt), ldp, plen, pos, reinterpret_cast<long long*>(tokens_out),
                                    stopped, stop_token, pad_token, S_(stream));
 }
+int coati_attn_decode_rows(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int head_size, int Tmax, const int32_t* pos,
+                           void* stream) {
+  return launch_attn_decode_rows(qkv, cache, y, B, n_head, head_size, Tmax, pos, S_(stream));
+}
+int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
+                           const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
+                           int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {
+  return launch_topk_sample_rows(logits, ldl, B, V, k, inv_temp, u, ldu, LL(prompt), ldp, plen, req, pos, reinterpret_cast<long long*>(out), ldo,
+                                 reinterpret_cast<long long*>(tok_next), done, Tmax, stop_token, S_(stream));
+}
 int coati_batch_ncols(const int64_t* tokens, int B, int n_seq, int32_t* ncols, void* stream) {
   return launch_batch_ncols(LL(tokens), B, n_seq, ncols, S_(stream));
 }

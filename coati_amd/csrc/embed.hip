@@ -298,6 +298,21 @@ int launch_seq_pack(const long long* tok, const long long* y, int pad_token, int
   return COATI_OK;
 }
 
+// The same row map from lengths the caller already has (ragged prompt prefill: len[b] tokens of row b count, whatever their ids --
+// a prompt may contain the [PAD] id).  len: [B] int32 on the device, every entry in 1 .. T (the caller checked it on the host);
+// the scan flags a total that differs from rows_expect (err |= 2) and the fill stays inside rows_expect rows either way.
+int launch_seq_pack_len(const int* len, int B, int T, int rows_expect, int* off, int* row_src, int* row_t, int* err, hipStream_t s, int* ord) {
+  COATI_CHECK_ARG(len && off && row_src && row_t && err, "seq_pack_len: null operand");
+  COATI_CHECK_SHAPE(B > 0 && T > 0 && rows_expect > 0 && rows_expect <= (long long)B * T, "seq_pack_len: bad row count %d for %d x %d", rows_expect, B, T);
+  hipError_t h = hipMemcpyAsync(off, len, sizeof(int) * B, hipMemcpyDeviceToDevice, s);
+  if (h != hipSuccess) { coati_set_error("seq_pack_len: hipMemcpyAsync failed: %s", hipGetErrorString(h)); return COATI_EHIP; }
+  hipLaunchKernelGGL(seq_scan_kernel, dim3(1), dim3(1024), 0, s, off, B, rows_expect, err, ord);
+  hipLaunchKernelGGL(seq_fill_kernel, dim3(cdiv((long long)B * T, 256)), dim3(256), 0, s, off, (const long long*)nullptr, row_src, row_t,
+                     (long long*)nullptr, B, T, rows_expect);
+  COATI_LAUNCH_CHECK("seq_pack_len");
+  return COATI_OK;
+}
+
 __global__ void bad_rows_kernel(const long long* __restrict__ tok, unsigned char* __restrict__ bad, int B, int T) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;

@@ -236,6 +236,7 @@ struct coati_engine {
   struct Decode {
     bool active = false;
     int B = 0, Tmax = 0, pos = 0;
+    bool ragged = false;       // a per-row-position entry has run (decode_step_rows / decode_prefill_rows): the host-side pos is not theirs
     bf16_t* cache = nullptr;   // [L][B][nh][Tmax][k16|v16]
     float *x = nullptr, *xmid = nullptr, *xn = nullptr, *mean = nullptr, *rstd = nullptr;
     bf16_t *a = nullptr, *qkv = nullptr, *y = nullptr, *hpre = nullptr, *g = nullptr, *af = nullptr;
@@ -246,6 +247,9 @@ struct coati_engine {
     float* logits_dev = nullptr;
     int64_t ldl = 0;
     hipGraphExec_t graph[2] = {nullptr, nullptr};   // [0] tokens only, [1] tokens + injection
+    // ragged steps (decode_step_rows): per-row rotary position (idle slots: 0) and the token vector the injection rule reads
+    int* rope_t = nullptr;
+    long long* tok_inj = nullptr;
   } dec;
   double prof_bytes = 0.0;   // algorithmic HBM bytes (operands read once, results written once) of the selected site
   // the E(3)-GNN's edge-level launches: their row count (the compacted neighbour list's length, g_ne[0]) lives on the device, so the
@@ -2293,6 +2297,8 @@ size_t decode_carve(coati_engine* e, Arena& ar, int B, int Tmax) {
   d.inj_dev = ar.take<float>(B * C);
   d.ldl = ((int64_t)c.n_tok + 7) / 8 * 8;
   d.logits_dev = ar.take<float>((size_t)B * d.ldl);
+  d.rope_t = ar.take<int>(B);
+  d.tok_inj = ar.take<long long>(B);
   return (ar.off + 255) & ~(size_t)255;
 }
 }  // namespace
@@ -2317,6 +2323,7 @@ int coati_engine_decode_begin(coati_engine* e, void* workspace, int64_t ws_bytes
   decode_carve(e, ar, B, Tmax);
   e->dec.active = true;
   e->dec.B = B; e->dec.Tmax = Tmax; e->dec.pos = 0;
+  e->dec.ragged = false;
   return COATI_OK;
 }
 
@@ -2327,15 +2334,24 @@ int coati_engine_decode_pos(coati_engine* e) { return (e && e->dec.active) ? e->
 namespace {
 // Enqueue one decode position.  graph_mode: the position comes from device memory (d.pos_dev) so that the very same
 // launch sequence can be replayed from a captured graph, and the sequence ends by incrementing it.
+// pos_rows (ragged step, not with graph_mode): row b sits at its own position pos_rows[b] (device; outside 0 .. Tmax - 1 = idle slot)
+// instead of the session's d.pos; inj_len (optional, with pos_rows): row b reads the injection only while pos_rows[b] < inj_len[b].
+// Idle slots ride through the row-wise products and LayerNorms (M stays B): their rotary index is clamped to a valid table row
+// (launch_decode_rows_prep), and what they compute is read by nobody -- the attention skips them, every other launch is row-wise.
 int decode_enqueue(coati_engine* e, const long long* tokens, const float* injection, float* logits, int64_t ldl,
-                   bool graph_mode, hipStream_t s) {
+                   bool graph_mode, hipStream_t s, const int* pos_rows = nullptr, const int* inj_len = nullptr) {
   auto& d = e->dec;
   const coati_config& c = e->cfg;
   const int C = c.n_hidden_xformer, L = c.n_layer_xformer, B = d.B, hs = C / c.n_head;
+  if (pos_rows) COATI_TRY(launch_decode_rows_prep(pos_rows, inj_len, tokens, d.rope_t, d.tok_inj, B, d.Tmax, s));
+  const long long* inj_tok = (pos_rows && inj_len) ? d.tok_inj : tokens;   // the ids the [UNK]-injection rule looks at
   if (c.norm_embed) {
     COATI_TRY(launch_embed_fwd(tokens, e->P + e->tok_emb, nullptr, c.unk_token, d.xmid, B, 1, C, c.n_tok, s));   // (xmid: free until the first block writes it)
     COATI_TRY(launch_layernorm_fwd(d.xmid, C, e->P + e->emb_lnw, e->P + e->emb_lnb, nullptr, 0, d.x, C, d.mean, d.rstd, B, C, s));
-    if (injection != nullptr) COATI_TRY(launch_embed_fwd(tokens, nullptr, injection, c.unk_token, d.x, B, 1, C, c.n_tok, s, nullptr, 0, 1));
+    if (injection != nullptr) COATI_TRY(launch_embed_fwd(inj_tok, nullptr, injection, c.unk_token, d.x, B, 1, C, c.n_tok, s, nullptr, 0, 1));
+  } else if (injection != nullptr && inj_tok != tokens) {   // the gather from the table, then the injected rows over it
+    COATI_TRY(launch_embed_fwd(tokens, e->P + e->tok_emb, nullptr, c.unk_token, d.x, B, 1, C, c.n_tok, s));
+    COATI_TRY(launch_embed_fwd(inj_tok, nullptr, injection, c.unk_token, d.x, B, 1, C, c.n_tok, s, nullptr, 0, 1));
   } else {
     COATI_TRY(launch_embed_fwd(tokens, e->P + e->tok_emb, injection, c.unk_token, d.x, B, 1, C, c.n_tok, s));
   }
@@ -2349,7 +2365,9 @@ int decode_enqueue(coati_engine* e, const long long* tokens, const float* inject
       memset(&a, 0, sizeof(a));
       a.A = d.a; a.lda = C; a.B = e->S + w.attnw; a.ldb = C; a.M = B; a.N = 3 * C; a.K = C; a.C = d.qkv; a.ldc = 3 * C;
       a.bias = e->P + w.attnb; a.rope_hs = hs; a.rope_T = 1; a.rope_C = C;
-      if (graph_mode) {   // every row sits at token position *pos_dev
+      if (pos_rows) {     // row b sits at token position rope_t[b] (= pos_rows[b]; idle slots: 0, a valid table row)
+        a.rope_cos = e->cos_t; a.rope_sin = e->sin_t; a.rope_row_t = d.rope_t;
+      } else if (graph_mode) {   // every row sits at token position *pos_dev
         a.rope_cos = e->cos_t; a.rope_sin = e->sin_t; a.rope_pos = d.pos_dev;
       } else {            // every row sits at token position pos: tables offset to that row, period 1
         a.rope_cos = e->cos_t + (size_t)d.pos * hs; a.rope_sin = e->sin_t + (size_t)d.pos * hs;
@@ -2357,7 +2375,8 @@ int decode_enqueue(coati_engine* e, const long long* tokens, const float* inject
       COATI_TRY(launch_gemm_nt(a, 0, EPI_QKV_ROPE, s));
     }
     bf16_t* cache_l = d.cache + (size_t)l * B * C * d.Tmax * 2;
-    COATI_TRY(launch_attn_decode(d.qkv, cache_l, d.y, B, c.n_head, hs, d.Tmax, d.pos, graph_mode ? d.pos_dev : nullptr, s));
+    if (pos_rows) COATI_TRY(launch_attn_decode_rows(d.qkv, cache_l, d.y, B, c.n_head, hs, d.Tmax, pos_rows, s));
+    else COATI_TRY(launch_attn_decode(d.qkv, cache_l, d.y, B, c.n_head, hs, d.Tmax, d.pos, graph_mode ? d.pos_dev : nullptr, s));
     COATI_TRY(gemm(e, SITE_NONE, d.y, 0, C, e->S + w.projw, C, B, C, C, xm, C, e->P + w.projb, EPI_RES_F32, x, nullptr, C, s));
     COATI_TRY(launch_layernorm_fwd(xm, C, e->P + w.ln2w, e->P + w.ln2b, d.a, C, nullptr, 0, d.mean, d.rstd, B, C, s));
     COATI_TRY(gemm(e, SITE_NONE, d.a, 0, C, e->S + w.fc1w, C, B, 4 * C, C, d.g, 4 * C, e->P + w.fc1b, EPI_GELU, nullptr, d.hpre, 4 * C, s));
@@ -2431,6 +2450,69 @@ int coati_engine_decode_prefill(coati_engine* e, void* workspace, int64_t ws_byt
   }
   COATI_TRY(launch_add_int(d.pos_dev, m, 1, s));   // a captured decode graph continues from position m
   d.pos = m;
+  return COATI_OK;
+}
+
+// One position for every LIVE row, each at its own: row b appends tokens[b] at pos[b] and attends to 0 .. pos[b] (pos: int32 [B] on the
+// device, the caller's; the session's host-side position is not used and does not move).  pos[b] < 0 (or >= Tmax) is an idle slot:
+// its cache records are untouched and its logits row is meaningless.  A slot may be set back to position 0 at any step: cache
+// entries behind a row's position are never read.  injection as in decode_step; inj_len (optional, int32 [B] on the device): row b
+// reads the injection only while pos[b] < inj_len[b] (the forced prefix of a request; a sampled [UNK] id takes the table's row).
+int coati_engine_decode_step_rows(coati_engine* e, const int64_t* tokens, const int32_t* pos, const float* injection, const int32_t* inj_len,
+                                  float* logits, int64_t ldl, void* stream) {
+  COATI_CHECK_ARG(e && e->dec.active && tokens && pos, "decode_step_rows: no decode session / null tokens or positions");
+  COATI_CHECK_ARG(!logits || ldl >= e->cfg.n_tok, "decode_step_rows: ldl too small");
+  COATI_CHECK_ARG(!inj_len || injection, "decode_step_rows: inj_len without an injection");
+  e->dec.ragged = true;
+  return decode_enqueue(e, reinterpret_cast<const long long*>(tokens), injection, logits, ldl, false, (hipStream_t)stream, pos, inj_len);
+}
+
+// Ragged prompt prefill: positions 0 .. plen[b] - 1 of EVERY row of a fresh session as one transformer pass on packed rows (the
+// row map comes from plen, not from [PAD] ids: a prompt may contain id 0), the pass's rotated k and v into the cache per layer, and
+// ln_f + the f32 lm_head on the B last-prompt rows only (gathered into the decode step's own buffers): logits[b] are those of
+// position plen[b] - 1, and the ragged steps continue with pos[b] = plen[b].  prompt: [B, ldp] int64; plen: int32 [B] on the device,
+// every entry in 1 .. min(ldp, Tmax) (the caller checks it where the lengths are made); rows: their sum, from the host.  The same
+// refusals as coati_engine_decode_prefill; nothing is kept for a backward, no training state moves.
+int coati_engine_decode_prefill_rows(coati_engine* e, void* workspace, int64_t ws_bytes, const int64_t* prompt, int64_t ldp,
+                                     const int32_t* plen, int64_t rows, const float* injection, float* logits, int64_t ldl, void* stream) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && prompt && plen, "decode_prefill_rows: engine not bound / null argument");
+  COATI_CHECK_ARG(e->dec.active, "decode_prefill_rows: no decode session");
+  auto& d = e->dec;
+  const coati_config& c = e->cfg;
+  COATI_CHECK_ARG(d.pos == 0 && !d.ragged, "decode_prefill_rows: the session has already stepped (prefill starts a fresh session)");
+  COATI_CHECK_ARG(!c.use_fp8, "decode_prefill_rows: not on fp8 engines (the pass would run MXFP8 products, the decode step runs bf16 ones): "
+                              "feed the prompts with decode_step_rows");
+  const int B = d.B, C = c.n_hidden_xformer, L = c.n_layer_xformer, hs = C / c.n_head;
+  COATI_CHECK_SHAPE(ldp >= 1 && ldp <= d.Tmax && rows >= B && rows <= (int64_t)B * ldp,
+                    "decode_prefill_rows: unsupported prompts ldp=%lld rows=%lld (B=%d, Tmax=%d; every length in 1 .. ldp <= Tmax)",
+                    (long long)ldp, (long long)rows, B, d.Tmax);
+  COATI_CHECK_ARG(!logits || ldl >= c.n_tok, "decode_prefill_rows: ldl too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int T = (int)ldp;
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)ws_bytes, false};
+  const size_t need = carve(e, ar, B, 1, T, 1, B);
+  COATI_CHECK_ARG((int64_t)need <= ws_bytes, "decode_prefill_rows: workspace too small (%zu > %lld)", need, (long long)ws_bytes);
+  if (e->nce) e->nce_cap = ((size_t)ws_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = 1; e->T2 = T; e->A = 1;
+  e->p1.idx = nullptr;
+  e->p2.idx = reinterpret_cast<const long long*>(prompt);
+  e->have_fwd = false;
+  e->decoder_pending = false;
+  e->have_ws = true;
+  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(launch_seq_pack_len(plen, B, T, (int)rows, e->p2.off, e->p2.row_src, e->p2.row_t, e->err_flag, s, e->p2.ord));
+  e->p2.packed = true;
+  e->p2.M = (int)rows;
+  e->p2.tail = false;
+  COATI_TRY(xformer_fwd(e, e->p2, injection, s));
+  for (int l = 0; l < L; ++l)
+    COATI_TRY(launch_kv_cache_fill_rows(e->p2.qkv[l], d.cache + (size_t)l * B * C * d.Tmax * 2, e->p2.row_src, (int)rows, B, T, c.n_head, hs, d.Tmax, s));
+  if (logits) {
+    COATI_TRY(launch_gather_last_rows(e->p2.x[L], e->p2.off, d.x, B, C, (int)rows, s));
+    COATI_TRY(launch_layernorm_fwd(d.x, C, e->P + e->lnfw, e->P + e->lnfb, d.af, C, nullptr, 0, d.mean, d.rstd, B, C, s));
+    COATI_TRY(gemm(e, SITE_NONE, d.af, 0, C, e->S + e->lmhead, C, B, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
+  }
+  d.ragged = true;
   return COATI_OK;
 }
 

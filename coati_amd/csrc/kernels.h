@@ -298,6 +298,9 @@ int launch_embed_bwd(const long long* idx, const float* dx, float* dtable, float
 // differs from rows_expect (the count the caller computed on the host)
 int launch_seq_pack(const long long* tok, const long long* y, int pad_token, int B, int T, int rows_expect, int* off,
                     int* row_src, int* row_t, long long* ypk, int* err, hipStream_t s, int* ord = nullptr);
+// the same map from per-row lengths len[B] (device, each in 1 .. T) instead of from the [PAD] ids
+int launch_seq_pack_len(const int* len, int B, int T, int rows_expect, int* off, int* row_src, int* row_t, int* err, hipStream_t s,
+                        int* ord = nullptr);
 // pos[b] = position of the single stop token of row b; err[0] |= 1 if some row has != 1 stop tokens
 int launch_find_stop(const long long* idx, int stop_token, int* pos, int* err, int B, int T, hipStream_t s);
 int launch_gather_rows(const float* x, const int* pos, float* out, int B, int T, int C, hipStream_t s, const int* off = nullptr);
@@ -311,12 +314,26 @@ int launch_bad_rows(const long long* tokens, unsigned char* bad, int B, int T, h
 int launch_attn_decode(const bf16_t* qkv, bf16_t* cache, bf16_t* y, int B, int n_head, int head_size, int Tmax, int pos,
                        const int* pos_dev, hipStream_t s);
 int launch_add_int(int* x, int v, int set, hipStream_t s);
+// ragged sessions: row b at its own position pos[b] (device); a position outside 0 .. Tmax - 1 = idle slot (nothing read or written)
+int launch_attn_decode_rows(const bf16_t* qkv, bf16_t* cache, bf16_t* y, int B, int n_head, int head_size, int Tmax, const int* pos,
+                            hipStream_t s);
+// rope_t[b] = pos[b] or 0 (idle); tok_inj[b] = tokens[b] where the row may read the injection (pos[b] < inj_len[b]; null: always), else -1
+int launch_decode_rows_prep(const int* pos, const int* inj_len, const long long* tokens, int* rope_t, long long* tok_inj, int B, int Tmax,
+                            hipStream_t s);
 int launch_topk_sample(const float* logits, long long ldl, int B, int V, int k, float inv_temp, const float* u,
                        long long* tok_out, int* stopped, int stop_token, int pad_token, hipStream_t s);
 // per-row prompts: rows with pos < plen[b] emit prompt[b * ldp + pos] (no draw), the others sample as launch_topk_sample
 int launch_topk_sample_prompt(const float* logits, long long ldl, int B, int V, int k, float inv_temp, const float* u,
                               const long long* prompt, long long ldp, const int* plen, int pos, long long* tok_out, int* stopped,
                               int stop_token, int pad_token, hipStream_t s);
+// ragged sampler (decode.hip): slot b serves request r = req ? req[b] : b and holds pos[b] + 1 tokens (pos[b] < 0: idle)
+int launch_topk_sample_rows(const float* logits, long long ldl, int B, int V, int k, float inv_temp, const float* u, long long ldu,
+                            const long long* prompt, long long ldp, const int* plen, const int* req, int* pos, long long* out,
+                            long long ldo, long long* tok_next, int* done, int Tmax, int stop_token, hipStream_t s);
+// ragged prefill: packed qkv rows [R, 3C] into one layer's cache by the pass's row map (row_src[r] = b * T + t)
+int launch_kv_cache_fill_rows(const bf16_t* qkv, bf16_t* cache, const int* row_src, int R, int B, int T, int n_head, int head_size,
+                              int Tmax, hipStream_t s);
+int launch_gather_last_rows(const float* x, const int* off, float* out, int B, int C, int R, hipStream_t s);
 // prompt prefill: the rotated k and the v of a padded [B, m] pass's qkv into one layer's cache [B][nh][Tmax][k|v], positions 0..m-1
 int launch_kv_cache_fill(const bf16_t* qkv, bf16_t* cache, int B, int m, int n_head, int head_size, int Tmax, hipStream_t s);
 // batch tail (batch.hip)

@@ -488,6 +488,7 @@ class Engine:
             raise RuntimeError("decode_begin: bad shape")
         self._dec_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
         self._dec_B = int(B)
+        self._dec_Tmax = Tmax
         _lib.check(self.l.coati_engine_decode_begin(self.h, ctypes.c_void_p(self._dec_ws.data_ptr()), n, int(B), Tmax), "decode_begin")
 
     def decode_step(self, tokens, injection=None, want_logits=True, graph=False):
@@ -536,6 +537,64 @@ class Engine:
                                                       ptr(logits), ld, stream()), "decode_prefill")
         self._shape = None
         return logits[:, :V] if want_logits else None
+
+    # ---- ragged sessions: every row at its own position -------------------------------------------------------------
+    def decode_step_rows(self, tokens, pos, injection=None, inj_len=None, want_logits=True):
+        """decode_step with a position per row: row b appends tokens[b] at pos[b] and attends to 0 .. pos[b].  pos: int32 [B] on the
+        device (the caller's; nothing is advanced here); pos[b] < 0 marks an idle slot: its cache is untouched and its logits row
+        means nothing.  A slot may be set back to position 0 at any step (what lies behind a row's position is never read).
+        inj_len (int32 [B], device; optional): row b reads `injection` only while pos[b] < inj_len[b]."""
+        B = self._dec_B
+        tokens = tokens.to(self.device, torch.long).contiguous()
+        assert tokens.shape == (B,)
+        assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.shape == (B,) and pos.device == tokens.device, "pos: int32 [B] on the device"
+        inj = None
+        if injection is not None:
+            inj = injection.to(self.device, torch.float32).contiguous()
+            assert inj.shape == (B, self.cfg.n_hidden_xformer)
+        if inj_len is not None:
+            assert inj is not None and inj_len.dtype == torch.int32 and inj_len.is_contiguous() and inj_len.shape == (B,)
+            assert inj_len.device == tokens.device
+        V = self.cfg.n_tok
+        ld = (V + 7) // 8 * 8
+        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
+        _lib.check(self.l.coati_engine_decode_step_rows(self.h, ptr(tokens), ptr(pos), ptr(inj), ptr(inj_len), ptr(logits), ld, stream()),
+                   "decode_step_rows")
+        return logits[:, :V] if want_logits else None
+
+    def decode_prefill_rows(self, prompt, plen, injection=None, want_logits=True):
+        """Every row's WHOLE prompt of a fresh session in one transformer pass on packed rows: prompt [B, W] int64 (row b counts
+        plen[b] tokens, whatever their ids), plen [B] with 1 <= plen[b] <= W <= Tmax.  Returns the logits [B, n_tok] f32 of position
+        plen[b] - 1 (or None); continue with decode_step_rows at pos[b] = plen[b].  Refused behind any step and on fp8 engines."""
+        B = self._dec_B
+        prompt = prompt.to(self.device, torch.long).contiguous()
+        assert prompt.dim() == 2 and prompt.shape[0] == B, prompt.shape
+        W = int(prompt.shape[1])
+        plen_h = plen.detach().to("cpu", torch.int64)
+        assert plen_h.shape == (B,)
+        Tmax = self._dec_Tmax
+        if int(plen_h.min()) < 1 or int(plen_h.max()) > min(W, Tmax):
+            raise ValueError(f"decode_prefill_rows: prompt lengths {int(plen_h.min())} .. {int(plen_h.max())}; 1 .. {min(W, Tmax)} fit")
+        plen_d = plen.to(self.device, torch.int32).contiguous()
+        inj = None
+        if injection is not None:
+            inj = injection.to(self.device, torch.float32).contiguous()
+            assert inj.shape == (B, self.cfg.n_hidden_xformer)
+        self._ensure_workspace(B, 1, W, 1)
+        V = self.cfg.n_tok
+        ld = (V + 7) // 8 * 8
+        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
+        self._keep = (prompt, plen_d, inj)
+        _lib.check(self.l.coati_engine_decode_prefill_rows(self.h, ptr(self.workspace), self.workspace.numel(), ptr(prompt), W, ptr(plen_d),
+                                                           int(plen_h.sum()), ptr(inj), ptr(logits), ld, stream()), "decode_prefill_rows")
+        self._shape = None
+        return logits[:, :V] if want_logits else None
+
+    def _sample_rows(self, logits, k, inv_temp, u, ldu, prompt, plen, req, pos, out, tok_next, done, Tmax, stop_token):
+        """coati_topk_sample_rows on the session's B slots (see include/coati_hip.h)."""
+        _lib.call("coati_topk_sample_rows", ptr(logits), logits.stride(0), int(logits.shape[0]), self.cfg.n_tok, int(k), float(inv_temp),
+                  ptr(u), int(ldu), ptr(prompt), int(prompt.stride(0)) if prompt is not None else 0, ptr(plen), ptr(req), ptr(pos), ptr(out),
+                  int(out.stride(0)), ptr(tok_next), ptr(done), int(Tmax), int(stop_token), stream())
 
     def decode_graph_build(self):
         """Capture the decode step into HIP graphs (call inside `with torch.cuda.stream(side_stream)`)."""
@@ -592,14 +651,18 @@ class Engine:
             return torch.cat([torch.tensor(prefix, dtype=torch.long, device=dev).unsqueeze(0).repeat(B, 1), gen], dim=1)
         return [prefix + row for row in gen.tolist()]
 
-    def generate_topk_batch(self, prefix, stop_token, pad_token=0, inv_temp=2, k=10, generator=None, prefill=True):
+    def generate_topk_batch(self, prefix, stop_token, pad_token=0, inv_temp=2, k=10, generator=None, prefill=True, ragged=False):
         """RotarySmilesTransformer.generate_topk_batch (smiles_xformer.py:157-198): continue B prompts of different lengths
         (token lists) on the KV-cached decode path.  Returns B lists of n_seq ints: every prompt verbatim, each row sampled
         from its own prompt end (softmax(top-k logits * inv_temp), uniforms from `generator`), [STOP] and then pad_token,
         zeros behind the last written column.  The loop ends when every row has stopped or column n_seq - 1 is written.
         prefill=True runs the shortest prompt's length as one pass (decode_prefill); the longer prompts' remaining tokens,
-        and with prefill=False every prompt token behind the first, are fed through forced steps."""
-        out, _ = self._complete(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, None)
+        and with prefill=False every prompt token behind the first, are fed through forced steps.
+        ragged=True: every prompt is prefilled in FULL (decode_prefill_rows) and the rows then step at their own positions, each
+        sampling from its own prompt end at once; a row is done when it draws [STOP], and the call when every row is.  Same output
+        format.  Off by default: with k > 1 the uniforms reach the rows in another order, so a seed's samples differ from the
+        aligned path's.  (fp8 engines: the prompts go through forced ragged steps.)"""
+        out, _ = self._complete(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, None, ragged)
         return out.tolist()
 
     def generate_topk_with_inj(self, prefix, stop_token, inv_temp=1, k=50, inj_token=None, inj_payload=None, generator=None,
@@ -624,13 +687,14 @@ class Engine:
         out, n = self._complete([prefix], stop_token, 0, inv_temp, k, generator, prefill, inj)
         return out[0, :n].tolist()
 
-    def _complete(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection):
+    def _complete(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection, ragged=False):
         """The decode loop of generate_topk_batch / generate_topk_with_inj on a private stream.  Returns (tokens [B, n_seq] on
         the host, number of columns written)."""
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            out = self._complete_on_stream(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection)
+            fn = self._complete_rows_on_stream if ragged else self._complete_on_stream
+            out = fn(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection)
         torch.cuda.current_stream(self.device).wait_stream(side)
         return out
 
@@ -662,6 +726,140 @@ class Engine:
                 break
             logits = self.decode_step(nxt, injection)
         return out.cpu(), pos
+
+    def _complete_rows_on_stream(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection):
+        """_complete_on_stream on a ragged session: the whole of every prompt in one packed pass, then steps in which row b sits at
+        its own position.  Returns (tokens [B, n_seq] on the host, number of columns written)."""
+        n_seq = int(self.cfg.n_seq)
+        prompt, plen = pack_prompts(prefix, n_seq)
+        B = prompt.shape[0]
+        longest = int(plen.max())
+        dev = self.device
+        prompt_d, plen_d = prompt.to(dev), plen.to(dev)
+        out = prompt_d.clone()                       # prompts verbatim (zeros behind them)
+        cols = torch.arange(n_seq).unsqueeze(0)
+        in_prompt = (prompt == int(stop_token)) & (cols < plen.unsqueeze(1))
+        has_stop = in_prompt.any(1)
+        first_stop = torch.where(has_stop, in_prompt.to(torch.int64).argmax(1) + 1, torch.zeros(B, dtype=torch.int64))
+        self.decode_begin(B, n_seq)
+        tok = prompt_d[:, 0].clone()
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
+        if prefill and not self.cfg.fp8:
+            logits = self.decode_prefill_rows(prompt_d[:, :longest], plen_d, injection)
+            # a prompt that holds a [STOP] is a finished row (its slot stays idle); a prompt of n_seq tokens is retired by the sampler
+            pos_h = torch.where(has_stop, torch.full((B,), -1, dtype=torch.int64), plen.to(torch.int64) - 1)
+            done_h = torch.where(has_stop, first_stop, torch.zeros(B, dtype=torch.int64))
+        else:   # (fp8 engines: the prompt goes through forced ragged steps; the sampler's prompt rule ends a row at a [STOP] in it)
+            stop0 = prompt[:, 0] == int(stop_token)
+            pos_h = torch.where(stop0, torch.full((B,), -1, dtype=torch.int64), torch.zeros(B, dtype=torch.int64))
+            done_h = stop0.to(torch.int64)
+            logits = None
+        pos = pos_h.to(torch.int32).to(dev)
+        done.copy_(done_h.to(torch.int32))
+        if logits is None:
+            logits = self.decode_step_rows(tok, pos, injection)
+        while True:
+            u = torch.rand(B, device=dev, generator=generator) if k > 1 else torch.zeros(B, device=dev)
+            self._sample_rows(logits, k, inv_temp, u, 0, prompt_d, plen_d, None, pos, out, tok, done, n_seq, stop_token)
+            if int((pos >= 0).sum().item()) == 0:
+                break
+            logits = self.decode_step_rows(tok, pos, injection)
+        # [STOP], then pad_token up to the column where the longest row ended, zeros behind
+        end = torch.maximum(done.to(torch.int64).cpu(), plen.to(torch.int64))
+        width = max(longest, int(end.max()))
+        out = out.cpu()
+        behind = (cols >= end.unsqueeze(1)) & (cols < width)
+        out[behind] = int(pad_token)
+        return out, width
+
+    def generate_stream(self, prefix, stop_token, pad_token=0, inv_temp=1.0, k=50, inj_token=None, inj_payload=None, slots=None,
+                        generator=None, as_tensor=False, poll=1, forced=None):
+        """generate_top_k_with_inj_batch for N = inj_payload.shape[0] requests on `slots` cache slots (default min(N,
+        slots.STREAM_SLOT_CAP)): a slot whose row has drawn [STOP] is handed the next request at position 0 while the other rows
+        carry on, so no step is spent on finished rows as long as requests wait.  A request enters with the first prefix token and
+        its own injection row; the rest of the prefix goes through forced steps.  Returns the N rows in REQUEST order, shaped like
+        generate_top_k_with_inj_batch's (prefix + generated, pad_token behind [STOP], rows that never stop end in stop_token, width =
+        the longest row of the call).  Request n's uniforms are row n of one [N, n_seq] draw from `generator` at the call: they
+        depend on n and the position, not on the slot or the step the request ran in.
+        poll: the host looks for ended rows every `poll` steps (1: every step, as the aligned loops synchronise every step).
+        forced (tokens [N, W], lengths [N]): request n emits tokens[n, :lengths[n]] through the sampler's prompt rule instead of
+        the prefix (benchmarks with random weights, which never draw [STOP], force their row lengths with it).
+        self.stream_steps holds the number of decode steps the call took."""
+        from .slots import STREAM_SLOT_CAP, SlotScheduler
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            prefix = [int(t) for t in prefix]
+            if inj_token is not None and int(inj_token) != self.cfg.unk_token:
+                raise NotImplementedError("the injection slot must be the engine's [UNK] id")
+            dev, n_seq, C = self.device, int(self.cfg.n_seq), self.cfg.n_hidden_xformer
+            payload = inj_payload.to(dev, torch.float32).contiguous()
+            N = int(payload.shape[0])
+            assert payload.shape == (N, C) and N > 0
+            S = int(slots) if slots is not None else min(N, STREAM_SLOT_CAP)
+            if S < 1:
+                raise ValueError("generate_stream: at least one slot")
+            S = min(S, N)
+            if forced is None:
+                if not 1 <= len(prefix) <= n_seq:
+                    raise ValueError(f"generate_stream: a prefix of {len(prefix)} tokens; 1 .. n_seq = {n_seq} fit")
+                prompt_d = torch.tensor(prefix, dtype=torch.long, device=dev).unsqueeze(0).repeat(N, 1)
+                plen_d = torch.full((N,), len(prefix), dtype=torch.int32, device=dev)
+            else:
+                prompt_d = forced[0].to(dev, torch.long).contiguous()
+                plen_d = forced[1].to(dev, torch.int32).contiguous()
+                assert prompt_d.shape[0] == N and plen_d.shape == (N,) and prompt_d.shape[1] <= n_seq
+                assert int(plen_d.min()) >= 1 and int(plen_d.max()) <= prompt_d.shape[1]
+            P = int(prompt_d.shape[1])
+            u = torch.rand(N, n_seq, device=dev, generator=generator) if k > 1 else None
+            out = torch.zeros(N, n_seq, dtype=torch.long, device=dev)
+            out[:, 0] = prompt_d[:, 0]
+            tok = torch.zeros(S, dtype=torch.long, device=dev)
+            pos = torch.full((S,), -1, dtype=torch.int32, device=dev)
+            req = torch.zeros(S, dtype=torch.int32, device=dev)
+            done = torch.zeros(S, dtype=torch.int32, device=dev)
+            inj = torch.zeros(S, C, dtype=torch.float32, device=dev)
+            inj_len = torch.zeros(S, dtype=torch.int32, device=dev)
+            use_inj = inj_token is not None
+            self.decode_begin(S, n_seq)
+            sched = SlotScheduler(N, S)
+            self.stream_steps = 0
+
+            def step(new):
+                if new:
+                    sl = torch.tensor([s for s, _ in new], dtype=torch.long, device=dev)
+                    rq = torch.tensor([r for _, r in new], dtype=torch.long, device=dev)
+                    tok[sl] = prompt_d[rq, 0]
+                    pos[sl] = 0
+                    req[sl] = rq.to(torch.int32)
+                    done[sl] = 0
+                    inj[sl] = payload[rq]
+                    inj_len[sl] = plen_d[rq]
+                logits = self.decode_step_rows(tok, pos, inj if use_inj else None, inj_len if use_inj else None)
+                self._sample_rows(logits, k, inv_temp, u, n_seq if u is not None else 0, prompt_d, plen_d, req, pos, out, tok, done, n_seq,
+                                  stop_token)
+                self.stream_steps += 1
+                return []
+
+            lens = [0] * N
+            while not sched.finished:
+                new = sched.refill()
+                for i in range(max(1, int(poll))):
+                    step(new if i == 0 else [])
+                d = done.cpu()           # (synchronises: the one look per `poll` steps)
+                for s in torch.nonzero(d).flatten().tolist():
+                    if sched.slot_req[s] >= 0:
+                        lens[sched.retire(s)] = int(d[s])
+                done.zero_()
+            lens_t = torch.tensor(lens, dtype=torch.long, device=dev)
+            width = int(lens_t.max())
+            gen = out[:, :width].clone()
+            if width == n_seq:       # rows that never stopped end in stop_token
+                gen[lens_t == n_seq, n_seq - 1] = int(stop_token)
+            gen[torch.arange(width, device=dev).unsqueeze(0) >= lens_t.unsqueeze(1)] = int(pad_token)
+            res = gen if as_tensor else gen.tolist()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        return res
 
     # ---- profiling ---------------------------------------------------------------------------------------------
     def site_names(self):

@@ -95,16 +95,27 @@ def _embed_padded(encoder, tokenizer, tok: torch.Tensor, pad: int) -> torch.Tens
     return h
 
 
-def _decode_batch(encoder, H: torch.Tensor, tokenizer, generator=None) -> List[str]:
+def _decode_batch(encoder, H: torch.Tensor, tokenizer, generator=None, slots=None) -> List[str]:
     fn = encoder.hcoati_to_2d_batch if _is_coati2(encoder) else encoder.hclip_to_2d_batch
     kw = {} if generator is None else {"generator": generator}
+    if slots is not None:
+        kw["slots"] = slots
     return list(fn(H, tokenizer, **kw))
 
 
-def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=None) -> List[Optional[List[str]]]:
+def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=None, slots=None) -> List[Optional[List[str]]]:
     """n_rep decodes of every row of V [N, E], as few decode calls as DECODE_ROW_CAP allows (whole vectors per call).  Per vector the
-    list of its n_rep strings in sample order, or None when its decode call raised."""
+    list of its n_rep strings in sample order, or None when its decode call raised.
+    slots (a number; default None = the chunked calls): ONE streamed call of all N * n_rep rows on that many cache slots
+    (Engine.generate_stream: a row that has stopped hands its slot to the next one, so the cache holds `slots` rows whatever N is)."""
     N = V.shape[0]
+    if slots is not None:
+        try:
+            got = _decode_batch(encoder, V.repeat_interleave(n_rep, dim=0), tokenizer, generator, slots=int(slots))
+            assert len(got) == N * n_rep
+            return [got[i * n_rep:(i + 1) * n_rep] for i in range(N)]
+        except Exception:
+            return [None] * N
     per_call = max(1, DECODE_ROW_CAP // max(n_rep, 1))
     out: List[Optional[List[str]]] = []
     for lo in range(0, N, per_call):

@@ -318,19 +318,26 @@ class e3gnn_smiles_clip_e2e(nn.Module):
     @torch.no_grad()
     def hclip_to_2d_batch(self, h_clip, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
                           inv_temp: float = 2, k: int = 100, do_suffix=False, keep_special: bool = False,
-                          return_tokens: bool = False, generator=None):
+                          return_tokens: bool = False, generator=None, slots=None):
         """clip_e2e.py:544-588: decode a batch of clip embeddings into token sequences (and SMILES when the tokenizer
         can decode).  Prefix "[CLIP][UNK]" + fill_in_from (+ "[SUFFIX][MIDDLE]"), the [UNK] slot carries the
-        special-token embedding of h_clip; generation = top-k sampling on the KV-cached decode path."""
+        special-token embedding of h_clip; generation = top-k sampling on the KV-cached decode path.
+        slots: None = one aligned batch of all rows; a number = Engine.generate_stream on that many cache slots (rows that have
+        stopped hand their slot to the next embedding; the draws of a seed differ from the aligned path's)."""
         self._sync_tokens(tokenizer)
         assert fill_in_from in ("[SMILES]", "[GRAPH]")
         if noise_scale > 0:
             h_clip = h_clip + noise_scale * torch.randn_like(h_clip)
         h_token = self.special_tokens_from_clip(h_clip)
         prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
-        generation = self.engine.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp,
-                                                               k=k, pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
-                                                               inj_payload=h_token, generator=generator)
+        if slots is None:
+            generation = self.engine.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp,
+                                                                   k=k, pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
+                                                                   inj_payload=h_token, generator=generator)
+        else:
+            generation = self.engine.generate_stream(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
+                                                     pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token, inj_payload=h_token,
+                                                     slots=int(slots), generator=generator)
         if hasattr(tokenizer, "decode"):
             smiles_list = [tokenizer.decode(t, special=keep_special) for t in generation]
         else:
@@ -339,11 +346,11 @@ class e3gnn_smiles_clip_e2e(nn.Module):
 
     @torch.no_grad()
     def points_to_2d_batch(self, atom_batch, coords_batch, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
-                           do_suffix: bool = False, inv_temp: float = 2, k=100, keep_special=False, generator=None):
-        """clip_e2e.py:590-632: encode_points, then the hclip_to_2d_batch flow (noise added out of place)."""
+                           do_suffix: bool = False, inv_temp: float = 2, k=100, keep_special=False, generator=None, slots=None):
+        """clip_e2e.py:590-632: encode_points, then the hclip_to_2d_batch flow (noise added out of place; slots as there)."""
         h_clip = self.encode_points(atom_batch, coords_batch)
         return self.hclip_to_2d_batch(h_clip, tokenizer, fill_in_from=fill_in_from, noise_scale=noise_scale, inv_temp=inv_temp, k=k,
-                                      do_suffix=do_suffix, keep_special=keep_special, generator=generator)
+                                      do_suffix=do_suffix, keep_special=keep_special, generator=generator, slots=slots)
 
     def _to_2d_one(self, h_clip, tokenizer, fill_in_from, noise_scale, suffix, inv_temp, k, generator):
         """hclip_to_2d / points_to_2d: the special token of h_clip injected as the reference does it, h_token[0] -- the first row of a

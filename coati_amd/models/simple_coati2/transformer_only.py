@@ -124,9 +124,10 @@ class COATI_Smiles_Inference(nn.Module):
     @torch.no_grad()
     def hcoati_to_2d_batch(self, h_coati: torch.Tensor, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
                            inv_temp: float = 2, k: int = 100, do_suffix=False, keep_special: bool = False, return_tokens: bool = False,
-                           generator=None):
+                           generator=None, slots=None):
         """transformer_only.py:154-200: decode [B, E] embeddings through coati_to_token at the [UNK] slot of
-        [CLIP][UNK]<fill_in_from> (+ [SUFFIX][MIDDLE]); top-k sampling on the KV-cached decode path.  Noise is added out of place."""
+        [CLIP][UNK]<fill_in_from> (+ [SUFFIX][MIDDLE]); top-k sampling on the KV-cached decode path.  Noise is added out of place.
+        slots: None = one aligned batch of all rows; a number = Engine.generate_stream on that many cache slots."""
         assert k > 1
         self._sync_tokens(tokenizer)
         h = h_coati.to(self.device, torch.float32)
@@ -136,9 +137,14 @@ class COATI_Smiles_Inference(nn.Module):
         prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
         assert h_token.dim() == 2
         assert h_token.shape[-1] == self.xformer.n_embd
-        generation = self.xformer.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
-                                                                pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
-                                                                inj_payload=h_token, generator=generator)
+        if slots is None:
+            generation = self.xformer.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
+                                                                    pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
+                                                                    inj_payload=h_token, generator=generator)
+        else:
+            generation = self.engine.generate_stream(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
+                                                     pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token, inj_payload=h_token,
+                                                     slots=int(slots), generator=generator)
         smiles_list = [tokenizer.decode(t, special=keep_special) for t in generation]
         if return_tokens:
             return smiles_list, generation

@@ -232,6 +232,19 @@ int coati_topk_sample(const float* logits, int64_t ldl, int B, int V, int k, flo
 int coati_topk_sample_prompt(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, const int64_t* prompt,
                              int64_t ldp, const int32_t* plen, int pos, int64_t* tokens_out, int32_t* stopped, int stop_token, int pad_token,
                              void* stream);
+/* ragged sessions: every row at its own position.  coati_attn_decode_rows is coati_attn_decode_hs with pos[B] (int32, device): the
+   wave of (b, head) appends at pos[b] and attends to 0 .. pos[b]; pos[b] outside 0 .. Tmax - 1 marks an idle slot, whose cache records
+   and y row are left untouched.
+   coati_topk_sample_rows: one workgroup per slot b, which serves request r = req ? req[b] : b and whose cache holds n = pos[b] + 1
+   tokens (pos[b] < 0: idle, nothing happens).  n < plen[r] emits prompt[r * ldp + n] without a draw, any other row samples exactly as
+   coati_topk_sample with the uniform u[b] (ldu == 0) or u[r * ldu + n].  The token goes to out[r * ldo + n] and to tok_next[b];
+   pos[b] becomes n, or -1 with done[b] = n + 1 (the row's length) when the token is stop_token or n is the last column
+   (min(Tmax, ldo) - 1).  plen / prompt / req / u may be null. */
+int coati_attn_decode_rows(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int head_size, int Tmax, const int32_t* pos,
+                           void* stream);
+int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
+                           const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
+                           int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream);
 
 /* E(3)-GNN pieces (e3gnn_clip.py:108-137, e_gcl_sparse.py) -- see csrc/gnn.hip for the dense-edge formulation */
 int coati_gnn_embed(const int64_t* atoms, const int32_t* lut_ix, const int32_t* lut_iy, const float* W,
@@ -482,6 +495,18 @@ int coati_engine_decode_pos(coati_engine* e);
    engines: the decode step's products run on the bf16 shadows, the pass would run MXFP8 ones. */
 int coati_engine_decode_prefill(coati_engine* e, void* workspace, int64_t ws_bytes, const int64_t* tokens, int m,
                                 const float* injection, float* logits, int64_t ldl, void* stream);
+/* ragged sessions (per-row positions; not captured into graphs).  decode_step_rows: row b appends tokens[b] at pos[b] and attends
+   to 0 .. pos[b] (pos: int32 [B], device, the caller's; the session's own position is neither used nor moved); pos[b] < 0 is an
+   idle slot (cache untouched, logits row meaningless), and a slot may be set back to position 0 at any step.  injection as in
+   decode_step; inj_len (optional, int32 [B], device): row b reads the injection only while pos[b] < inj_len[b].
+   decode_prefill_rows: positions 0 .. plen[b] - 1 of every row of a fresh session in ONE pass over packed rows: prompt [B, ldp]
+   (ldp <= Tmax), plen int32 [B] on the device with every entry in 1 .. ldp, rows = their sum (host).  logits (optional) are those of
+   position plen[b] - 1; continue with decode_step_rows at pos[b] = plen[b].  workspace: coati_engine_workspace_bytes(e, B, 1, ldp, 1, B).
+   Refused behind any step and on fp8 engines, as decode_prefill. */
+int coati_engine_decode_step_rows(coati_engine* e, const int64_t* tokens, const int32_t* pos, const float* injection, const int32_t* inj_len,
+                                  float* logits, int64_t ldl, void* stream);
+int coati_engine_decode_prefill_rows(coati_engine* e, void* workspace, int64_t ws_bytes, const int64_t* prompt, int64_t ldp,
+                                     const int32_t* plen, int64_t rows, const float* injection, float* logits, int64_t ldl, void* stream);
 /* the same step captured into HIP graphs (one hipGraphLaunch instead of ~115 kernel launches; pays off at small batch).
    graph_build: after decode_begin, on an explicit stream.  graph_step: tokens[B] / injection[B, C] (device) are copied
    into the session's fixed input buffers; *logits_out points at the session's logits [B, n_tok] (row stride *ldl_out),
