@@ -21,6 +21,9 @@
 #include "../../include/coati_hip.h"
 #include "kernels.h"
 
+// a HIP runtime call inside a function that returns a COATI_* code (beside COATI_TRY / COATI_CHECK_* of common.h)
+#define HIPCHK(x) do { hipError_t _h = (x); if (_h != hipSuccess) { coati_set_error("%s: %s", #x, hipGetErrorString(_h)); return COATI_EHIP; } } while (0)
+
 static thread_local char g_err[512] = "";
 void coati_set_error(const char* fmt, ...) {
   va_list ap;
@@ -1493,6 +1496,84 @@ int coati2_head_fwd(coati_engine* e, const coati_engine::Coati2Head& h, const fl
   return COATI_OK;
 }
 
+// ---- what the C-ABI entries share: an entry is its argument checks, begin_call, and a short list of the stages below ----------
+// Host side of every entry that runs on the step workspace: carve it for (B, T1, T2, A) and refuse one that is too small (`entry`: the
+// caller's name in the message), hand the InfoNCE region whatever the workspace holds beyond the carve, reset the per-step state.
+// scal: the entry's loss / error scalars (recorded in the engine), nullptr when it has none.  Nothing is enqueued.
+int begin_call(coati_engine* e, const char* entry, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, int A, float* scal) {
+  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
+  const size_t need = carve(e, ar, B, T1, T2, A, B);
+  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "%s: workspace too small (%zu > %lld)", entry, need, (long long)workspace_bytes);
+  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
+  e->B = B; e->T1 = T1; e->T2 = T2; e->A = A;
+  if (scal) e->scal = scal;
+  e->have_fwd = false;
+  e->decoder_pending = false;
+  e->have_ws = true;
+  return COATI_OK;
+}
+// clears the step's error state: the caller's scalars (scal, where the entry has them) and the device-side error word
+int clear_errors(coati_engine* e, float* scal, hipStream_t s) {
+  if (scal) HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
+  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  return COATI_OK;
+}
+// publishes the error word where the host reads it (scal[6], coati_amd/engine.py SCAL_ERR)
+int publish_errors(coati_engine* e, float* scal, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
+  return COATI_OK;
+}
+
+// pass p on packed rows -- the rows' real prefixes only (embed.hip launch_seq_pack) --, with the packed copy of `targets` where given.
+// rows comes from the caller (the batch assembler knows it on the host: no device -> host sync here), the device checks it
+int pack_pass(coati_engine* e, XPass& p, const long long* targets, int64_t rows, hipStream_t s) {
+  COATI_TRY(launch_seq_pack(p.idx, targets, e->cfg.pad_token, p.B, p.T, (int)rows, p.off, p.row_src, p.row_t, targets ? p.ypk : nullptr, e->err_flag, s, p.ord));
+  p.packed = true;
+  p.M = (int)rows;
+  return COATI_OK;
+}
+
+// the [STOP] rows behind the encoder pass -> smiles_to_clip (COATI2: smiles_to_coati) into out [B, E]
+int stop_rows_head_fwd(coati_engine* e, float* out, hipStream_t s) {
+  const XPass& p = e->p1;
+  const int C = e->cfg.n_hidden_xformer;
+  if (p.tail) HIPCHK(hipMemcpyAsync(e->hstop, p.t_xf, (size_t)p.B * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  else COATI_TRY(launch_gather_rows(p.xf32, e->stop_pos, e->hstop, p.B, p.T, C, s, p.packed ? p.off : nullptr));
+  if (e->enc_to_coati > 0) return coati2_head_fwd(e, e->c2s, e->hstop, out, p.B, s);   // COATI2 SwiGLU smiles_to_coati
+  return smiles_head_fwd(e, out, s);
+}
+// encode_tokens (clip_e2e.py:448-452): the [STOP] positions, the encoder pass over e->p1.idx, the head
+int token_tower_fwd(coati_engine* e, float* out, hipStream_t s) {
+  COATI_TRY(launch_find_stop(e->p1.idx, e->cfg.stop_token, e->stop_pos, e->err_flag, e->p1.B, e->p1.T, s));
+  COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
+  return stop_rows_head_fwd(e, out, s);
+}
+
+// point_clip_to_special_tokens (clip_e2e.py:432-437) of the embeddings h [B, E]: SiLU (into act) -> Linear (into tok) as one more
+// problem of the batch `sb`, which the caller launches; nn.Identity (token_mlp = False): h itself.  *out: where the token is read
+int special_token_add(coati_engine* e, SgemmBatch& sb, const float* h, float* act, float* tok, const float** out, hipStream_t s) {
+  const int E = e->cfg.n_embd_common, B = e->B;
+  *out = h;
+  if (!e->cfg.token_mlp) return COATI_OK;
+  COATI_TRY(launch_silu_fwd(h, act, (long long)B * E, s));
+  COATI_TRY(sgemm_batch_add(sb, act, E, 1, e->P + e->tokw, 1, E, tok, E, B, E, E, e->P + e->tokb, 1.f, 0));
+  *out = tok;
+  return COATI_OK;
+}
+
+// ln_f on the decode session's B rows of x (row stride ldx) and the f32 lm_head: logits [B, ldl]
+int last_row_logits(coati_engine* e, const float* x, long long ldx, float* logits, int64_t ldl, hipStream_t s) {
+  auto& d = e->dec;
+  const int C = e->cfg.n_hidden_xformer;
+  COATI_TRY(launch_layernorm_fwd(x, ldx, e->P + e->lnfw, e->P + e->lnfb, d.af, C, nullptr, 0, d.mean, d.rstd, d.B, C, s));
+  return gemm(e, SITE_NONE, d.af, 0, C, e->S + e->lmhead, C, d.B, e->cfg.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s);
+}
+// the f32 lm_head on every row of the (padded) decoder pass: logits [B * T2, ldl]
+int pass_logits(coati_engine* e, int site, float* logits, int64_t ldl, hipStream_t s) {
+  const int C = e->cfg.n_hidden_xformer;
+  return gemm(e, site, e->p2.af, 0, C, e->S + e->lmhead, C, e->B * e->T2, e->cfg.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s);
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1631,8 +1712,6 @@ static int refresh_fp8_weights(coati_engine* e, hipStream_t s) {
 static int refresh_shadows_impl(coati_engine* e, void* stream, bool natural_done) {
   COATI_CHECK_ARG(e && e->P && e->S, "refresh_shadows: engine not bound");
   hipStream_t s = (hipStream_t)stream;
-  const coati_config& c = e->cfg;
-  const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn;
   ProfScope ps(e, SITE_OPTIM, 0, s);
   if (!natural_done) COATI_TRY(launch_cast_bf16(e->P, e->S, e->n_params, s));
   if (e->d_jobs != nullptr) {
@@ -1686,10 +1765,7 @@ static int forward_decoder_impl(coati_engine* e, hipStream_t s) {
     COATI_TRY(lmhead_ce_partial(e, s, &tiles_v));
     COATI_TRY(launch_ce_finish(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next, e->ce_lse, scal, e->p2.M, C, c.n_tok, s));
   }
-  if (hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-    coati_set_error("engine_forward: error-word copy failed");
-    return COATI_EHIP;
-  }
+  COATI_TRY(publish_errors(e, scal, s));
   e->have_fwd = true;
   return COATI_OK;
 }
@@ -1710,39 +1786,20 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
   COATI_CHECK_SHAPE(rows1 >= 0 && rows2 >= 0 && rows1 <= (int64_t)B * T1 && rows2 <= (int64_t)B * T2 && (rows1 > 0) == (rows2 > 0),
                     "engine_forward: packed row counts %lld / %lld do not fit %d x %d / %d x %d", (long long)rows1, (long long)rows2, B, T1, B, T2);
   hipStream_t s = (hipStream_t)stream;
-  const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn, E = c.n_embd_common;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
-  const size_t need = carve(e, ar, B, T1, T2, A, B);
-  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_forward: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
-  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = T1; e->T2 = T2; e->A = A;
+  const int E = c.n_embd_common;
+  COATI_TRY(begin_call(e, "engine_forward", workspace, workspace_bytes, B, T1, T2, A, scal));
   e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
   e->p2.idx = reinterpret_cast<const long long*>(tokens);
   e->y_next = reinterpret_cast<const long long*>(y_next);
   e->atoms = reinterpret_cast<const long long*>(atoms);
   e->use_point = use_point;
-  e->scal = scal;
-  e->have_fwd = false;
-  e->decoder_pending = false;
-
-#define HIPCHK(x) do { hipError_t _h = (x); if (_h != hipSuccess) { coati_set_error("%s: %s", #x, hipGetErrorString(_h)); return COATI_EHIP; } } while (0)
-  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
-  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(clear_errors(e, scal, s));
   if (train) HIPCHK(hipMemsetAsync(e->G, 0, (size_t)e->n_params * sizeof(float), s));
-  // ---- packed rows: both transformer passes run on the rows' real prefixes only (embed.hip, launch_seq_pack); the counts
-  // come from the caller (the batch assembler knows them on the host: no device -> host sync here), the device checks them
-  if (rows1 > 0) {
-    COATI_TRY(launch_seq_pack(e->p1.idx, nullptr, c.pad_token, B, T1, (int)rows1, e->p1.off, e->p1.row_src, e->p1.row_t, nullptr, e->err_flag, s, e->p1.ord));
-    COATI_TRY(launch_seq_pack(e->p2.idx, e->y_next, c.pad_token, B, T2, (int)rows2, e->p2.off, e->p2.row_src, e->p2.row_t, e->y_next ? e->p2.ypk : nullptr, e->err_flag, s, e->p2.ord));
-    e->p1.packed = e->p2.packed = true;
-    e->p1.M = (int)rows1;
-    e->p2.M = (int)rows2;
+  if (rows1 > 0) {   // both transformer passes on packed rows
+    COATI_TRY(pack_pass(e, e->p1, nullptr, rows1, s));
+    COATI_TRY(pack_pass(e, e->p2, e->y_next, rows2, s));
   }
-  {
-    // ones[B] for bias column sums
-    std::vector<float> dummy;  // (filled on device below)
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)e->ones, 0x3f800000, B, s));
-  }
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)e->ones, 0x3f800000, B, s));   // ones[B] for bias column sums
 
   // ---- point encoder (clip_e2e.py:454-461): on the side stream, concurrent with the encoder pass ----
   const bool ovl = e->overlap && (e->prof_mask == 0 || e->prof_keep_overlap) && c.use_point_encoder;
@@ -1767,26 +1824,17 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
   if (ovl) COATI_TRY(join_side(e, s));
   COATI_TRY(point_head_fwd(e, e->h_e3gnn, s));
   // ---- smiles_to_clip ----
-  if (e->p1.tail) HIPCHK(hipMemcpyAsync(e->hstop, e->p1.t_xf, (size_t)B * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s, e->p1.packed ? e->p1.off : nullptr));
-  COATI_TRY(smiles_head_fwd(e, e->h_smiles, s));
-  // ---- special token (clip_e2e.py:800-808): SiLU -> Linear of either embedding, or the embeddings themselves (token_mlp = False:
-  // nn.Identity, clip_e2e.py:436-437) ----
-  const float *ptok = e->h_e3gnn, *stok = e->h_smiles;
-  if (c.token_mlp) {
-    COATI_TRY(launch_silu_fwd(e->h_e3gnn, e->sa, (long long)B * E, s));
-    COATI_TRY(launch_silu_fwd(e->h_smiles, e->sb, (long long)B * E, s));
-    SgemmBatch sb;
-    COATI_TRY(sgemm_batch_add(sb, e->sa, E, 1, e->P + e->tokw, 1, E, e->ptok, E, B, E, E, e->P + e->tokb, 1.f, 0));
-    COATI_TRY(sgemm_batch_add(sb, e->sb, E, 1, e->P + e->tokw, 1, E, e->stok, E, B, E, E, e->P + e->tokb, 1.f, 0));
-    COATI_TRY(launch_sgemm_batch(sb, s));
-    ptok = e->ptok; stok = e->stok;
-  }
+  COATI_TRY(stop_rows_head_fwd(e, e->h_smiles, s));
+  // ---- special token (clip_e2e.py:800-808) of either embedding: one batched launch ----
+  const float *ptok = nullptr, *stok = nullptr;
+  SgemmBatch sb;
+  COATI_TRY(special_token_add(e, sb, e->h_e3gnn, e->sa, e->ptok, &ptok, s));
+  COATI_TRY(special_token_add(e, sb, e->h_smiles, e->sb, e->stok, &stok, s));
+  COATI_TRY(launch_sgemm_batch(sb, s));
   COATI_TRY(launch_select_rows(use_point, ptok, stok, e->cliptok, B, E, s));
   if (bad_rows) COATI_TRY(launch_bad_rows(e->p2.idx, bad_rows, B, T2, s));
   if (h_e3gnn) HIPCHK(hipMemcpyAsync(h_e3gnn, e->h_e3gnn, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (h_smiles) HIPCHK(hipMemcpyAsync(h_smiles, e->h_smiles, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
-  e->have_ws = true;
   if (stop_after_heads) {
     // the embeddings are out: the caller may run the contrastive head (+ its collectives) on another stream while
     // coati_engine_forward_decoder enqueues the decoder pass on this one
@@ -1818,33 +1866,21 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
   if (!do_pts) A = 1;
   COATI_CHECK_SHAPE(B > 0 && T1 > 0 && A > 0 && T1 <= c.n_seq, "engine_encode: unsupported shape B=%d T1=%d A=%d", B, T1, A);
   hipStream_t s = (hipStream_t)stream;
-  const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn, E = c.n_embd_common;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
-  const size_t need = carve(e, ar, B, T1, 1, A, B);
-  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_encode: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
-  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = T1; e->T2 = 1; e->A = A;
-  e->have_fwd = false;
-  e->have_ws = true;
-  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
-  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(begin_call(e, "engine_encode", workspace, workspace_bytes, B, T1, 1, A, scal));
+  COATI_TRY(clear_errors(e, scal, s));
   if (do_pts) {
     e->atoms = reinterpret_cast<const long long*>(atoms);
     if (c.use_point_encoder) {
       COATI_TRY(gnn_fwd(e, e->atoms, coords, s));
       COATI_TRY(point_head_fwd(e, h_e3gnn, s));
     } else {
-      HIPCHK(hipMemsetAsync(h_e3gnn, 0, (size_t)B * E * sizeof(float), s));   // clip_e2e.py:462-463
+      HIPCHK(hipMemsetAsync(h_e3gnn, 0, (size_t)B * c.n_embd_common * sizeof(float), s));   // clip_e2e.py:462-463
     }
   }
   if (do_tok) {
     e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
-    COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
-    COATI_TRY(launch_find_stop(e->p1.idx, c.stop_token, e->stop_pos, e->err_flag, B, T1, s));
-    COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s));
-    if (e->enc_to_coati > 0) COATI_TRY(coati2_head_fwd(e, e->c2s, e->hstop, h_smiles, B, s));   // COATI2 SwiGLU smiles_to_coati
-    else COATI_TRY(smiles_head_fwd(e, h_smiles, s));
-    HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
+    COATI_TRY(token_tower_fwd(e, h_smiles, s));
+    COATI_TRY(publish_errors(e, scal, s));
   }
   return COATI_OK;
 }
@@ -1858,13 +1894,7 @@ int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_
   const size_t bytes = (size_t)B * E * sizeof(float);
   const char *ph = reinterpret_cast<const char*>(h), *pt = reinterpret_cast<const char*>(h_token);
   COATI_CHECK_ARG(ph + bytes <= pt || pt + bytes <= ph, "engine_token_head: h_token must not overlap h");
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
-  const size_t need = carve(e, ar, B, 1, 1, 1, B);
-  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_token_head: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
-  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = 1; e->T2 = 1; e->A = 1;
-  e->have_fwd = false;
-  e->have_ws = true;
+  COATI_TRY(begin_call(e, "engine_token_head", workspace, workspace_bytes, B, 1, 1, 1, nullptr));
   return coati2_head_fwd(e, e->c2t, h, h_token, B, (hipStream_t)stream);
 }
 
@@ -1885,57 +1915,32 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
   COATI_CHECK_SHAPE(rows1 >= 0 && rows2 >= 0 && rows1 <= (int64_t)B * T1 && rows2 <= (int64_t)B * T2 && (!raw_tokens || (rows1 > 0) == (rows2 > 0)),
                     "engine_score: packed row counts %lld / %lld do not fit %d x %d / %d x %d", (long long)rows1, (long long)rows2, B, T1, B, T2);
   hipStream_t s = (hipStream_t)stream;
-  const int C = c.n_hidden_xformer, E = c.n_embd_common;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
-  const size_t need = carve(e, ar, B, T1, T2, 1, B);
-  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_score: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
-  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = T1; e->T2 = T2; e->A = 1;
+  const int C = c.n_hidden_xformer;
+  COATI_TRY(begin_call(e, "engine_score", workspace, workspace_bytes, B, T1, T2, 1, scal));
   e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
   e->p2.idx = reinterpret_cast<const long long*>(tokens);
   e->y_next = reinterpret_cast<const long long*>(y_next);
-  e->scal = scal;
-  e->have_fwd = false;
-  e->decoder_pending = false;
-  e->have_ws = true;
-  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
-  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
-  if (rows1 > 0) {
-    COATI_TRY(launch_seq_pack(e->p1.idx, nullptr, c.pad_token, B, T1, (int)rows1, e->p1.off, e->p1.row_src, e->p1.row_t, nullptr, e->err_flag, s, e->p1.ord));
-    e->p1.packed = true;
-    e->p1.M = (int)rows1;
-  }
-  if (rows2 > 0) {
-    COATI_TRY(launch_seq_pack(e->p2.idx, e->y_next, c.pad_token, B, T2, (int)rows2, e->p2.off, e->p2.row_src, e->p2.row_t, e->p2.ypk, e->err_flag, s, e->p2.ord));
-    e->p2.packed = true;
-    e->p2.M = (int)rows2;
-  }
+  COATI_TRY(clear_errors(e, scal, s));
+  if (rows1 > 0) COATI_TRY(pack_pass(e, e->p1, nullptr, rows1, s));
+  if (rows2 > 0) COATI_TRY(pack_pass(e, e->p2, e->y_next, rows2, s));
   // ---- the embedding: encode_tokens (clip_e2e.py:448-452) or the caller's ----
   const float* hclip = h_clip;
   if (raw_tokens) {
-    COATI_TRY(launch_find_stop(e->p1.idx, c.stop_token, e->stop_pos, e->err_flag, B, T1, s));
-    COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
-    COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s, e->p1.packed ? e->p1.off : nullptr));
-    COATI_TRY(smiles_head_fwd(e, e->h_smiles, s));
+    COATI_TRY(token_tower_fwd(e, e->h_smiles, s));
     hclip = e->h_smiles;
   }
-  // ---- special token: point_clip_to_special_tokens = SiLU -> Linear, or nn.Identity (clip_e2e.py:432-437) ----
-  const float* inj = hclip;
-  if (c.token_mlp) {
-    COATI_TRY(launch_silu_fwd(hclip, e->sb, (long long)B * E, s));
-    SgemmBatch sb;
-    COATI_TRY(sgemm_batch_add(sb, e->sb, E, 1, e->P + e->tokw, 1, E, e->stok, E, B, E, E, e->P + e->tokb, 1.f, 0));
-    COATI_TRY(launch_sgemm_batch(sb, s));
-    inj = e->stok;
-  }
+  // ---- special token: point_clip_to_special_tokens (clip_e2e.py:432-437) ----
+  const float* inj = nullptr;
+  SgemmBatch sb;
+  COATI_TRY(special_token_add(e, sb, hclip, e->sb, e->stok, &inj, s));
+  COATI_TRY(launch_sgemm_batch(sb, s));
   // ---- decoder pass with the injection, lm_head partials, per-sequence sums (forward_with_replacement + cross_entropy) ----
   COATI_TRY(xformer_fwd(e, e->p2, inj, s));
   int tiles_v = 0;
   COATI_TRY(lmhead_ce_partial(e, s, &tiles_v));
   COATI_TRY(launch_ce_seq(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next,
                           e->p2.packed ? e->p2.off : nullptr, nll, B, T2, C, c.n_tok, s));
-  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
-  return COATI_OK;
+  return publish_errors(e, scal, s);
 }
 
 // encode_tokens on packed rows: the encoder pass over the rows' real prefixes only (the encoder half of coati_engine_score), then the
@@ -1948,29 +1953,12 @@ int coati_engine_encode_packed(coati_engine* e, void* workspace, int64_t workspa
   COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T1 <= c.n_seq, "engine_encode_packed: unsupported shape B=%d T1=%d (n_seq=%d)", B, T1, c.n_seq);
   COATI_CHECK_SHAPE(rows1 > 0 && rows1 <= (int64_t)B * T1, "engine_encode_packed: packed row count %lld does not fit %d x %d", (long long)rows1, B, T1);
   hipStream_t s = (hipStream_t)stream;
-  const int C = c.n_hidden_xformer;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
-  const size_t need = carve(e, ar, B, T1, 1, 1, B);
-  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_encode_packed: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
-  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = T1; e->T2 = 1; e->A = 1;
+  COATI_TRY(begin_call(e, "engine_encode_packed", workspace, workspace_bytes, B, T1, 1, 1, scal));
   e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
-  e->scal = scal;
-  e->have_fwd = false;
-  e->decoder_pending = false;
-  e->have_ws = true;
-  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
-  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
-  COATI_TRY(launch_seq_pack(e->p1.idx, nullptr, c.pad_token, B, T1, (int)rows1, e->p1.off, e->p1.row_src, e->p1.row_t, nullptr, e->err_flag, s, e->p1.ord));
-  e->p1.packed = true;
-  e->p1.M = (int)rows1;
-  COATI_TRY(launch_find_stop(e->p1.idx, c.stop_token, e->stop_pos, e->err_flag, B, T1, s));
-  COATI_TRY(xformer_fwd(e, e->p1, nullptr, s));
-  COATI_TRY(launch_gather_rows(e->p1.xf32, e->stop_pos, e->hstop, B, T1, C, s, e->p1.off));
-  if (e->enc_to_coati > 0) COATI_TRY(coati2_head_fwd(e, e->c2s, e->hstop, h_smiles, B, s));   // COATI2 SwiGLU smiles_to_coati
-  else COATI_TRY(smiles_head_fwd(e, h_smiles, s));
-  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
-  return COATI_OK;
+  COATI_TRY(clear_errors(e, scal, s));
+  COATI_TRY(pack_pass(e, e->p1, nullptr, rows1, s));
+  COATI_TRY(token_tower_fwd(e, h_smiles, s));
+  return publish_errors(e, scal, s);
 }
 
 // RotarySmilesTransformer.forward / forward_with_replacement (smiles_xformer.py:375-382, 426-454): the decoder pass over the padded
@@ -1983,33 +1971,19 @@ int coati_engine_decoder_logits(coati_engine* e, void* workspace, int64_t worksp
   COATI_CHECK_SHAPE(B > 0 && T > 0 && T <= c.n_seq && ldl >= c.n_tok, "engine_decoder_logits: unsupported shape B=%d T=%d ldl=%lld (n_seq=%d, n_tok=%d)",
                     B, T, (long long)ldl, c.n_seq, c.n_tok);
   hipStream_t s = (hipStream_t)stream;
-  const int C = c.n_hidden_xformer;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)workspace_bytes, false};
-  const size_t need = carve(e, ar, B, 1, T, 1, B);
-  COATI_CHECK_ARG((int64_t)need <= workspace_bytes, "engine_decoder_logits: workspace too small (%zu > %lld)", need, (long long)workspace_bytes);
-  if (e->nce) e->nce_cap = ((size_t)workspace_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = 1; e->T2 = T; e->A = 1;
+  COATI_TRY(begin_call(e, "engine_decoder_logits", workspace, workspace_bytes, B, 1, T, 1, scal));
   e->p2.idx = reinterpret_cast<const long long*>(tokens);
-  e->scal = scal;
-  e->have_fwd = false;
-  e->decoder_pending = false;
-  e->have_ws = true;
-  HIPCHK(hipMemsetAsync(scal, 0, 16 * sizeof(float), s));
-  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(clear_errors(e, scal, s));
   COATI_TRY(xformer_fwd(e, e->p2, injection, s));
-  COATI_TRY(gemm(e, SITE_NONE, e->p2.af, 0, C, e->S + e->lmhead, C, B * T, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
-  HIPCHK(hipMemcpyAsync(scal + 6, e->err_flag, sizeof(int), hipMemcpyDeviceToDevice, s));
-  return COATI_OK;
+  COATI_TRY(pass_logits(e, SITE_NONE, logits, ldl, s));
+  return publish_errors(e, scal, s);
 }
 
 int coati_engine_logits(coati_engine* e, float* logits, int64_t ldl, void* stream) {
   COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_logits: a COATI2 engine is inference-only (no training forward)");
   COATI_CHECK_ARG(e->have_fwd && logits, "engine_logits: no forward to read");
-  const coati_config& c = e->cfg;
-  hipStream_t s = (hipStream_t)stream;
   COATI_CHECK_ARG(!e->p2.packed, "engine_logits: the last forward ran on packed rows (logits of padded positions do not exist): run it with rows1 = rows2 = 0");
-  return gemm(e, SITE_LMHEAD_FWD, e->p2.af, 0, c.n_hidden_xformer, e->S + e->lmhead, c.n_hidden_xformer, e->B * e->T2, c.n_tok,
-              c.n_hidden_xformer, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s);
+  return pass_logits(e, SITE_LMHEAD_FWD, logits, ldl, (hipStream_t)stream);
 }
 
 int coati_engine_infonce(coati_engine* e, const float* S_loc, const float* C_loc, const float* S_all,
@@ -2382,10 +2356,7 @@ int decode_enqueue(coati_engine* e, const long long* tokens, const float* inject
     COATI_TRY(gemm(e, SITE_NONE, d.a, 0, C, e->S + w.fc1w, C, B, 4 * C, C, d.g, 4 * C, e->P + w.fc1b, EPI_GELU, nullptr, d.hpre, 4 * C, s));
     COATI_TRY(gemm(e, SITE_NONE, d.g, 0, 4 * C, e->S + w.fc2w, 4 * C, B, C, 4 * C, x, C, e->P + w.fc2b, EPI_RES_F32, xm, nullptr, C, s));
   }
-  if (logits) {
-    COATI_TRY(launch_layernorm_fwd(x, C, e->P + e->lnfw, e->P + e->lnfb, d.af, C, nullptr, 0, d.mean, d.rstd, B, C, s));
-    COATI_TRY(gemm(e, SITE_NONE, d.af, 0, C, e->S + e->lmhead, C, B, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
-  }
+  if (logits) COATI_TRY(last_row_logits(e, x, C, logits, ldl, s));
   if (graph_mode) COATI_TRY(launch_add_int(d.pos_dev, 1, 0, s));
   return COATI_OK;
 }
@@ -2430,24 +2401,13 @@ int coati_engine_decode_prefill(coati_engine* e, void* workspace, int64_t ws_byt
   COATI_CHECK_ARG(!logits || ldl >= c.n_tok, "decode_prefill: ldl too small");
   hipStream_t s = (hipStream_t)stream;
   const int B = d.B, C = c.n_hidden_xformer, L = c.n_layer_xformer, hs = C / c.n_head;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)ws_bytes, false};
-  const size_t need = carve(e, ar, B, 1, m, 1, B);
-  COATI_CHECK_ARG((int64_t)need <= ws_bytes, "decode_prefill: workspace too small (%zu > %lld)", need, (long long)ws_bytes);
-  if (e->nce) e->nce_cap = ((size_t)ws_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = 1; e->T2 = m; e->A = 1;
+  COATI_TRY(begin_call(e, "decode_prefill", workspace, ws_bytes, B, 1, m, 1, nullptr));
   e->p1.idx = nullptr;
   e->p2.idx = reinterpret_cast<const long long*>(tokens);
-  e->have_fwd = false;
-  e->decoder_pending = false;
-  e->have_ws = true;
   COATI_TRY(xformer_fwd(e, e->p2, injection, s));
   for (int l = 0; l < L; ++l)
     COATI_TRY(launch_kv_cache_fill(e->p2.qkv[l], d.cache + (size_t)l * B * C * d.Tmax * 2, B, m, c.n_head, hs, d.Tmax, s));
-  if (logits) {
-    COATI_TRY(launch_layernorm_fwd(e->p2.x[L] + (size_t)(m - 1) * C, (long long)m * C, e->P + e->lnfw, e->P + e->lnfb, d.af, C, nullptr, 0,
-                                   d.mean, d.rstd, B, C, s));
-    COATI_TRY(gemm(e, SITE_NONE, d.af, 0, C, e->S + e->lmhead, C, B, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
-  }
+  if (logits) COATI_TRY(last_row_logits(e, e->p2.x[L] + (size_t)(m - 1) * C, (long long)m * C, logits, ldl, s));
   COATI_TRY(launch_add_int(d.pos_dev, m, 1, s));   // a captured decode graph continues from position m
   d.pos = m;
   return COATI_OK;
@@ -2489,17 +2449,10 @@ int coati_engine_decode_prefill_rows(coati_engine* e, void* workspace, int64_t w
   COATI_CHECK_ARG(!logits || ldl >= c.n_tok, "decode_prefill_rows: ldl too small");
   hipStream_t s = (hipStream_t)stream;
   const int T = (int)ldp;
-  Arena ar{reinterpret_cast<char*>(workspace), 0, (size_t)ws_bytes, false};
-  const size_t need = carve(e, ar, B, 1, T, 1, B);
-  COATI_CHECK_ARG((int64_t)need <= ws_bytes, "decode_prefill_rows: workspace too small (%zu > %lld)", need, (long long)ws_bytes);
-  if (e->nce) e->nce_cap = ((size_t)ws_bytes - (size_t)(reinterpret_cast<char*>(e->nce) - reinterpret_cast<char*>(workspace))) / sizeof(float);
-  e->B = B; e->T1 = 1; e->T2 = T; e->A = 1;
+  COATI_TRY(begin_call(e, "decode_prefill_rows", workspace, ws_bytes, B, 1, T, 1, nullptr));
   e->p1.idx = nullptr;
   e->p2.idx = reinterpret_cast<const long long*>(prompt);
-  e->have_fwd = false;
-  e->decoder_pending = false;
-  e->have_ws = true;
-  HIPCHK(hipMemsetAsync(e->err_flag, 0, 4 * sizeof(int), s));
+  COATI_TRY(clear_errors(e, nullptr, s));
   COATI_TRY(launch_seq_pack_len(plen, B, T, (int)rows, e->p2.off, e->p2.row_src, e->p2.row_t, e->err_flag, s, e->p2.ord));
   e->p2.packed = true;
   e->p2.M = (int)rows;
@@ -2509,8 +2462,7 @@ int coati_engine_decode_prefill_rows(coati_engine* e, void* workspace, int64_t w
     COATI_TRY(launch_kv_cache_fill_rows(e->p2.qkv[l], d.cache + (size_t)l * B * C * d.Tmax * 2, e->p2.row_src, (int)rows, B, T, c.n_head, hs, d.Tmax, s));
   if (logits) {
     COATI_TRY(launch_gather_last_rows(e->p2.x[L], e->p2.off, d.x, B, C, (int)rows, s));
-    COATI_TRY(launch_layernorm_fwd(d.x, C, e->P + e->lnfw, e->P + e->lnfb, d.af, C, nullptr, 0, d.mean, d.rstd, B, C, s));
-    COATI_TRY(gemm(e, SITE_NONE, d.af, 0, C, e->S + e->lmhead, C, B, c.n_tok, C, logits, ldl, nullptr, EPI_F32, nullptr, nullptr, 0, s));
+    COATI_TRY(last_row_logits(e, d.x, C, logits, ldl, s));
   }
   d.ragged = true;
   return COATI_OK;

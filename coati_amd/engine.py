@@ -164,6 +164,33 @@ class Engine:
         _lib.check(self.l.coati_engine_refresh_shadows(self.h, stream()), "refresh_shadows")
 
     # ---- step pieces ---------------------------------------------------------------------------------------
+    def _fit_workspace(self, B, T1, T2, A, Bg=None):
+        """The step workspace holds what the library carves for (B, T1, T2, A) and Bg InfoNCE columns (default B): re-allocated when
+        it is too small.  Returns the size asked for."""
+        need = int(self.l.coati_engine_workspace_bytes(self.h, B, T1, T2, A, B if Bg is None else Bg))
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None
+            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return need
+
+    def _injection(self, injection, B):
+        """an optional injection as a contiguous f32 [B, C] device tensor (or None)"""
+        if injection is None:
+            return None
+        inj = injection.to(self.device, torch.float32).contiguous()
+        assert inj.shape == (B, self.cfg.n_hidden_xformer), inj.shape
+        return inj
+
+    def _logits_rows(self, rows, want=True):
+        """(buffer [rows, ld] f32, ld, its [:, :n_tok] view): ld = n_tok rounded up to 8 floats, so that the f32 rows are 16-B aligned
+        for the GEMM epilogue's float4 stores.  want=False: (None, ld, None)."""
+        V = self.cfg.n_tok
+        ld = (V + 7) // 8 * 8
+        if not want:
+            return None, ld, None
+        buf = torch.empty(rows, ld, device=self.device, dtype=torch.float32)
+        return buf, ld, buf[:, :V]
+
     def _ensure_workspace(self, B, T1, T2, A):
         # Bg = columns of the InfoNCE logits: the global batch when torch.distributed is up
         world = 1
@@ -188,11 +215,7 @@ class Engine:
             self._cap = new
             self.growth_events = getattr(self, "growth_events", 0) + 1
         cb, c1, c2, ca = self._cap
-        need = int(self.l.coati_engine_workspace_bytes(self.h, max(B, cb), max(T1, c1), max(T2, c2), max(A, ca), max(B, cb) * world))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
-        return need
+        return self._fit_workspace(max(B, cb), max(T1, c1), max(T2, c2), max(A, ca), max(B, cb) * world)
 
     def reserve(self, B, T1, T2, A, headroom=0.9):
         """Carve every buffer for batches of up to B molecules, T1 / T2 token columns and A atoms now (coati_engine_reserve): later
@@ -227,7 +250,7 @@ class Engine:
         use_point = use_point.to(torch.uint8).contiguous()
         if y_next is not None:
             y_next = y_next.contiguous()
-        need = self._ensure_workspace(B, T1, T2, A)
+        self._ensure_workspace(B, T1, T2, A)
         E = self.cfg.n_embd_common
         h_e = torch.empty(B, E, device=self.device, dtype=torch.float32)
         h_s = torch.empty(B, E, device=self.device, dtype=torch.float32)
@@ -287,10 +310,7 @@ class Engine:
         T1 = raw_tokens.shape[1] if raw_tokens is not None else 1
         A = atoms.shape[1] if atoms is not None else 1
         E = self.cfg.n_embd_common
-        need = int(self.l.coati_engine_workspace_bytes(self.h, B, T1, 1, A, B))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        self._fit_workspace(B, T1, 1, A)
         h_s = torch.empty(B, E, device=self.device, dtype=torch.float32) if raw_tokens is not None else None
         h_e = torch.empty(B, E, device=self.device, dtype=torch.float32) if atoms is not None else None
         if coords is not None:
@@ -305,10 +325,7 @@ class Engine:
     def _encode_packed(self, raw_tokens, rows1):
         assert raw_tokens.dtype == torch.int64 and raw_tokens.is_cuda and raw_tokens.is_contiguous() and raw_tokens.dim() == 2
         B, T1 = raw_tokens.shape
-        need = int(self.l.coati_engine_workspace_bytes(self.h, B, T1, 1, 1, B))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        self._fit_workspace(B, T1, 1, 1)
         h_s = torch.empty(B, self.cfg.n_embd_common, device=self.device, dtype=torch.float32)
         self._keep = (raw_tokens,)
         _lib.check(self.l.coati_engine_encode_packed(self.h, ptr(self.workspace), self.workspace.numel(), B, T1, ptr(raw_tokens), rows1,
@@ -322,21 +339,14 @@ class Engine:
         padded row stride).  COATI1 and COATI2 engines; nothing is kept for a backward."""
         assert tokens.dtype == torch.int64 and tokens.is_cuda and tokens.is_contiguous() and tokens.dim() == 2
         B, T = tokens.shape
-        C, V = self.cfg.n_hidden_xformer, self.cfg.n_tok
-        if injection is not None:
-            injection = injection.to(self.device, torch.float32).contiguous()
-            assert injection.shape == (B, C), injection.shape
-        need = int(self.l.coati_engine_workspace_bytes(self.h, B, 1, T, 1, B))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
-        ld = (V + 7) // 8 * 8
-        out = torch.empty(B * T, ld, device=self.device, dtype=torch.float32)
+        injection = self._injection(injection, B)
+        self._fit_workspace(B, 1, T, 1)
+        out, ld, logits = self._logits_rows(B * T)
         self._keep = (tokens, injection)
         _lib.check(self.l.coati_engine_decoder_logits(self.h, ptr(self.workspace), self.workspace.numel(), B, T, ptr(tokens), ptr(injection),
                                                       ptr(out), ld, ptr(self.scal), stream()), "coati_engine_decoder_logits")
         self._shape = None
-        return out[:, :V].view(B, T, V)
+        return logits.view(B, T, self.cfg.n_tok)
 
     def token_head(self, h):
         """COATI2 coati_to_token (SwiGLUResNet(E, E), simple_coati2/transformer_only.py:19-36) on h [B, E] -> [B, E] f32; scratch from
@@ -345,10 +355,7 @@ class Engine:
         E = self.cfg.n_embd_common
         assert h.dim() == 2 and h.shape[1] == E, h.shape
         B = int(h.shape[0])
-        need = int(self.l.coati_engine_workspace_bytes(self.h, B, 1, 1, 1, B))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = None
-            self.workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        self._fit_workspace(B, 1, 1, 1)
         out = torch.empty(B, E, device=self.device, dtype=torch.float32)
         self._keep = (h,)
         _lib.check(self.l.coati_engine_token_head(self.h, ptr(self.workspace), self.workspace.numel(), B, ptr(h), ptr(out), stream()),
@@ -390,11 +397,9 @@ class Engine:
         if getattr(self, "_packed", False):
             raise RuntimeError("logits(): the last forward ran on packed rows; call forward(..., rows=None)")
         B, _, T2, _ = self._shape
-        V = self.cfg.n_tok
-        ld = (V + 7) // 8 * 8
-        out = torch.empty(B * T2, ld, device=self.device, dtype=torch.float32)
+        out, ld, logits = self._logits_rows(B * T2)
         _lib.check(self.l.coati_engine_logits(self.h, ptr(out), ld, stream()), "coati_engine_logits")
-        return out[:, :V].view(B, T2, V)
+        return logits.view(B, T2, self.cfg.n_tok)
 
     def infonce(self, s_loc, c_loc, s_all, c_all, bad_all, row0=0, gscale=1.0):
         B, Bg = s_loc.shape[0], s_all.shape[0]
@@ -499,21 +504,17 @@ class Engine:
         B = self._dec_B
         tokens = tokens.to(self.device, torch.long).contiguous()
         assert tokens.shape == (B,)
-        inj = None
-        if injection is not None:
-            inj = injection.to(self.device, torch.float32).contiguous()
-            assert inj.shape == (B, self.cfg.n_hidden_xformer)
-        V = self.cfg.n_tok
+        inj = self._injection(injection, B)
         if graph:
+            V = self.cfg.n_tok
             lp, ld = ctypes.c_void_p(), ctypes.c_int64()
             _lib.check(self.l.coati_engine_decode_graph_step(self.h, ptr(tokens), ptr(inj), ctypes.byref(lp), ctypes.byref(ld), stream()),
                        "decode_graph_step")
             off = lp.value - self._dec_ws.data_ptr()
             return self._dec_ws[off: off + B * ld.value * 4].view(torch.float32).view(B, ld.value)[:, :V]
-        ld = (V + 7) // 8 * 8          # f32 rows 16-B aligned for the GEMM epilogue's float4 stores
-        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
-        _lib.check(self.l.coati_engine_decode_step(self.h, ptr(tokens), ptr(inj), ptr(logits), ld, stream()), "decode_step")
-        return logits[:, :V] if want_logits else None
+        buf, ld, logits = self._logits_rows(B, want_logits)
+        _lib.check(self.l.coati_engine_decode_step(self.h, ptr(tokens), ptr(inj), ptr(buf), ld, stream()), "decode_step")
+        return logits
 
     def decode_prefill(self, tokens, injection=None, want_logits=True):
         """Positions 0..m-1 of a fresh session (decode_begin) in ONE transformer pass over tokens [B, m] int64 instead of m
@@ -524,19 +525,14 @@ class Engine:
         tokens = tokens.to(self.device, torch.long).contiguous()
         assert tokens.dim() == 2 and tokens.shape[0] == B, tokens.shape
         m = int(tokens.shape[1])
-        inj = None
-        if injection is not None:
-            inj = injection.to(self.device, torch.float32).contiguous()
-            assert inj.shape == (B, self.cfg.n_hidden_xformer)
+        inj = self._injection(injection, B)
         self._ensure_workspace(B, 1, m, 1)
-        V = self.cfg.n_tok
-        ld = (V + 7) // 8 * 8
-        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
+        buf, ld, logits = self._logits_rows(B, want_logits)
         self._keep = (tokens, inj)
         _lib.check(self.l.coati_engine_decode_prefill(self.h, ptr(self.workspace), self.workspace.numel(), ptr(tokens), m, ptr(inj),
-                                                      ptr(logits), ld, stream()), "decode_prefill")
+                                                      ptr(buf), ld, stream()), "decode_prefill")
         self._shape = None
-        return logits[:, :V] if want_logits else None
+        return logits
 
     # ---- ragged sessions: every row at its own position -------------------------------------------------------------
     def decode_step_rows(self, tokens, pos, injection=None, inj_len=None, want_logits=True):
@@ -548,19 +544,14 @@ class Engine:
         tokens = tokens.to(self.device, torch.long).contiguous()
         assert tokens.shape == (B,)
         assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.shape == (B,) and pos.device == tokens.device, "pos: int32 [B] on the device"
-        inj = None
-        if injection is not None:
-            inj = injection.to(self.device, torch.float32).contiguous()
-            assert inj.shape == (B, self.cfg.n_hidden_xformer)
+        inj = self._injection(injection, B)
         if inj_len is not None:
             assert inj is not None and inj_len.dtype == torch.int32 and inj_len.is_contiguous() and inj_len.shape == (B,)
             assert inj_len.device == tokens.device
-        V = self.cfg.n_tok
-        ld = (V + 7) // 8 * 8
-        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
-        _lib.check(self.l.coati_engine_decode_step_rows(self.h, ptr(tokens), ptr(pos), ptr(inj), ptr(inj_len), ptr(logits), ld, stream()),
+        buf, ld, logits = self._logits_rows(B, want_logits)
+        _lib.check(self.l.coati_engine_decode_step_rows(self.h, ptr(tokens), ptr(pos), ptr(inj), ptr(inj_len), ptr(buf), ld, stream()),
                    "decode_step_rows")
-        return logits[:, :V] if want_logits else None
+        return logits
 
     def decode_prefill_rows(self, prompt, plen, injection=None, want_logits=True):
         """Every row's WHOLE prompt of a fresh session in one transformer pass on packed rows: prompt [B, W] int64 (row b counts
@@ -576,19 +567,14 @@ class Engine:
         if int(plen_h.min()) < 1 or int(plen_h.max()) > min(W, Tmax):
             raise ValueError(f"decode_prefill_rows: prompt lengths {int(plen_h.min())} .. {int(plen_h.max())}; 1 .. {min(W, Tmax)} fit")
         plen_d = plen.to(self.device, torch.int32).contiguous()
-        inj = None
-        if injection is not None:
-            inj = injection.to(self.device, torch.float32).contiguous()
-            assert inj.shape == (B, self.cfg.n_hidden_xformer)
+        inj = self._injection(injection, B)
         self._ensure_workspace(B, 1, W, 1)
-        V = self.cfg.n_tok
-        ld = (V + 7) // 8 * 8
-        logits = torch.empty(B, ld, device=self.device, dtype=torch.float32) if want_logits else None
+        buf, ld, logits = self._logits_rows(B, want_logits)
         self._keep = (prompt, plen_d, inj)
         _lib.check(self.l.coati_engine_decode_prefill_rows(self.h, ptr(self.workspace), self.workspace.numel(), ptr(prompt), W, ptr(plen_d),
-                                                           int(plen_h.sum()), ptr(inj), ptr(logits), ld, stream()), "decode_prefill_rows")
+                                                           int(plen_h.sum()), ptr(inj), ptr(buf), ld, stream()), "decode_prefill_rows")
         self._shape = None
-        return logits[:, :V] if want_logits else None
+        return logits
 
     def _sample_rows(self, logits, k, inv_temp, u, ldu, prompt, plen, req, pos, out, tok_next, done, Tmax, stop_token):
         """coati_topk_sample_rows on the session's B slots (see include/coati_hip.h)."""

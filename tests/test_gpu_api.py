@@ -162,3 +162,26 @@ def test_reference_written_checkpoint_loads_and_resumes(golden_dir):
         d_hip, d_ref = (sd[k].cpu() - a1).flatten().double(), (a3 - a1).flatten().double()
         cos = float((d_hip @ d_ref) / (d_hip.norm() * d_ref.norm() + 1e-30))
         assert cos > 0.9, (k, cos)
+
+
+def test_forward_decoder_refused_behind_an_encode(golden_dir):
+    """Every entry that re-carves the workspace drops a pending decoder pass: forward(stop_after_heads=True) followed by an encode
+    leaves buffers laid out for the encode's shape, so forward_decoder() is refused (a host-side argument check: nothing is launched)."""
+    from coati_amd.engine import Engine, ModelConfig
+    z = np.load(os.path.join(golden_dir, "small_model.npz"))
+    v = np.load(os.path.join(golden_dir, "small_vectors.npz"))
+    eng = Engine(ModelConfig(n_layer_e3gnn=2, n_layer_xformer=2, n_hidden_xformer=64, n_hidden_e3nn=64, n_embd_common=64,
+                             n_head=4, n_seq=24, n_tok=48), DEV)
+    eng.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files})
+    b = {k: torch.from_numpy(v["b_" + k]).to(DEV) for k in ("raw_tokens", "tokens", "atoms", "coords", "y_next")}
+    up = torch.ones(b["atoms"].shape[0], dtype=torch.bool, device=DEV)
+    _, h_s, _ = eng.forward(b["raw_tokens"], b["tokens"], b["atoms"], b["coords"], up, y_next=b["y_next"], stop_after_heads=True)
+    h_enc, _ = eng.encode(raw_tokens=b["raw_tokens"][:3].contiguous())
+    with pytest.raises(RuntimeError, match="no forward stopped"):
+        eng.forward_decoder()
+    torch.cuda.synchronize()
+    assert torch.isfinite(h_enc).all() and h_enc.shape == (3, 64) and torch.isfinite(h_s).all()
+    # the sequence itself still works: a forward stopped behind the heads, then its decoder pass
+    eng.forward(b["raw_tokens"], b["tokens"], b["atoms"], b["coords"], up, y_next=b["y_next"], stop_after_heads=True)
+    eng.forward_decoder()
+    assert np.isfinite(eng.losses()["ar_loss"])
