@@ -101,6 +101,7 @@ _SIGS = {
     "coati_engine_logits": [P, P, L, P],
     "coati_engine_encode": [P, P, L, I, I, I, P, P, P, P, P, P, P],
     "coati_engine_score": [P, P, L, I, I, I, P, P, P, P, L, L, P, P, P],
+    "coati_engine_score_grad": [P, P, L, I, I, P, P, P, L, P, P, P, P, P],
     "coati_engine_encode_packed": [P, P, L, I, I, P, L, P, P, P],
     "coati_engine_decoder_logits": [P, P, L, I, I, P, P, P, L, P, P],
     "coati_engine_infonce": [P, P, P, P, P, P, I, I, I, F, P, P, P, P],

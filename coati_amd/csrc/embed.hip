@@ -400,23 +400,47 @@ int launch_ce_finish(const float2* partial, int tiles_n, const bf16_t* a, long l
 // (targets < 0 ignored).  One workgroup per sequence: wave w takes rows w, w + 4, ... of the sequence, the four wave sums are added in
 // LDS in a fixed order -- no float atomics, so the same batch always gives the same bits.  Rows: b * T .. b * T + T (padded) or
 // off[b] .. off[b + 1] (packed; target = the packed targets ypk).
+// BWD: also what the per-sequence backward reads (gemm_epi.h EPI_CE_BWD_ROW) -- lse[row] of every row the workgroup walks and
+// row_scale[row] = weights[b] (null: 1) where the row has a target, else 0.  The sums are formed exactly as without it.
+template <bool BWD>
+__device__ __forceinline__ void ce_seq_body(const float2* __restrict__ partial, int tiles_n, const bf16_t* __restrict__ a, long long lda,
+                                            const bf16_t* __restrict__ W, long long ldw, const long long* __restrict__ target,
+                                            const int* __restrict__ off, const float* __restrict__ weights, float* __restrict__ nll,
+                                            float* __restrict__ lse, float* __restrict__ row_scale, int T, int C, int V) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
+  const long long r0 = off ? (long long)off[b] : (long long)b * T, r1 = off ? (long long)off[b + 1] : r0 + T;
+  float wb = 1.f;
+  if constexpr (BWD) wb = weights ? weights[b] : 1.f;
+  float acc = 0.f;
+  for (long long row = r0 + wave; row < r1; row += 4) {
+    bool valid;
+    const float d = ce_row(partial, tiles_n, a, lda, W, ldw, target[row], row, C, V, BWD ? lse + row : nullptr, lane, &valid);
+    if (valid) acc += d;
+    if constexpr (BWD) {
+      if (lane == 0) row_scale[row] = valid ? wb : 0.f;
+    }
+  }
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) nll[b] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 __global__ __launch_bounds__(256) void ce_seq_kernel(const float2* __restrict__ partial, int tiles_n,
                                                      const bf16_t* __restrict__ a, long long lda,
                                                      const bf16_t* __restrict__ W, long long ldw,
                                                      const long long* __restrict__ target, const int* __restrict__ off,
                                                      float* __restrict__ nll, int T, int C, int V) {
-  __shared__ float red[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
-  const long long r0 = off ? (long long)off[b] : (long long)b * T, r1 = off ? (long long)off[b + 1] : r0 + T;
-  float acc = 0.f;
-  for (long long row = r0 + wave; row < r1; row += 4) {
-    bool valid;
-    const float d = ce_row(partial, tiles_n, a, lda, W, ldw, target[row], row, C, V, nullptr, lane, &valid);
-    if (valid) acc += d;
-  }
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) nll[b] = ((red[0] + red[1]) + red[2]) + red[3];
+  ce_seq_body<false>(partial, tiles_n, a, lda, W, ldw, target, off, nullptr, nll, nullptr, nullptr, T, C, V);
+}
+
+__global__ __launch_bounds__(256) void ce_seq_bwd_kernel(const float2* __restrict__ partial, int tiles_n,
+                                                         const bf16_t* __restrict__ a, long long lda,
+                                                         const bf16_t* __restrict__ W, long long ldw,
+                                                         const long long* __restrict__ target, const int* __restrict__ off,
+                                                         const float* __restrict__ weights, float* __restrict__ nll,
+                                                         float* __restrict__ lse, float* __restrict__ row_scale, int T, int C, int V) {
+  ce_seq_body<true>(partial, tiles_n, a, lda, W, ldw, target, off, weights, nll, lse, row_scale, T, C, V);
 }
 
 int launch_ce_seq(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,
@@ -425,5 +449,16 @@ int launch_ce_seq(const float2* partial, int tiles_n, const bf16_t* a, long long
   COATI_CHECK_SHAPE(B > 0 && T > 0 && C % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "ce_seq: shape / alignment");
   hipLaunchKernelGGL(ce_seq_kernel, dim3(B), dim3(256), 0, s, partial, tiles_n, a, lda, W, ldw, target, off, nll, T, C, V);
   COATI_LAUNCH_CHECK("ce_seq");
+  return COATI_OK;
+}
+
+int launch_ce_seq_bwd(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,
+                      const long long* target, const int* off, const float* weights, float* nll, float* lse, float* row_scale, int B, int T,
+                      int C, int V, hipStream_t s) {
+  COATI_CHECK_ARG(partial && a && W && target && nll && lse && row_scale, "ce_seq_bwd: null operand");
+  COATI_CHECK_SHAPE(B > 0 && T > 0 && C % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "ce_seq_bwd: shape / alignment");
+  hipLaunchKernelGGL(ce_seq_bwd_kernel, dim3(B), dim3(256), 0, s, partial, tiles_n, a, lda, W, ldw, target, off, weights, nll, lse, row_scale,
+                     T, C, V);
+  COATI_LAUNCH_CHECK("ce_seq_bwd");
   return COATI_OK;
 }

@@ -160,6 +160,7 @@ struct coati_engine {
   // lm head
   float2* ce_partial;
   float* ce_lse;
+  float* ce_rowscale;   // [M2] per-row factor of the per-sequence dlogits (coati_engine_score_grad)
   bf16_t* dlogits;
   // gnn
   std::vector<float*> g_h32, g_rstd;
@@ -558,7 +559,7 @@ static int row_split_plan(const GemmArgs& a, int a_f32, int epi) {
   if (!row_split_on() || a.m_dev != nullptr || a_f32 || a.M <= 65536 || a.q8_out != nullptr) return 0;
   if (!(a.K == 256 || a.N == 256)) return 0;
   if (epi != EPI_BF16 && epi != EPI_RES_F32 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL &&
-      epi != EPI_CE_BWD && epi != EPI_LNBWD) return 0;
+      epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_LNBWD) return 0;
   // a launch starts on a 16-row slab and, in the padded layout of the rotary epilogue (row m sits at position m % rope_T), on a sequence
   // boundary
   long long unit = 16;
@@ -588,6 +589,7 @@ static void advance_rows(GemmArgs& a, long long r0, int epi, int lnb_partial_row
   a.aux_out = const_cast<void*>(adv(a.aux_out, r0 * a.ld_aux * aux_out_b));
   if (a.lse) a.lse += r0;
   if (a.target) a.target += r0;
+  if (a.row_scale) a.row_scale += r0;
   if (a.partial) a.partial += r0 * cdiv(a.N, a.partial_tile > 0 ? a.partial_tile : 128);
   if (a.rope_row_t) a.rope_row_t += r0;
   if (a.ln_x) { a.ln_x += r0 * a.ln_ldx; a.ln_mean += r0; a.ln_rstd += r0; }
@@ -832,6 +834,7 @@ size_t carve(coati_engine* e, Arena& ar, int B_, int T1_, int T2_, int A_, int B
     e->q8b = ar.take<unsigned char>(Mmax * 4 * C);
     e->q8bs = ar.take<unsigned char>(Mmax * 4 * C / 32);
   }
+  e->ce_rowscale = ar.take<float>(M2);
   e->opt_partial = ar.take<float>(1024);
   e->ln_partial = ar.take<float>((size_t)COATI_LN_PARTIAL_ROWS * 2 * (C > H ? C : H));
   e->ln_part_x = ar.take<float>((size_t)(2 * c.n_layer_xformer + 1) * COATI_LN_PARTIAL_ROWS * 2 * C);
@@ -1059,8 +1062,11 @@ int xformer_wgrad_group(coati_engine* e, XPass& p, int l_lo, int l_hi, hipStream
 // layers [l_lo, l_hi) only, descending; the ln_f backward belongs to l_hi == L, the embedding backward to l_lo == 0
 // lmh_dlogits (decoder pass): d logits [M, Vpad] bf16 -- dyf (= e->da) has NOT been computed yet, xformer_bwd runs the lm_head's
 // input-gradient product itself (with ln_f's backward fused into it at packed-batch sizes)
+// inputs_only: the gradient w.r.t. the injection alone (coati_engine_score_grad; e->G may be null) -- no weight gradient, single or grouped,
+// no dgamma / dbeta sums, no token-table scatter, and no address inside the gradient buffer is formed.  The deferred and GEMM-fused
+// LayerNorm backwards still leave their partial rows in the workspace; nobody adds them up
 int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* dinjection, hipStream_t s, int l_hi = -1, int l_lo = 0,
-                const bf16_t* lmh_dlogits = nullptr) {
+                const bf16_t* lmh_dlogits = nullptr, bool inputs_only = false) {
   const coati_config& c = e->cfg;
   const int C = c.n_hidden_xformer, L = c.n_layer_xformer, M = p.M;
   if (l_hi < 0) l_hi = L;
@@ -1073,6 +1079,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
   int nblk = 0;
   auto ln_bwd = [&](const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd, const float* gamma,
                     const float* dres, size_t goff, size_t boff, bf16_t* dx16) -> int {
+    if (!defer && inputs_only) return launch_layernorm_bwd(dy, dy_f32, C, x, C, 0, mean, rstd, gamma, dres, DX, dx16, nullptr, nullptr, e->ln_partial, M, C, s);
     if (!defer) return launch_layernorm_bwd(dy, dy_f32, C, x, C, 0, mean, rstd, gamma, dres, DX, dx16, e->G + goff, e->G + boff, e->ln_partial, M, C, s);
     fin.dg_off[fin.n] = (long long)goff;
     fin.db_off[fin.n] = (long long)boff;
@@ -1107,7 +1114,9 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
   };
   // Weight gradients: immediately, one launch per Linear (small shapes), or deferred to ONE grouped launch at the end of
   // this call (grouped = every activation gradient of the layer range stays alive in its own buffer).
-  const bool grp = e->wg_group && M >= 4096;
+  const bool grp = e->wg_group && M >= 4096 && !inputs_only;
+  const bool wg_each = !grp && !inputs_only;   // one weight-gradient launch per Linear
+  COATI_CHECK_ARG(!inputs_only || (!p.tail && !c.use_fp8 && dinjection != nullptr), "xformer_bwd: the inputs-only backward serves a full bf16 pass with an injection");
   if (l_hi == L && p.tail) {
     // ln_f backward on the B tail rows (dyf = [B, C]); not deferred: its partial sums have their own row count
     ProfScope ps(e, SITE_XF_TAIL, 0, s, (double)p.B * C * ((dyf_f32 ? 4 : 2) + 4 + 4 + 2));
@@ -1173,7 +1182,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
       if (ln2_fused < 0) return ln2_fused;
       if (!ln2_fused) COATI_TRY(gemm(e, SITE_FC1_DGRAD, dh4, 0, 4 * C, e->S + w.fc1T, 4 * C, M, C, 4 * C, e->da, C, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
       }
-      if (!grp) {
+      if (wg_each) {
         COATI_TRY(wgrad(e, SITE_XF_WGRAD, dh4, 0, 4 * C, p.a2[l], C, M, 4 * C, C, e->G + w.fc1w, C, e->G + w.fc1b, 0, s));
         // (the fc2 weight gradient runs after the two consumers of dh4, so that dh4 is re-read while it is still warm)
         COATI_TRY(wgrad(e, SITE_XF_WGRAD, dxa, 0, C, p.g[l], 4 * C, M, C, 4 * C, e->G + w.fc2w, 4 * C, e->G + w.fc2b, 0, s));
@@ -1192,7 +1201,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
     } else if (!ln2_fused) {   // (fused: the chained product of the launch above has written dyb)
     COATI_TRY(gemm(e, SITE_PROJ_DGRAD, dxb, 0, C, e->S + w.projT, C, M, C, C, e->dyb, C, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
     }
-    if (!grp) COATI_TRY(wgrad(e, SITE_XF_WGRAD, dxb, 0, C, p.y[l], C, M, C, C, e->G + w.projw, C, e->G + w.projb, 0, s));
+    if (wg_each) COATI_TRY(wgrad(e, SITE_XF_WGRAD, dxb, 0, C, p.y[l], C, M, C, C, e->G + w.projw, C, e->G + w.projb, 0, s));
     {
       ProfScope ps(e, SITE_ATTN_BWD, 10.0 * M * (double)p.T * C, s, (double)M * 8 * C * 2 + (double)M * c.n_head * 8);   // qkv, y, dy in; dqkv out
       COATI_TRY(launch_attn_bwd(p.qkv[l], p.y[l], e->dyb, p.lse[l], e->attnD, dqkv, e->cos_t, e->sin_t, p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed && lpt_on() ? p.ord : nullptr));
@@ -1207,19 +1216,21 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
     if (ln1_fused < 0) return ln1_fused;
     if (!ln1_fused) COATI_TRY(gemm(e, SITE_QKV_DGRAD, dqkv, 0, 3 * C, e->S + w.attnT, 3 * C, M, C, 3 * C, e->da, C, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
     }
-    if (!grp) COATI_TRY(wgrad(e, SITE_XF_WGRAD, dqkv, 0, 3 * C, p.a1[l], C, M, 3 * C, C, e->G + w.attnw, C, e->G + w.attnb, 0, s));
+    if (wg_each) COATI_TRY(wgrad(e, SITE_XF_WGRAD, dqkv, 0, 3 * C, p.a1[l], C, M, 3 * C, C, e->G + w.attnw, C, e->G + w.attnb, 0, s));
     if (!ln1_fused) {
       ProfScope ps(e, SITE_LN_BWD, 0, s, (double)M * C * (2 + 4 + 4 + 4 + 2));   // dy16, x, dres in; dx, dx16 out
       COATI_TRY(ln_bwd(e->da, 0, p.x[l], p.mean1[l], p.rstd1[l], e->P + w.ln1w, DX, w.ln1w, w.ln1b, dx_out));
     }
   }
   if (grp && l_hi > l_lo) COATI_TRY(xformer_wgrad_group(e, p, l_lo, l_hi, s));
-  if (defer && fin.n > 0) {
+  if (defer && fin.n > 0 && !inputs_only) {
     ProfScope ps(e, SITE_LN_BWD, 0, s, 0.0);
     COATI_TRY(launch_ln_finish_batched(e->ln_part_x, slot_stride, nblk, e->G, fin, C, s));
   }
   if (l_lo > 0) return COATI_OK;
   ProfScope ps(e, SITE_EMBED, 0, s);
+  // (inputs_only: the [UNK] rows' gradient is all that is wanted -- with norm_embed the injection replaced the LayerNorm's output there)
+  if (inputs_only) return launch_embed_bwd(p.idx, DX, nullptr, dinjection, c.unk_token, p.B, p.T, C, c.n_tok, s, p.packed ? p.off : nullptr, 1);
   if (c.norm_embed) {
     // the injected rows' gradient goes to the injection and is CLEARED (the LayerNorm's output was overwritten there: nothing flows into
     // it), then the embedding LayerNorm's backward over all rows (its output lands in x[0], dead by now), then the table scatter
@@ -1902,21 +1913,23 @@ int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_
 // the caller's h_clip, or smiles_to_clip of the encoder pass over raw_tokens --, the special-token head, the decoder pass with that
 // injection, lm_head as CE partials and their per-sequence sums.  No point encoder, no logits, nothing saved for a backward
 // (have_fwd stays false).  rows2 > 0: the decoder pass on packed rows (rows1 > 0 with it for the encoder pass over raw_tokens).
-int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
-                       const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
-                       float* scal, void* stream) {
-  COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens && y_next && nll && scal, "engine_score: engine not bound / null argument");
-  COATI_CHECK_ARG((raw_tokens != nullptr) != (h_clip != nullptr), "engine_score: give exactly one of raw_tokens / h_clip");
-  COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_score: a COATI2 engine is inference-only (COATI1's scoring head)");
+// What coati_engine_score and coati_engine_score_grad share: the argument checks (`entry`: the caller's name in the messages), the
+// prologue and the forward up to the per-sequence sums.  for_grad: the sums also leave lse and the per-row factors (weights: [B] or null =
+// ones) that the dlogits product of the backward reads; the transformer's saves are in the workspace either way.
+static int score_forward(coati_engine* e, const char* entry, void* workspace, int64_t workspace_bytes, int B, int T1, int T2,
+                         const int64_t* raw_tokens, const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1,
+                         int64_t rows2, float* nll, float* scal, bool for_grad, const float* weights, hipStream_t s) {
+  COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens && y_next && nll && scal, "%s: engine not bound / null argument", entry);
+  COATI_CHECK_ARG((raw_tokens != nullptr) != (h_clip != nullptr), "%s: give exactly one of raw_tokens / h_clip", entry);
+  COATI_CHECK_ARG(e->enc_to_coati < 0, "%s: a COATI2 engine is inference-only (COATI1's scoring head)", entry);
   const coati_config& c = e->cfg;
   if (!raw_tokens) { T1 = 1; rows1 = 0; }
-  COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T2 > 0 && T1 <= c.n_seq && T2 <= c.n_seq, "engine_score: unsupported shape B=%d T1=%d T2=%d (n_seq=%d)",
+  COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T2 > 0 && T1 <= c.n_seq && T2 <= c.n_seq, "%s: unsupported shape B=%d T1=%d T2=%d (n_seq=%d)", entry,
                     B, T1, T2, c.n_seq);
   COATI_CHECK_SHAPE(rows1 >= 0 && rows2 >= 0 && rows1 <= (int64_t)B * T1 && rows2 <= (int64_t)B * T2 && (!raw_tokens || (rows1 > 0) == (rows2 > 0)),
-                    "engine_score: packed row counts %lld / %lld do not fit %d x %d / %d x %d", (long long)rows1, (long long)rows2, B, T1, B, T2);
-  hipStream_t s = (hipStream_t)stream;
+                    "%s: packed row counts %lld / %lld do not fit %d x %d / %d x %d", entry, (long long)rows1, (long long)rows2, B, T1, B, T2);
   const int C = c.n_hidden_xformer;
-  COATI_TRY(begin_call(e, "engine_score", workspace, workspace_bytes, B, T1, T2, 1, scal));
+  COATI_TRY(begin_call(e, entry, workspace, workspace_bytes, B, T1, T2, 1, scal));
   e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
   e->p2.idx = reinterpret_cast<const long long*>(tokens);
   e->y_next = reinterpret_cast<const long long*>(y_next);
@@ -1938,8 +1951,62 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
   COATI_TRY(xformer_fwd(e, e->p2, inj, s));
   int tiles_v = 0;
   COATI_TRY(lmhead_ce_partial(e, s, &tiles_v));
-  COATI_TRY(launch_ce_seq(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next,
-                          e->p2.packed ? e->p2.off : nullptr, nll, B, T2, C, c.n_tok, s));
+  const long long* const target = e->p2.packed ? e->p2.ypk : e->y_next;
+  const int* const off = e->p2.packed ? e->p2.off : nullptr;
+  if (for_grad)
+    return launch_ce_seq_bwd(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, target, off, weights, nll, e->ce_lse, e->ce_rowscale, B, T2,
+                             C, c.n_tok, s);
+  return launch_ce_seq(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, target, off, nll, B, T2, C, c.n_tok, s);
+}
+
+int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
+                       const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
+                       float* scal, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COATI_TRY(score_forward(e, "engine_score", workspace, workspace_bytes, B, T1, T2, raw_tokens, h_clip, tokens, y_next, rows1, rows2, nll, scal,
+                          false, nullptr, s));
+  return publish_errors(e, scal, s);
+}
+
+// The likelihood's gradient w.r.t. the injected embedding (the reference reaches it by autograd through clip_e2e.py:634-665):
+// nll as coati_engine_score(h_clip = ...) gives it, dh_clip[b] = weights[b] * d nll[b] / d h_clip[b] through the decoder pass and
+// point_clip_to_special_tokens, summed over the [UNK] positions of row b.  Launches: the scoring forward; dlogits with the per-row factor
+// (EPI_CE_BWD_ROW); the lm_head's input gradient (+ ln_f's backward); the layers' input gradients; the [UNK] rows' gather; the token
+// head's backward to dh alone.  The model is a constant here: no parameter gradient is formed, the gradient buffer, the Adam state and
+// the parameters are not touched (a forward-only engine, whose gradient buffer is null, serves), and have_fwd stays false.
+int coati_engine_score_grad(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_clip,
+                            const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll, float* dh_clip,
+                            float* scal, void* stream) {
+  COATI_CHECK_ARG(e && h_clip && dh_clip, "engine_score_grad: null argument");
+  COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_score_grad: a COATI2 engine has no likelihood head");
+  COATI_CHECK_ARG(!e->cfg.use_fp8, "engine_score_grad: not available on an fp8 engine (the inputs-only backward runs the bf16 products)");
+  hipStream_t s = (hipStream_t)stream;
+  COATI_TRY(score_forward(e, "engine_score_grad", workspace, workspace_bytes, B, 1, T2, nullptr, h_clip, tokens, y_next, 0, rows2, nll, scal, true,
+                          weights, s));
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, E = c.n_embd_common, M2 = e->p2.M;
+  // ---- dlogits[row] = (softmax - onehot) * weights[seq(row)], 0 on rows without target ----
+  {
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = M2; a.N = c.n_tok; a.K = C;
+    a.C = e->dlogits; a.ldc = e->Vpad; a.n_store = e->Vpad; a.lse = e->ce_lse; a.target = e->p2.packed ? e->p2.ypk : e->y_next;
+    a.row_scale = e->ce_rowscale;
+    ProfScope ps(e, SITE_LMHEAD_DLOGITS, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2 + (double)M2 * e->Vpad * 2);
+    COATI_TRY(gemm_rows(a, 0, EPI_CE_BWD_ROW, s));
+  }
+  // ---- decoder pass, input gradients only; the [UNK] rows' gradient sums into dcliptok ----
+  HIPCHK(hipMemsetAsync(e->dcliptok, 0, (size_t)B * E * sizeof(float), s));
+  COATI_TRY(xformer_bwd(e, e->p2, e->da, 0, e->dcliptok, s, -1, 0, e->dlogits, true));
+  // ---- point_clip_to_special_tokens backward to dh alone: dh = (dtok W) * SiLU'(h) ; nn.Identity: dh = dtok ----
+  if (c.token_mlp) {
+    SgemmBatch sb;
+    COATI_TRY(sgemm_batch_add(sb, e->dcliptok, E, 1, e->P + e->tokw, E, 1, e->dsb, E, B, E, E, nullptr, 1.f, 0));   // dact[b,k] = sum_n dtok[b,n] W[n,k]
+    COATI_TRY(launch_sgemm_batch(sb, s));
+    COATI_TRY(launch_silu_bwd(h_clip, e->dsb, dh_clip, (long long)B * E, 0, s));
+  } else {
+    HIPCHK(hipMemcpyAsync(dh_clip, e->dcliptok, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
   return publish_errors(e, scal, s);
 }
 

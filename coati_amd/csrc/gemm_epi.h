@@ -189,10 +189,15 @@ __device__ __forceinline__ void epilogue8(const GemmArgs& p, int row, int col0, 
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = v[e] * ((EPI == EPI_DGELU) ? dgelu_f(x[e]) : dsilu_f(x[e]));
-  } else if (EPI == EPI_CE_BWD) {
+  } else if (EPI == EPI_CE_BWD || EPI == EPI_CE_BWD_ROW) {
     const long long tgt = p.target[row];
-    const float cnt = p.scal[1];
-    const float inv = (tgt >= 0 && cnt > 0.f) ? 1.0f / cnt : 0.f;
+    float inv;
+    if (EPI == EPI_CE_BWD_ROW) {   // per-sequence gradient: the row's own factor (launch_ce_seq_bwd: 0 where the row has no target)
+      inv = p.row_scale[row];
+    } else {
+      const float cnt = p.scal[1];
+      inv = (tgt >= 0 && cnt > 0.f) ? 1.0f / cnt : 0.f;
+    }
     const float l = p.lse[row];
     // (softmax(v) - onehot) / count in few VALU slots (they add to the tile time): the target's position relative to this lane's 8
     // columns as ONE 32-bit value (anything outside 0..7 never matches).  exp(v - lse) keeps the subtraction FIRST: folded into

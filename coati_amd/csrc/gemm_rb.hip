@@ -384,7 +384,7 @@ bool gemm_rb256_supported(const GemmArgs& a, int a_f32, int epi) {
   if (a_f32 || a.K != RB_K) return false;
   if (epi == EPI_CE_PARTIAL && a.partial_tile != 64) return false;   // the caller's partial buffer is laid out for 128-column tiles
   if (epi == EPI_QKV_ROPE && a.rope_hs == 32) return false;   // the staged rotary rows are laid out for head size 16
-  if (a.N % 16 != 0 && epi != EPI_CE_BWD && epi != EPI_CE_PARTIAL) return false;   // (those two write no N-wide rows)
+  if (a.N % 16 != 0 && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_CE_PARTIAL) return false;   // (those write no N-wide rows)
   // small problems run on the tiled kernel.  (Packed rows: a full-size batch carries ~50 000 rows instead of 81 920, i.e.
   // 6-7 slabs per workgroup -- still one round of one workgroup per CU, with LayerNorm fused into the operand load.)
   if (rb_waves(a.M) < 5) return false;
@@ -431,7 +431,7 @@ static int launch_rb_t(const GemmArgs& a, hipStream_t s) {
   // 3.51 ms/step, lm_head 0.78 -> 0.75 / 0.73 -> 0.72, but FC2 input gradient 2.41 -> 2.63 and QKV 2.37 -> 2.43 -- it pays only
   // where the epilogue outweighs the extra MFMA block of a half wave;
   // epilogues whose per-wave LDS does not fit 12 times keep 10 waves.
-  const bool half_on = (EPI == EPI_GELU_GRAD || EPI == EPI_CE_PARTIAL || EPI == EPI_CE_BWD);
+  const bool half_on = (EPI == EPI_GELU_GRAD || EPI == EPI_CE_PARTIAL || EPI == EPI_CE_BWD || EPI == EPI_CE_BWD_ROW);
   constexpr bool half_fits = 2 * 64 * RB_K * 2 + RB_HALF_W * rb_per_wave_bytes<EPI, 64>() <= 160 * 1024;
   const bool half = half_on && half_fits && W == RB_MAX_W && a.m_dev == nullptr;
   if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_GELU_GRAD) {
@@ -463,6 +463,7 @@ int launch_gemm_rb256(const GemmArgs& a, int epi, hipStream_t s) {
     case EPI_DSILU: return launch_rb_t<EPI_DSILU>(a, s);
     case EPI_ACC_F32: return launch_rb_t<EPI_ACC_F32>(a, s);
     case EPI_CE_BWD: return launch_rb_t<EPI_CE_BWD>(a, s);
+    case EPI_CE_BWD_ROW: return launch_rb_t<EPI_CE_BWD_ROW>(a, s);
     case EPI_CE_PARTIAL: return launch_rb_t<EPI_CE_PARTIAL>(a, s);
     case EPI_EDGE_DPRE: return launch_rb_t<EPI_EDGE_DPRE>(a, s);
     case EPI_QKV_ROPE: return launch_rb_t<EPI_QKV_ROPE>(a, s);

@@ -687,10 +687,10 @@ static int rb16_min_waves() {
 
 bool gemm_rb16_supported(const GemmArgs& a, int a_f32, int epi) {
   if (a_f32 || a.K != R16_K || a.m_dev != nullptr) return false;
-  if (epi != EPI_BF16 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL && epi != EPI_CE_BWD) return false;
+  if (epi != EPI_BF16 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW) return false;
   if (epi == EPI_CE_PARTIAL && a.partial_tile != 64) return false;
   if (epi == EPI_QKV_ROPE && a.rope_hs == 32) return false;
-  if (a.N % 16 != 0 && epi != EPI_CE_BWD && epi != EPI_CE_PARTIAL) return false;
+  if (a.N % 16 != 0 && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_CE_PARTIAL) return false;
   if (a.bias != nullptr && cdiv(a.N, R16_BN) * R16_BN > R16_BIAS_MAX) return false;
   if (a.q8_out != nullptr) return false;                              // (the fused MXFP8 emission assumes epilogue8's lane layout)
   if (epi == EPI_GELU_GRAD && a.n_store > a.N) return false;
@@ -733,6 +733,7 @@ int launch_gemm_rb16(const GemmArgs& a, int epi, hipStream_t s) {
     case EPI_MUL_AUX: return launch_rb16_t<EPI_MUL_AUX, false>(a, s);
     case EPI_CE_PARTIAL: return launch_rb16_t<EPI_CE_PARTIAL, false>(a, s);
     case EPI_CE_BWD: return launch_rb16_t<EPI_CE_BWD, false>(a, s);
+    case EPI_CE_BWD_ROW: return launch_rb16_t<EPI_CE_BWD_ROW, false>(a, s);
     default:
       coati_set_error("gemm_rb16: unsupported epilogue %d", epi);
       return COATI_EARG;

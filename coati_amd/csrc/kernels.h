@@ -24,7 +24,9 @@ enum CoatiEpi {
   EPI_LNBWD = 14,      // N = C, ring GEMM only: dy = acc is the gradient w.r.t. a LayerNorm's output; C(f32) = aux_in(f32) + LayerNorm-backward(dy | lnb_x, lnb_mean,
                        // lnb_rstd, lnb_gamma) (aux_in may be C: the residual-stream gradient in place), aux_out(bf16, optional) = its bf16 copy,
                        // lnb_partial[workgroup][2N] = the workgroup's dgamma | dbeta sums (added up by launch_ln_finish_batched)
-  EPI_COUNT = 15
+  EPI_CE_BWD_ROW = 15, // C(bf16) = (exp(acc - lse[row]) - [col==target[row]]) * row_scale[row]: EPI_CE_BWD with a per-row factor in place of
+                       // 1 / count (the per-sequence likelihood gradient, launch_ce_seq_bwd writes lse and row_scale)
+  EPI_COUNT = 16
 };
 
 struct GemmArgs {
@@ -96,6 +98,8 @@ struct GemmArgs {
   long long chain_ldw;
   bf16_t* chain_C;
   long long chain_ldc;
+  // EPI_CE_BWD_ROW
+  const float* row_scale;   // [M]: the factor of row m's (softmax - onehot); 0 for a row without target
 };
 
 int launch_gemm_nt(const GemmArgs& a, int a_f32, int epi, hipStream_t s);
@@ -352,6 +356,11 @@ int launch_ce_finish(const float2* partial, int tiles_n, const bf16_t* a, long l
 // b: b * T .. b * T + T, or off[b] .. off[b + 1] when off is given (packed rows, target = the packed targets)
 int launch_ce_seq(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,
                   const long long* target, const int* off, float* nll, int B, int T, int C, int V, hipStream_t s);
+// the same sums (same reduction order: nll is bit-identical) + what the per-sequence backward reads (EPI_CE_BWD_ROW): lse[row] of every row and
+// row_scale[row] = weights[b] (null: 1) for the rows of sequence b that have a target, 0 for the others
+int launch_ce_seq_bwd(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,
+                      const long long* target, const int* off, const float* weights, float* nll, float* lse, float* row_scale, int B, int T,
+                      int C, int V, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // E(3)-GNN kernels (gnn.hip)

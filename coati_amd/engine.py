@@ -393,6 +393,36 @@ class Engine:
         self._shape = None
         return nll
 
+    def score_grad(self, tokens, y_next, h_clip, weights=None, rows=None):
+        """(nll [B], dh_clip [B, E]) f32: the per-sequence NLL of score(tokens, y_next, h_clip=h_clip) -- the same bits -- and
+        dh_clip[b] = weights[b] * d nll[b] / d h_clip[b] (weights [B] f32, None = ones), through the decoder pass and the special-token
+        head, summed over row b's [UNK] positions (coati_engine_score_grad).  The model is a constant: nothing of params / grads / Adam
+        state is written, a train=False engine serves, and backward() afterwards is refused as after score().  rows as in score() (only
+        rows2 matters).  Stays on the device (no sync); COATI2 and fp8 engines raise."""
+        B, T2 = tokens.shape
+        for t in (tokens, y_next):
+            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.shape[0] == B
+        assert y_next.shape == tokens.shape
+        h_clip = h_clip.to(self.device, torch.float32).contiguous()
+        assert h_clip.shape == (B, self.cfg.n_embd_common)
+        if weights is not None:
+            weights = weights.to(self.device, torch.float32).contiguous()
+            assert weights.shape == (B,)
+        self._ensure_workspace(B, 1, T2, 1)
+        r2 = 0
+        if rows is not None and PACK_ROWS:
+            r2 = int((rows.tolist() if isinstance(rows, torch.Tensor) else rows)[1])
+            if r2 <= 0:
+                r2 = 0
+        nll = torch.empty(B, device=self.device, dtype=torch.float32)
+        dh = torch.empty(B, self.cfg.n_embd_common, device=self.device, dtype=torch.float32)
+        self._keep = (h_clip, tokens, y_next, weights)
+        _lib.check(self.l.coati_engine_score_grad(self.h, ptr(self.workspace), self.workspace.numel(), B, T2, ptr(h_clip), ptr(tokens),
+                                                  ptr(y_next), r2, ptr(weights), ptr(nll), ptr(dh), ptr(self.scal), stream()),
+                   "coati_engine_score_grad")
+        self._shape = None
+        return nll, dh
+
     def logits(self):
         if getattr(self, "_packed", False):
             raise RuntimeError("logits(): the last forward ran on packed rows; call forward(..., rows=None)")

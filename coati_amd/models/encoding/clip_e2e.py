@@ -392,9 +392,10 @@ class e3gnn_smiles_clip_e2e(nn.Module):
                                                      inv_temp=inv_temp, k=k, generator=generator)
         return [tokenizer.decode(t, special=keep_special, de_fim=de_fim) for t in generation]
 
-    def _score(self, tokens, y_next, h_clip=None, raw_tokens=None):
+    def _score(self, tokens, y_next, h_clip=None, raw_tokens=None, differentiable=False):
         """Engine.score on host-built rows: columns behind every row's last live position are dropped (their targets are -1 and,
-        under causal attention, they change no earlier logit) and the passes run on packed rows."""
+        under causal attention, they change no earlier logit) and the passes run on packed rows.  differentiable (with h_clip): the
+        same call through HclipLikelihood, so that the result carries the gradient w.r.t. h_clip."""
         from ...synthetic import packed_lengths
         l_raw, l_tok = packed_lengths(raw_tokens if raw_tokens is not None else tokens, tokens, y_next)   # (l_raw unused without raw_tokens)
         T2 = max(int(l_tok.max()), 1)
@@ -403,7 +404,11 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         if raw_tokens is not None:
             raw_tokens = self._tok(_trim_columns(raw_tokens, max(int(l_raw.max()), 1)))
         eng = self.engine
-        nll = eng.score(self._tok(tokens), self._tok(y_next), h_clip=h_clip, raw_tokens=raw_tokens, rows=rows)
+        if differentiable:
+            from ..autograd_funs.likelihood import HclipLikelihood
+            nll = HclipLikelihood.apply(h_clip, eng, self._tok(tokens), self._tok(y_next), rows)
+        else:
+            nll = eng.score(self._tok(tokens), self._tok(y_next), h_clip=h_clip, raw_tokens=raw_tokens, rows=rows)
         err = int(eng.scal[6:7].view(torch.int32).item())
         if err & 1:
             raise RuntimeError("Some smiles in the batch do not have stop tokens. Did some tokenizations fail?")
@@ -411,19 +416,25 @@ class e3gnn_smiles_clip_e2e(nn.Module):
             raise RuntimeError("packed rows: the row counts passed to score() differ from what the device found in the tokens")
         return nll
 
-    @torch.no_grad()
     def hclip_and_tokens_to_likelihood(self, hclip: torch.Tensor, smiles, tokenizer) -> torch.Tensor:
         """clip_e2e.py:634-665: summed NLL of [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smiles>[STOP] with hclip's special token at [UNK].
-        hclip [E] + one SMILES string -> [1] (the reference's form); hclip [B, E] + a list of B strings -> [B] in one engine call."""
+        hclip [E] + one SMILES string -> [1] (the reference's form); hclip [B, E] + a list of B strings -> [B] in one engine call.
+
+        As in the reference the result is differentiable w.r.t. hclip: with grad mode on and hclip.requires_grad it carries a grad_fn
+        (HclipLikelihood) and .backward() leaves d NLL / d hclip in hclip.grad.  The gradient reaches hclip ONLY: the model's parameters
+        are constants of this call (the engine owns them as flat buffers outside autograd).  Otherwise nothing is recorded and the
+        values are those of the plain scoring call, bit for bit."""
         self._sync_tokens(tokenizer)
         single = isinstance(smiles, str)
-        h = hclip.to(self.device, torch.float32)
-        if single:
-            assert h.dim() == 1, "one SMILES string goes with one embedding [E]"
-            smiles, h = [smiles], h.unsqueeze(0)
-        assert h.dim() == 2 and h.shape[0] == len(smiles), "hclip [B, E] needs a list of B SMILES strings"
-        tokens, y_next = hclip_likelihood_tokens(list(smiles), tokenizer)
-        return self._score(tokens, y_next, h_clip=h.contiguous())
+        want_grad = torch.is_grad_enabled() and hclip.requires_grad
+        with torch.set_grad_enabled(want_grad):
+            h = hclip.to(self.device, torch.float32)
+            if single:
+                assert h.dim() == 1, "one SMILES string goes with one embedding [E]"
+                smiles, h = [smiles], h.unsqueeze(0)
+            assert h.dim() == 2 and h.shape[0] == len(smiles), "hclip [B, E] needs a list of B SMILES strings"
+            tokens, y_next = hclip_likelihood_tokens(list(smiles), tokenizer)
+            return self._score(tokens, y_next, h_clip=h.contiguous(), differentiable=want_grad)
 
     @torch.no_grad()
     def batch_smiles_to_s2s_likelihood(self, smiles: List[str], tokenizer):

@@ -426,6 +426,17 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
                        const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
                        float* scal, void* stream);
 
+/* The likelihood's gradient w.r.t. the injected embedding (in the reference: autograd through hclip_and_tokens_to_likelihood,
+ * clip_e2e.py:634-665).  nll[b] is bit for bit what coati_engine_score(h_clip = ...) returns for the same arguments;
+ * dh_clip[b] = weights[b] * d nll[b] / d h_clip[b] ([B,E] f32; weights [B] f32 or null = ones), through the decoder pass and the
+ * special-token head (SiLU + Linear, or the identity without token_mlp), summed over every [UNK] position of row b.  rows2 > 0: packed
+ * decoder rows as in coati_engine_score.  The model is a constant: no parameter gradient is formed; parameters, gradient buffer and Adam
+ * state are not written and a forward-only engine (no gradient buffer bound) serves.  Nothing is kept for coati_engine_backward, which
+ * refuses to run after it.  COATI2 engines and use_fp8 engines are refused.  Workspace as for coati_engine_score. */
+int coati_engine_score_grad(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_clip,
+                            const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll, float* dh_clip,
+                            float* scal, void* stream);
+
 /* encode_tokens on PACKED rows (coati_engine_encode's token tower, COATI1 and COATI2): the encoder pass runs on the concatenation of the
  * rows' real prefixes, rows1 = sum over rows of (1 + last non-[PAD] position) of raw_tokens [B,T1], counted by the caller on the host.
  * h_smiles [B,E] f32 equals the padded encode's to bf16 rounding.  scal[6] bit 0: a row without exactly one [STOP]; bit 1: rows1
