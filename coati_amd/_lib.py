@@ -52,6 +52,7 @@ _SIGS = {
     "coati_bad_rows": [P, P, I, I, P],
     "coati_silu": [P, P, L, P],
     "coati_swiglu": [P, L, P, L, I, I, P],
+    "coati_swiglu_bwd": [P, L, P, L, P, L, I, I, P],
     "coati_group_mean_rows": [P, L, P, P, P, P, I, I, P],
     "coati_attn_decode": [P, P, P, I, I, I, I, P],
     "coati_attn_decode_hs": [P, P, P, I, I, I, I, I, P],
@@ -102,6 +103,8 @@ _SIGS = {
     "coati_engine_encode": [P, P, L, I, I, I, P, P, P, P, P, P, P],
     "coati_engine_score": [P, P, L, I, I, I, P, P, P, P, L, L, P, P, P],
     "coati_engine_score_grad": [P, P, L, I, I, P, P, P, L, P, P, P, P, P],
+    "coati_engine_score_coati2": [P, P, L, I, I, I, P, P, P, P, L, L, P, P, P],
+    "coati_engine_score_grad_coati2": [P, P, L, I, I, P, P, P, L, P, P, P, P, P],
     "coati_engine_encode_packed": [P, P, L, I, I, P, L, P, P, P],
     "coati_engine_decoder_logits": [P, P, L, I, I, P, P, P, L, P, P],
     "coati_engine_infonce": [P, P, P, P, P, P, I, I, I, F, P, P, P, P],

@@ -222,6 +222,9 @@ int coati_silu(const float* x, float* y, int64_t n, void* stream) { return launc
 int coati_swiglu(const float* u, int64_t ldu, float* g, int64_t ldg, int B, int N, void* stream) {
   return launch_swiglu(u, ldu, g, ldg, B, N, S_(stream));
 }
+int coati_swiglu_bwd(const float* u, int64_t ldu, const float* dg, int64_t lddg, float* du, int64_t lddu, int B, int N, void* stream) {
+  return launch_swiglu_bwd(u, ldu, dg, lddg, du, lddu, B, N, S_(stream));
+}
 int coati_group_mean_rows(const float* x, int64_t ldx, const int32_t* off, const float* w, const float* fallback, float* out, int G, int E,
                           void* stream) {
   return launch_group_mean_rows(x, ldx, off, w, fallback, out, G, E, S_(stream));

@@ -133,6 +133,7 @@ struct coati_engine {
   int enc_to_coati = -1;
   struct Coati2Head { int64_t lnw = 0, lnb = 0, w1 = 0, b1 = 0, w2 = 0, b2 = 0; bool residual = false; } c2s, c2t;
   float* c2_u = nullptr;   // [B, 2E] scratch: the first Linear of a SwiGLU head
+  float* c2_du = nullptr;  // [B, 2E] its gradient (coati_engine_score_grad_coati2)
   // bound buffers
   float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;
   bf16_t* S = nullptr;
@@ -750,7 +751,7 @@ size_t carve(coati_engine* e, Arena& ar, int B_, int T1_, int T2_, int A_, int B
   e->ones = ar.take<float>(B);
   e->stop_pos = ar.take<int>(B);
   e->err_flag = ar.take<int>(4);
-  if (e->enc_to_coati >= 0) e->c2_u = ar.take<float>((size_t)B * 2 * E);
+  if (e->enc_to_coati >= 0) { e->c2_u = ar.take<float>((size_t)B * 2 * E); e->c2_du = ar.take<float>((size_t)B * 2 * E); }
   // lm head
   const int tiles_v = cdiv(c.n_tok, 64);   // one (max, sum) pair per 64 columns: either GEMM kernel fits
   e->ce_partial = ar.take<float2>(M2 * tiles_v);
@@ -1913,21 +1914,27 @@ int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_
 // the caller's h_clip, or smiles_to_clip of the encoder pass over raw_tokens --, the special-token head, the decoder pass with that
 // injection, lm_head as CE partials and their per-sequence sums.  No point encoder, no logits, nothing saved for a backward
 // (have_fwd stays false).  rows2 > 0: the decoder pass on packed rows (rows1 > 0 with it for the encoder pass over raw_tokens).
-// What coati_engine_score and coati_engine_score_grad share: the argument checks (`entry`: the caller's name in the messages), the
-// prologue and the forward up to the per-sequence sums.  for_grad: the sums also leave lse and the per-row factors (weights: [B] or null =
-// ones) that the dlogits product of the backward reads; the transformer's saves are in the workspace either way.
-static int score_forward(coati_engine* e, const char* entry, void* workspace, int64_t workspace_bytes, int B, int T1, int T2,
+//
+// score_forward is what the four scoring entries share: the argument checks (`entry`: the caller's name in the messages), the prologue and the forward
+// up to the per-sequence sums.  coati2: the COATI2 entries -- the engine must be one of coati_engine_create_coati2, the embedding of the
+// encoder pass is smiles_to_coati and the injected token is coati_to_token (SwiGLUResNet(E, E)) instead of the special-token head; the
+// COATI1 entries refuse such an engine.  for_grad: the sums also leave lse and the per-row factors (weights: [B] or null = ones) that the
+// dlogits product of the backward reads; the transformer's saves are in the workspace either way.  Every refusal is decided on the host
+// before the workspace is carved or anything is enqueued.
+static int score_forward(coati_engine* e, const char* entry, bool coati2, void* workspace, int64_t workspace_bytes, int B, int T1, int T2,
                          const int64_t* raw_tokens, const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1,
                          int64_t rows2, float* nll, float* scal, bool for_grad, const float* weights, hipStream_t s) {
-  COATI_CHECK_ARG(e && e->P && e->S && workspace && tokens && y_next && nll && scal, "%s: engine not bound / null argument", entry);
-  COATI_CHECK_ARG((raw_tokens != nullptr) != (h_clip != nullptr), "%s: give exactly one of raw_tokens / h_clip", entry);
-  COATI_CHECK_ARG(e->enc_to_coati < 0, "%s: a COATI2 engine is inference-only (COATI1's scoring head)", entry);
+  COATI_CHECK_ARG(e && workspace && tokens && y_next && nll && scal, "%s: engine not bound / null argument", entry);
+  COATI_CHECK_ARG((raw_tokens != nullptr) != (h_clip != nullptr), "%s: give exactly one of raw_tokens / %s", entry, coati2 ? "h_coati" : "h_clip");
+  if (coati2) COATI_CHECK_ARG(e->enc_to_coati >= 0, "%s: not a COATI2 engine (coati_engine_create_coati2)", entry);
+  else COATI_CHECK_ARG(e->enc_to_coati < 0, "%s: a COATI2 engine is inference-only (COATI1's scoring head)", entry);
   const coati_config& c = e->cfg;
   if (!raw_tokens) { T1 = 1; rows1 = 0; }
   COATI_CHECK_SHAPE(B > 0 && T1 > 0 && T2 > 0 && T1 <= c.n_seq && T2 <= c.n_seq, "%s: unsupported shape B=%d T1=%d T2=%d (n_seq=%d)", entry,
                     B, T1, T2, c.n_seq);
   COATI_CHECK_SHAPE(rows1 >= 0 && rows2 >= 0 && rows1 <= (int64_t)B * T1 && rows2 <= (int64_t)B * T2 && (!raw_tokens || (rows1 > 0) == (rows2 > 0)),
                     "%s: packed row counts %lld / %lld do not fit %d x %d / %d x %d", entry, (long long)rows1, (long long)rows2, B, T1, B, T2);
+  COATI_CHECK_ARG(e->P && e->S, "%s: engine not bound / null argument", entry);
   const int C = c.n_hidden_xformer;
   COATI_TRY(begin_call(e, entry, workspace, workspace_bytes, B, T1, T2, 1, scal));
   e->p1.idx = reinterpret_cast<const long long*>(raw_tokens);
@@ -1942,11 +1949,17 @@ static int score_forward(coati_engine* e, const char* entry, void* workspace, in
     COATI_TRY(token_tower_fwd(e, e->h_smiles, s));
     hclip = e->h_smiles;
   }
-  // ---- special token: point_clip_to_special_tokens (clip_e2e.py:432-437) ----
+  // ---- special token: point_clip_to_special_tokens (clip_e2e.py:432-437), COATI2: coati_to_token (its LayerNorm's statistics and
+  // the first Linear's output stay in hs_mean / hs_rstd / hs_ln / c2_u for coati2_token_head_bwd) ----
   const float* inj = nullptr;
-  SgemmBatch sb;
-  COATI_TRY(special_token_add(e, sb, hclip, e->sb, e->stok, &inj, s));
-  COATI_TRY(launch_sgemm_batch(sb, s));
+  if (coati2) {
+    COATI_TRY(coati2_head_fwd(e, e->c2t, hclip, e->stok, B, s));
+    inj = e->stok;
+  } else {
+    SgemmBatch sb;
+    COATI_TRY(special_token_add(e, sb, hclip, e->sb, e->stok, &inj, s));
+    COATI_TRY(launch_sgemm_batch(sb, s));
+  }
   // ---- decoder pass with the injection, lm_head partials, per-sequence sums (forward_with_replacement + cross_entropy) ----
   COATI_TRY(xformer_fwd(e, e->p2, inj, s));
   int tiles_v = 0;
@@ -1963,9 +1976,30 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
                        const float* h_clip, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
                        float* scal, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  COATI_TRY(score_forward(e, "engine_score", workspace, workspace_bytes, B, T1, T2, raw_tokens, h_clip, tokens, y_next, rows1, rows2, nll, scal,
+  COATI_TRY(score_forward(e, "engine_score", false, workspace, workspace_bytes, B, T1, T2, raw_tokens, h_clip, tokens, y_next, rows1, rows2, nll, scal,
                           false, nullptr, s));
   return publish_errors(e, scal, s);
+}
+
+// The backward that the two score_grad entries share, behind score_forward(for_grad = true): dlogits with the per-row factor, then the
+// decoder pass for its input gradients only; the [UNK] rows' gradient sums into dcliptok [B, E]
+static int score_backward_to_token(coati_engine* e, hipStream_t s) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, E = c.n_embd_common, M2 = e->p2.M, B = e->B;
+  // ---- dlogits[row] = (softmax - onehot) * weights[seq(row)], 0 on rows without target ----
+  {
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = M2; a.N = c.n_tok; a.K = C;
+    a.C = e->dlogits; a.ldc = e->Vpad; a.n_store = e->Vpad; a.lse = e->ce_lse; a.target = e->p2.packed ? e->p2.ypk : e->y_next;
+    a.row_scale = e->ce_rowscale;
+    ProfScope ps(e, SITE_LMHEAD_DLOGITS, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2 + (double)M2 * e->Vpad * 2);
+    COATI_TRY(gemm_rows(a, 0, EPI_CE_BWD_ROW, s));
+  }
+  // ---- decoder pass, input gradients only; the [UNK] rows' gradient sums into dcliptok ----
+  HIPCHK(hipMemsetAsync(e->dcliptok, 0, (size_t)B * E * sizeof(float), s));
+  COATI_TRY(xformer_bwd(e, e->p2, e->da, 0, e->dcliptok, s, -1, 0, e->dlogits, true));
+  return COATI_OK;
 }
 
 // The likelihood's gradient w.r.t. the injected embedding (the reference reaches it by autograd through clip_e2e.py:634-665):
@@ -1981,23 +2015,11 @@ int coati_engine_score_grad(coati_engine* e, void* workspace, int64_t workspace_
   COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_score_grad: a COATI2 engine has no likelihood head");
   COATI_CHECK_ARG(!e->cfg.use_fp8, "engine_score_grad: not available on an fp8 engine (the inputs-only backward runs the bf16 products)");
   hipStream_t s = (hipStream_t)stream;
-  COATI_TRY(score_forward(e, "engine_score_grad", workspace, workspace_bytes, B, 1, T2, nullptr, h_clip, tokens, y_next, 0, rows2, nll, scal, true,
+  COATI_TRY(score_forward(e, "engine_score_grad", false, workspace, workspace_bytes, B, 1, T2, nullptr, h_clip, tokens, y_next, 0, rows2, nll, scal, true,
                           weights, s));
   const coati_config& c = e->cfg;
-  const int C = c.n_hidden_xformer, E = c.n_embd_common, M2 = e->p2.M;
-  // ---- dlogits[row] = (softmax - onehot) * weights[seq(row)], 0 on rows without target ----
-  {
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = M2; a.N = c.n_tok; a.K = C;
-    a.C = e->dlogits; a.ldc = e->Vpad; a.n_store = e->Vpad; a.lse = e->ce_lse; a.target = e->p2.packed ? e->p2.ypk : e->y_next;
-    a.row_scale = e->ce_rowscale;
-    ProfScope ps(e, SITE_LMHEAD_DLOGITS, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2 + (double)M2 * e->Vpad * 2);
-    COATI_TRY(gemm_rows(a, 0, EPI_CE_BWD_ROW, s));
-  }
-  // ---- decoder pass, input gradients only; the [UNK] rows' gradient sums into dcliptok ----
-  HIPCHK(hipMemsetAsync(e->dcliptok, 0, (size_t)B * E * sizeof(float), s));
-  COATI_TRY(xformer_bwd(e, e->p2, e->da, 0, e->dcliptok, s, -1, 0, e->dlogits, true));
+  const int E = c.n_embd_common;
+  COATI_TRY(score_backward_to_token(e, s));
   // ---- point_clip_to_special_tokens backward to dh alone: dh = (dtok W) * SiLU'(h) ; nn.Identity: dh = dtok ----
   if (c.token_mlp) {
     SgemmBatch sb;
@@ -2007,6 +2029,48 @@ int coati_engine_score_grad(coati_engine* e, void* workspace, int64_t workspace_
   } else {
     HIPCHK(hipMemcpyAsync(dh_clip, e->dcliptok, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
+  return publish_errors(e, scal, s);
+}
+
+// COATI2 likelihood scoring: coati_engine_score with COATI2's heads.  The embedding is the caller's h_coati or smiles_to_coati of the
+// encoder pass over raw_tokens (transformer_only.py:108-110, any of the three variants); coati_to_token (SwiGLUResNet(E, E)) of it is
+// injected at the [UNK] positions (what hcoati_to_2d decodes from, transformer_only.py:144, 177); the rest is score_forward.
+int coati_engine_score_coati2(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
+                              const float* h_coati, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
+                              float* scal, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COATI_TRY(score_forward(e, "engine_score_coati2", true, workspace, workspace_bytes, B, T1, T2, raw_tokens, h_coati, tokens, y_next, rows1, rows2,
+                          nll, scal, false, nullptr, s));
+  return publish_errors(e, scal, s);
+}
+
+// coati_to_token's backward to its input alone, behind coati2_head_fwd(e->c2t, ...) of the same call (hs_ln holds LN(h), hs_mean / hs_rstd
+// its statistics, c2_u the first Linear's output): for x -> LN -> Linear(E -> 2E) -> SwiGLU -> Linear(E -> E) + x and dtok [B, E],
+// dsa = dtok W2 ; du = swiglu_bwd(u, dsa) ; dln = du W1 ; dh = dtok + LN-backward(dln).  Exact-f32 products, no parameter gradient
+static int coati2_token_head_bwd(coati_engine* e, const float* h, const float* dtok, float* dh, int B, hipStream_t s) {
+  const int E = e->cfg.n_embd_common;
+  const coati_engine::Coati2Head& t = e->c2t;
+  const float* P = e->P;
+  COATI_TRY(launch_sgemm(dtok, E, 1, P + t.w2, E, 1, e->dsa, E, B, E, E, nullptr, 1.f, 0, s));              // dsa[b,k] = sum_n dtok[b,n] W2[n,k]
+  COATI_TRY(launch_swiglu_bwd(e->c2_u, 2 * E, e->dsa, E, e->c2_du, 2 * E, B, E, s));
+  COATI_TRY(launch_sgemm(e->c2_du, 2 * E, 1, P + t.w1, E, 1, e->dhs_ln, E, B, E, 2 * E, nullptr, 1.f, 0, s));  // dln[b,k] = sum_n du[b,n] W1[n,k]
+  return launch_layernorm_bwd(e->dhs_ln, 1, E, h, E, 0, e->hs_mean, e->hs_rstd, P + t.lnw, dtok, dh, nullptr, nullptr, nullptr, nullptr, B, E, s);
+}
+
+// The COATI2 likelihood's gradient w.r.t. the embedding: coati_engine_score_grad with COATI2's token head.  nll as
+// coati_engine_score_coati2(h_coati = ...) gives it (the same bits), dh_coati[b] = weights[b] * d nll[b] / d h_coati[b] through the decoder
+// pass and coati_to_token, summed over the [UNK] positions of row b.  Launches: the scoring forward; dlogits with the per-row factor; the
+// lm_head's and the layers' input gradients; the [UNK] rows' gather; coati2_token_head_bwd.  The model is a constant: no parameter
+// gradient is formed and nothing of the engine's parameters moves (COATI2 engines are forward-only); have_fwd stays false.
+int coati_engine_score_grad_coati2(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_coati,
+                                   const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll,
+                                   float* dh_coati, float* scal, void* stream) {
+  COATI_CHECK_ARG(e && h_coati && dh_coati, "engine_score_grad_coati2: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  COATI_TRY(score_forward(e, "engine_score_grad_coati2", true, workspace, workspace_bytes, B, 1, T2, nullptr, h_coati, tokens, y_next, 0, rows2, nll,
+                          scal, true, weights, s));
+  COATI_TRY(score_backward_to_token(e, s));
+  COATI_TRY(coati2_token_head_bwd(e, h_coati, e->dcliptok, dh_coati, B, s));
   return publish_errors(e, scal, s);
 }
 

@@ -402,6 +402,8 @@ int launch_silu_fwd(const float* x, float* y, long long n, hipStream_t s);
 int launch_silu_bwd(const float* x, const float* dy, float* dx, long long n, int accumulate, hipStream_t s);
 // g[b, j] = u[b, j] * silu(u[b, N + j]), b < B, j < N (SwiGLU: the first half of u's columns is the value, the second the gate)
 int launch_swiglu(const float* u, long long ldu, float* g, long long ldg, int B, int N, hipStream_t s);
+// its backward: u as above, dg [B, N] -> du [B, 2N] = [dg * silu(gate) | dg * x * silu'(gate)]
+int launch_swiglu_bwd(const float* u, long long ldu, const float* dg, long long lddg, float* du, long long lddu, int B, int N, hipStream_t s);
 // out[g] = sum_{i in [off[g], off[g+1])} w[i] x[i] / sum w[i] (w null: 1), an empty group = fallback[g]; [G, E] rows, fixed order
 int launch_group_mean_rows(const float* x, long long ldx, const int* off, const float* w, const float* fallback, float* out, int G, int E,
                            hipStream_t s);

@@ -45,6 +45,52 @@ int launch_swiglu(const float* u, long long ldu, float* g, long long ldg, int B,
   return COATI_OK;
 }
 
+// SwiGLU's backward (the token head of coati_engine_score_grad_coati2): for g = x * silu(q), u = [x | q] each half N wide as above and
+// dg [B, N], du = [dg * silu(q) | dg * x * silu'(q)], silu'(q) = s (1 + q (1 - s)), s = sigmoid(q).  One thread owns both halves of its
+// columns, so q is read and its sigmoid formed once.  V4 as in swiglu_kernel (N, the three strides and base addresses multiples of 4 floats)
+__device__ __forceinline__ void swiglu_bwd_f(float x, float q, float dg, float& dx, float& dq) {
+  const float sg = sigmoid_f(q);
+  dx = dg * (q * sg);
+  dq = dg * x * (sg * (1.0f + q * (1.0f - sg)));
+}
+template <bool V4>
+__global__ __launch_bounds__(256) void swiglu_bwd_kernel(const float* __restrict__ u, long long ldu, const float* __restrict__ dg, long long lddg,
+                                                         float* __restrict__ du, long long lddu, int B, int N) {
+  const int W = V4 ? N / 4 : N;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * W) return;
+  const long long b = i / W;
+  const int j = (int)(i - b * W);
+  const float* r = u + b * ldu;
+  float* o = du + b * lddu;
+  if constexpr (V4) {
+    const float4 x = *reinterpret_cast<const float4*>(r + 4 * j);
+    const float4 q = *reinterpret_cast<const float4*>(r + N + 4 * j);
+    const float4 d = *reinterpret_cast<const float4*>(dg + b * lddg + 4 * j);
+    float4 dx, dq;
+    swiglu_bwd_f(x.x, q.x, d.x, dx.x, dq.x);
+    swiglu_bwd_f(x.y, q.y, d.y, dx.y, dq.y);
+    swiglu_bwd_f(x.z, q.z, d.z, dx.z, dq.z);
+    swiglu_bwd_f(x.w, q.w, d.w, dx.w, dq.w);
+    *reinterpret_cast<float4*>(o + 4 * j) = dx;
+    *reinterpret_cast<float4*>(o + N + 4 * j) = dq;
+  } else {
+    swiglu_bwd_f(r[j], r[N + j], dg[b * lddg + j], o[j], o[N + j]);
+  }
+}
+int launch_swiglu_bwd(const float* u, long long ldu, const float* dg, long long lddg, float* du, long long lddu, int B, int N, hipStream_t s) {
+  COATI_CHECK_ARG(u && dg && du, "swiglu_bwd: null operand");
+  COATI_CHECK_SHAPE(B > 0 && N > 0 && ldu >= 2LL * N && lddg >= N && lddu >= 2LL * N, "swiglu_bwd: bad shape B=%d N=%d ldu=%lld lddg=%lld lddu=%lld", B, N,
+                    ldu, lddg, lddu);
+  const bool v4 = N % 4 == 0 && ldu % 4 == 0 && lddg % 4 == 0 && lddu % 4 == 0 && reinterpret_cast<uintptr_t>(u) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(dg) % 16 == 0 && reinterpret_cast<uintptr_t>(du) % 16 == 0;
+  const long long n = (long long)B * (v4 ? N / 4 : N);
+  if (v4) hipLaunchKernelGGL(swiglu_bwd_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, ldu, dg, lddg, du, lddu, B, N);
+  else hipLaunchKernelGGL(swiglu_bwd_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, ldu, dg, lddg, du, lddu, B, N);
+  COATI_LAUNCH_CHECK("swiglu_bwd");
+  return COATI_OK;
+}
+
 // Segmented weighted mean (batched purification: the embeddings of a vector's distinct decodes, weighted by multiplicity):
 // out[g] = sum_{i in [off[g], off[g+1])} w[i] x[i] / sum w[i]; an empty group copies fallback[g].  One workgroup per group, each lane
 // owns whole columns and runs through the group's rows in index order: no atomics, no cross-lane reduction, the same bits every call

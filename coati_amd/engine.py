@@ -363,21 +363,20 @@ class Engine:
         self._shape = None
         return out
 
-    def score(self, tokens, y_next, h_clip=None, raw_tokens=None, rows=None):
-        """Per-sequence autoregressive NLL [B] f32 of `tokens` [B, T2] against `y_next` [B, T2] (-1 = ignored), with the special-token
-        head's image of an embedding injected at the [UNK] positions (clip_e2e.py:634-742): either the caller's `h_clip` [B, E] or
-        encode_tokens(`raw_tokens` [B, T1]).  No point encoder, no logits; the sums are deterministic.  rows = (rows1, rows2) from
-        coati_amd.synthetic.packed_rows on host tensors: the transformer passes on packed rows (rows1 only matters with raw_tokens).
-        Stays on the device (no sync): error_bits() / losses() report a row without [STOP] or a packed-row mismatch."""
-        assert (h_clip is None) != (raw_tokens is None), "score: give exactly one of h_clip / raw_tokens"
+    def _score_args(self, tokens, y_next, h, raw_tokens, weights, rows):
+        """What the scoring calls share: the checks of the token tensors, the embedding / weights as contiguous f32 device tensors, the
+        workspace for (B, T1, T2) and the packed row counts (0, 0 = padded rows).  Returns (B, T1, T2, h, weights, r1, r2)."""
         B, T2 = tokens.shape
         T1 = raw_tokens.shape[1] if raw_tokens is not None else 1
         for t in (tokens, y_next) + ((raw_tokens,) if raw_tokens is not None else ()):
             assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.shape[0] == B
         assert y_next.shape == tokens.shape
-        if h_clip is not None:
-            h_clip = h_clip.to(self.device, torch.float32).contiguous()
-            assert h_clip.shape == (B, self.cfg.n_embd_common)
+        if h is not None:
+            h = h.to(self.device, torch.float32).contiguous()
+            assert h.shape == (B, self.cfg.n_embd_common)
+        if weights is not None:
+            weights = weights.to(self.device, torch.float32).contiguous()
+            assert weights.shape == (B,)
         self._ensure_workspace(B, T1, T2, 1)
         r1 = r2 = 0
         if rows is not None and PACK_ROWS:
@@ -386,12 +385,35 @@ class Engine:
                 r1 = 0
             if r2 <= 0 or (raw_tokens is not None and r1 <= 0):
                 r1 = r2 = 0
+        return B, T1, T2, h, weights, r1, r2
+
+    def _score(self, entry, tokens, y_next, h, raw_tokens, rows):
+        B, T1, T2, h, _, r1, r2 = self._score_args(tokens, y_next, h, raw_tokens, None, rows)
         nll = torch.empty(B, device=self.device, dtype=torch.float32)
-        self._keep = (raw_tokens, h_clip, tokens, y_next)
-        _lib.check(self.l.coati_engine_score(self.h, ptr(self.workspace), self.workspace.numel(), B, T1, T2, ptr(raw_tokens), ptr(h_clip),
-                                             ptr(tokens), ptr(y_next), r1, r2, ptr(nll), ptr(self.scal), stream()), "coati_engine_score")
+        self._keep = (raw_tokens, h, tokens, y_next)
+        _lib.check(getattr(self.l, entry)(self.h, ptr(self.workspace), self.workspace.numel(), B, T1, T2, ptr(raw_tokens), ptr(h), ptr(tokens),
+                                          ptr(y_next), r1, r2, ptr(nll), ptr(self.scal), stream()), entry)
         self._shape = None
         return nll
+
+    def _score_grad(self, entry, tokens, y_next, h, weights, rows):
+        B, _, T2, h, weights, _, r2 = self._score_args(tokens, y_next, h, None, weights, rows)
+        nll = torch.empty(B, device=self.device, dtype=torch.float32)
+        dh = torch.empty(B, self.cfg.n_embd_common, device=self.device, dtype=torch.float32)
+        self._keep = (h, tokens, y_next, weights)
+        _lib.check(getattr(self.l, entry)(self.h, ptr(self.workspace), self.workspace.numel(), B, T2, ptr(h), ptr(tokens), ptr(y_next), r2,
+                                          ptr(weights), ptr(nll), ptr(dh), ptr(self.scal), stream()), entry)
+        self._shape = None
+        return nll, dh
+
+    def score(self, tokens, y_next, h_clip=None, raw_tokens=None, rows=None):
+        """Per-sequence autoregressive NLL [B] f32 of `tokens` [B, T2] against `y_next` [B, T2] (-1 = ignored), with the special-token
+        head's image of an embedding injected at the [UNK] positions (clip_e2e.py:634-742): either the caller's `h_clip` [B, E] or
+        encode_tokens(`raw_tokens` [B, T1]).  No point encoder, no logits; the sums are deterministic.  rows = (rows1, rows2) from
+        coati_amd.synthetic.packed_rows on host tensors: the transformer passes on packed rows (rows1 only matters with raw_tokens).
+        Stays on the device (no sync): error_bits() / losses() report a row without [STOP] or a packed-row mismatch."""
+        assert (h_clip is None) != (raw_tokens is None), "score: give exactly one of h_clip / raw_tokens"
+        return self._score("coati_engine_score", tokens, y_next, h_clip, raw_tokens, rows)
 
     def score_grad(self, tokens, y_next, h_clip, weights=None, rows=None):
         """(nll [B], dh_clip [B, E]) f32: the per-sequence NLL of score(tokens, y_next, h_clip=h_clip) -- the same bits -- and
@@ -399,29 +421,20 @@ class Engine:
         head, summed over row b's [UNK] positions (coati_engine_score_grad).  The model is a constant: nothing of params / grads / Adam
         state is written, a train=False engine serves, and backward() afterwards is refused as after score().  rows as in score() (only
         rows2 matters).  Stays on the device (no sync); COATI2 and fp8 engines raise."""
-        B, T2 = tokens.shape
-        for t in (tokens, y_next):
-            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.shape[0] == B
-        assert y_next.shape == tokens.shape
-        h_clip = h_clip.to(self.device, torch.float32).contiguous()
-        assert h_clip.shape == (B, self.cfg.n_embd_common)
-        if weights is not None:
-            weights = weights.to(self.device, torch.float32).contiguous()
-            assert weights.shape == (B,)
-        self._ensure_workspace(B, 1, T2, 1)
-        r2 = 0
-        if rows is not None and PACK_ROWS:
-            r2 = int((rows.tolist() if isinstance(rows, torch.Tensor) else rows)[1])
-            if r2 <= 0:
-                r2 = 0
-        nll = torch.empty(B, device=self.device, dtype=torch.float32)
-        dh = torch.empty(B, self.cfg.n_embd_common, device=self.device, dtype=torch.float32)
-        self._keep = (h_clip, tokens, y_next, weights)
-        _lib.check(self.l.coati_engine_score_grad(self.h, ptr(self.workspace), self.workspace.numel(), B, T2, ptr(h_clip), ptr(tokens),
-                                                  ptr(y_next), r2, ptr(weights), ptr(nll), ptr(dh), ptr(self.scal), stream()),
-                   "coati_engine_score_grad")
-        self._shape = None
-        return nll, dh
+        return self._score_grad("coati_engine_score_grad", tokens, y_next, h_clip, weights, rows)
+
+    def score_coati2(self, tokens, y_next, h_coati=None, raw_tokens=None, rows=None):
+        """score() of a COATI2 engine (coati_engine_score_coati2): the embedding is the caller's `h_coati` [B, E] or
+        smiles_to_coati of the encoder pass over `raw_tokens` [B, T1], and coati_to_token of it is injected at the [UNK] positions.
+        Everything else as in score(); a COATI1 engine raises."""
+        assert (h_coati is None) != (raw_tokens is None), "score_coati2: give exactly one of h_coati / raw_tokens"
+        return self._score("coati_engine_score_coati2", tokens, y_next, h_coati, raw_tokens, rows)
+
+    def score_grad_coati2(self, tokens, y_next, h_coati, weights=None, rows=None):
+        """(nll [B], dh_coati [B, E]) f32 on a COATI2 engine (coati_engine_score_grad_coati2): the NLL of
+        score_coati2(tokens, y_next, h_coati=h_coati) -- the same bits -- and dh_coati[b] = weights[b] * d nll[b] / d h_coati[b] through
+        the decoder pass and coati_to_token.  Everything else as in score_grad(); a COATI1 engine raises."""
+        return self._score_grad("coati_engine_score_grad_coati2", tokens, y_next, h_coati, weights, rows)
 
     def logits(self):
         if getattr(self, "_packed", False):

@@ -103,20 +103,61 @@ def _tokenize_smiles(smi, tokenizer, prefix="[SMILES]", suffix="[STOP]", device=
 _LIKELIHOOD_PREFIX = "[CLIP][UNK][SMILES][SUFFIX][MIDDLE]"
 
 
-def hclip_likelihood_tokens(smiles: List[str], tokenizer):
-    """Host-side rows of hclip_and_tokens_to_likelihood (clip_e2e.py:638-655) for a list of SMILES: tokens
-    [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smi>[STOP] [B, T] (rows of different length end in [PAD]) and their targets (the next token;
-    [CLIP] / [PAD] / [SMILES] / [UNK] / [SUFFIX] / [MIDDLE] targets are -1).  Tokenizer errors propagate as in the reference."""
-    rows = [tokenizer.tokenize_text(_LIKELIHOOD_PREFIX + smi + "[STOP]", pad=False) for smi in smiles]
-    tokens = torch.full((len(rows), max(len(r) for r in rows)), tokenizer.pad_token, dtype=torch.long)
-    for i, r in enumerate(rows):
-        tokens[i, : len(r)] = torch.tensor(r, dtype=torch.long)
-    y_next = torch.zeros_like(tokens)
+def _masked_next_tokens(tokens, tokenizer):
+    """the next token of every position ([PAD] behind the last column: the reference's 0 is its [PAD] id, a COATI2 vocabulary has
+    another token there); [CLIP] / [PAD] / [SMILES] / [UNK] / [SUFFIX] / [MIDDLE] targets are -1 (clip_e2e.py:647-654)"""
+    y_next = torch.full_like(tokens, tokenizer.pad_token)
     y_next[:, : (tokens.shape[1] - 1)] = tokens[:, 1:].clone()
     for t in (tokenizer.clip_token, tokenizer.pad_token, tokenizer.smiles_token, tokenizer.unk_token, tokenizer.suffix_token,
               tokenizer.middle_token):
         y_next[y_next == t] = -1
-    return tokens, y_next
+    return y_next
+
+
+def _rows_to_tokens(rows, pad_token):
+    tokens = torch.full((len(rows), max(len(r) for r in rows)), pad_token, dtype=torch.long)
+    for i, r in enumerate(rows):
+        tokens[i, : len(r)] = torch.tensor(r, dtype=torch.long)
+    return tokens
+
+
+def hclip_likelihood_tokens(smiles: List[str], tokenizer):
+    """Host-side rows of hclip_and_tokens_to_likelihood (clip_e2e.py:638-655) for a list of SMILES: tokens
+    [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smi>[STOP] [B, T] (rows of different length end in [PAD]) and their targets (the next token;
+    [CLIP] / [PAD] / [SMILES] / [UNK] / [SUFFIX] / [MIDDLE] targets are -1).  Tokenizer errors propagate as in the reference."""
+    tokens = _rows_to_tokens([tokenizer.tokenize_text(_LIKELIHOOD_PREFIX + smi + "[STOP]", pad=False) for smi in smiles], tokenizer.pad_token)
+    return tokens, _masked_next_tokens(tokens, tokenizer)
+
+
+def hcoati_likelihood_tokens(smiles: List[str], tokenizer, do_suffix: bool = False):
+    """The COATI2 twin of hclip_likelihood_tokens: rows [CLIP][UNK][SMILES] (+ [SUFFIX][MIDDLE]) <smi>[STOP] -- the prompt hcoati_to_2d
+    decodes from (injection_prefix) and the string behind it -- padded with the tokenizer's [PAD], and their targets, masked alike."""
+    prefix = injection_prefix(tokenizer, "[SMILES]", do_suffix)
+    tokens = _rows_to_tokens([prefix + tokenizer.tokenize_text(smi + "[STOP]", pad=False) for smi in smiles], tokenizer.pad_token)
+    return tokens, _masked_next_tokens(tokens, tokenizer)
+
+
+def s2s_hcoati_likelihood_tokens(smiles: List[str], tokenizer, do_suffix: bool = False):
+    """The COATI2 twin of s2s_likelihood_tokens: the mask of the SMILES whose <smi>[STOP] tokenizes and fits n_seq minus the prompt, and for
+    those rows the encoder's [SMILES]<smi>[STOP] [n_ok, T1] and the decoder's rows and targets of hcoati_likelihood_tokens, all padded with
+    the tokenizer's [PAD].  No row fits: empty tensors and an all-False mask."""
+    prefix = injection_prefix(tokenizer, "[SMILES]", do_suffix)
+    room = tokenizer.n_seq - len(prefix)
+    bodies = []
+    for smi in smiles:
+        try:
+            ids = tokenizer.tokenize_text(smi + "[STOP]", pad=False, range_check=False)
+        except KeyError:
+            ids = None
+        bodies.append(ids if ids is not None and len(ids) <= room else None)
+    mask = torch.tensor([b is not None for b in bodies], dtype=torch.bool)
+    ok = [b for b in bodies if b is not None]
+    if not ok:
+        empty = torch.zeros(0, 1, dtype=torch.long)
+        return empty, empty, empty, mask
+    raw_tokens = _rows_to_tokens([[int(tokenizer.smiles_token)] + b for b in ok], tokenizer.pad_token)
+    tokens = _rows_to_tokens([prefix + b for b in ok], tokenizer.pad_token)
+    return raw_tokens, tokens, _masked_next_tokens(tokens, tokenizer), mask
 
 
 def s2s_likelihood_tokens(smiles: List[str], tokenizer):
@@ -203,6 +244,34 @@ def attach_xformer_logits(xformer: nn.Module, engine: Engine):
 
 def _trim_columns(t, n):
     return t[:, :n].contiguous()
+
+
+def score_host_rows(engine, tokens, y_next, h=None, raw_tokens=None, differentiable=False, coati2=False):
+    """Engine.score (coati2: Engine.score_coati2) on host-built rows: columns behind every row's last live position are dropped (their
+    targets are -1 and, under causal attention, they change no earlier logit) and the passes run on packed rows.  differentiable (with
+    h): the same call through HclipLikelihood (coati2: HcoatiLikelihood), so that the result carries the gradient w.r.t. h.  Raises
+    on the error word: a row without [STOP], a packed-row mismatch."""
+    from ...synthetic import packed_lengths
+    dev = engine.device
+    l_raw, l_tok = packed_lengths(raw_tokens if raw_tokens is not None else tokens, tokens, y_next, pad=engine.cfg.pad_token)   # (l_raw unused without raw_tokens)
+    T2 = max(int(l_tok.max()), 1)
+    tokens, y_next = _trim_columns(tokens, T2).to(dev, torch.long), _trim_columns(y_next, T2).to(dev, torch.long)
+    rows = (int(l_raw.sum()), int(l_tok.sum()))
+    if raw_tokens is not None:
+        raw_tokens = _trim_columns(raw_tokens, max(int(l_raw.max()), 1)).to(dev, torch.long)
+    if differentiable:
+        from ..autograd_funs.likelihood import HclipLikelihood, HcoatiLikelihood
+        nll = (HcoatiLikelihood if coati2 else HclipLikelihood).apply(h, engine, tokens, y_next, rows)
+    elif coati2:
+        nll = engine.score_coati2(tokens, y_next, h_coati=h, raw_tokens=raw_tokens, rows=rows)
+    else:
+        nll = engine.score(tokens, y_next, h_clip=h, raw_tokens=raw_tokens, rows=rows)
+    err = int(engine.scal[6:7].view(torch.int32).item())
+    if err & 1:
+        raise RuntimeError("Some smiles in the batch do not have stop tokens. Did some tokenizations fail?")
+    if err & 2:
+        raise RuntimeError("packed rows: the row counts passed to score() differ from what the device found in the tokens")
+    return nll
 
 
 class e3gnn_smiles_clip_e2e(nn.Module):
@@ -393,28 +462,8 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         return [tokenizer.decode(t, special=keep_special, de_fim=de_fim) for t in generation]
 
     def _score(self, tokens, y_next, h_clip=None, raw_tokens=None, differentiable=False):
-        """Engine.score on host-built rows: columns behind every row's last live position are dropped (their targets are -1 and,
-        under causal attention, they change no earlier logit) and the passes run on packed rows.  differentiable (with h_clip): the
-        same call through HclipLikelihood, so that the result carries the gradient w.r.t. h_clip."""
-        from ...synthetic import packed_lengths
-        l_raw, l_tok = packed_lengths(raw_tokens if raw_tokens is not None else tokens, tokens, y_next)   # (l_raw unused without raw_tokens)
-        T2 = max(int(l_tok.max()), 1)
-        tokens, y_next = _trim_columns(tokens, T2), _trim_columns(y_next, T2)
-        rows = (int(l_raw.sum()), int(l_tok.sum()))
-        if raw_tokens is not None:
-            raw_tokens = self._tok(_trim_columns(raw_tokens, max(int(l_raw.max()), 1)))
-        eng = self.engine
-        if differentiable:
-            from ..autograd_funs.likelihood import HclipLikelihood
-            nll = HclipLikelihood.apply(h_clip, eng, self._tok(tokens), self._tok(y_next), rows)
-        else:
-            nll = eng.score(self._tok(tokens), self._tok(y_next), h_clip=h_clip, raw_tokens=raw_tokens, rows=rows)
-        err = int(eng.scal[6:7].view(torch.int32).item())
-        if err & 1:
-            raise RuntimeError("Some smiles in the batch do not have stop tokens. Did some tokenizations fail?")
-        if err & 2:
-            raise RuntimeError("packed rows: the row counts passed to score() differ from what the device found in the tokens")
-        return nll
+        """score_host_rows on this model's engine (Engine.score / HclipLikelihood)"""
+        return score_host_rows(self.engine, tokens, y_next, h_clip, raw_tokens, differentiable)
 
     def hclip_and_tokens_to_likelihood(self, hclip: torch.Tensor, smiles, tokenizer) -> torch.Tensor:
         """clip_e2e.py:634-665: summed NLL of [CLIP][UNK][SMILES][SUFFIX][MIDDLE]<smiles>[STOP] with hclip's special token at [UNK].

@@ -5,7 +5,8 @@ import torch
 import torch.nn as nn
 
 from ...engine import Engine, ModelConfig
-from ..encoding.clip_e2e import _attach, attach_xformer_logits, injection_prefix, reference_parameter_order, torch_default_init
+from ..encoding.clip_e2e import (_attach, attach_xformer_logits, hcoati_likelihood_tokens, injection_prefix, reference_parameter_order,
+                                 s2s_hcoati_likelihood_tokens, score_host_rows, torch_default_init)
 
 
 class SwiGLUResNet(nn.Module):
@@ -149,3 +150,35 @@ class COATI_Smiles_Inference(nn.Module):
         if return_tokens:
             return smiles_list, generation
         return smiles_list
+
+    def hcoati_and_tokens_to_likelihood(self, h_coati: torch.Tensor, smiles, tokenizer, do_suffix=False) -> torch.Tensor:
+        """The likelihood of a SMILES string under an embedding (COATI1's hclip_and_tokens_to_likelihood, clip_e2e.py:634-665, on
+        COATI2's decoding prompt): the summed NLL of [CLIP][UNK][SMILES] (+ [SUFFIX][MIDDLE]) <smiles>[STOP] with coati_to_token(h_coati)
+        at [UNK]; [CLIP] / [PAD] / [SMILES] / [UNK] / [SUFFIX] / [MIDDLE] targets do not count.  h_coati [E] + one string -> [1];
+        h_coati [B, E] + a list of B strings -> [B] in one engine call on packed rows.
+
+        Differentiable w.r.t. h_coati: with grad mode on and h_coati.requires_grad the result carries a grad_fn (HcoatiLikelihood) and
+        .backward() leaves d NLL / d h_coati in h_coati.grad.  The gradient reaches h_coati ONLY: the model's parameters are constants
+        of this call.  Otherwise nothing is recorded and the values are those of the plain scoring call, bit for bit."""
+        self._sync_tokens(tokenizer)
+        single = isinstance(smiles, str)
+        want_grad = torch.is_grad_enabled() and h_coati.requires_grad
+        with torch.set_grad_enabled(want_grad):
+            h = h_coati.to(self.device, torch.float32)
+            if single:
+                assert h.dim() == 1, "one SMILES string goes with one embedding [E]"
+                smiles, h = [smiles], h.unsqueeze(0)
+            assert h.dim() == 2 and h.shape[0] == len(smiles), "h_coati [B, E] needs a list of B SMILES strings"
+            tokens, y_next = hcoati_likelihood_tokens(list(smiles), tokenizer, do_suffix)
+            return score_host_rows(self.engine, tokens, y_next, h=h.contiguous(), differentiable=want_grad, coati2=True)
+
+    @torch.no_grad()
+    def batch_smiles_to_s2s_likelihood(self, smiles, tokenizer, do_suffix=False):
+        """SMILES -> h_coati (encode_tokens of [SMILES]<smi>[STOP]) -> SMILES round-trip NLL per molecule (COATI1's
+        batch_smiles_to_s2s_likelihood, clip_e2e.py:667-742, on hcoati_and_tokens_to_likelihood's rows).  Returns (nll [n_ok],
+        mask [len(smiles)]): rows that do not tokenize, or do not fit n_seq minus the prompt, are dropped and False in mask."""
+        self._sync_tokens(tokenizer)
+        raw_tokens, tokens, y_next, mask = s2s_hcoati_likelihood_tokens(list(smiles), tokenizer, do_suffix)
+        if not bool(mask.any()):
+            return torch.zeros(0, device=self.device), mask.to(self.device)
+        return score_host_rows(self.engine, tokens, y_next, raw_tokens=raw_tokens, coati2=True), mask.to(self.device)

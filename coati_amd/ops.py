@@ -182,6 +182,20 @@ def swiglu(u, out=None):
     return out
 
 
+def swiglu_bwd(u, dg, out=None):
+    """SwiGLU's backward: u [B, 2N] f32 = [x | gate] as in swiglu(), dg [B, N] f32 -> du [B, 2N] f32 =
+    [dg * silu(gate) | dg * x * silu'(gate)] (coati_swiglu_bwd); row strides free."""
+    _need_cuda(u)
+    assert u.dtype == torch.float32 and u.dim() == 2 and u.stride(1) == 1 and u.shape[1] % 2 == 0
+    B, N = u.shape[0], u.shape[1] // 2
+    assert dg.dtype == torch.float32 and dg.shape == (B, N) and dg.stride(1) == 1 and dg.device == u.device
+    if out is None:
+        out = torch.empty(B, 2 * N, device=u.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == (B, 2 * N) and out.stride(1) == 1
+    _lib.call("coati_swiglu_bwd", ptr(u), u.stride(0), ptr(dg), dg.stride(0), ptr(out), out.stride(0), B, N, stream())
+    return out
+
+
 def group_mean_rows(x, off, w=None, fallback=None, out=None):
     """Segmented weighted mean (coati_group_mean_rows): out[g] = sum_{i in [off[g], off[g+1])} w[i] x[i] / sum w[i]; an empty group
     copies fallback[g].  x [N, E] f32 (row stride free), off [G + 1] int32 on the device, w [N] f32 or None (weights 1), fallback [G, E]

@@ -16,18 +16,19 @@ def y_next_from_tokens(tokens):
     return y
 
 
-def packed_rows(raw_tokens, tokens, y_next=None):
+def packed_rows(raw_tokens, tokens, y_next=None, pad=PAD):
     """Host-side row counts of the packed layout (include/coati_hip.h, coati_engine_forward rows1 / rows2): per row
     1 + the last position that holds a non-[PAD] token (or, for `tokens`, a target that is not -1), summed over the batch.
     The batch assembler calls this while the tokens are still on the host; on device tensors it costs one synchronisation."""
-    l1, l2 = packed_lengths(raw_tokens, tokens, y_next)
+    l1, l2 = packed_lengths(raw_tokens, tokens, y_next, pad)
     return int(l1.sum().item()), int(l2.sum().item())
 
 
-def packed_lengths(raw_tokens, tokens, y_next=None):
-    """Per-row lengths of the packed layout: [B] int32 for each of the two passes (their sums are packed_rows)."""
+def packed_lengths(raw_tokens, tokens, y_next=None, pad=PAD):
+    """Per-row lengths of the packed layout: [B] int32 for each of the two passes (their sums are packed_rows).  pad: the model's
+    [PAD] id (the engine's cfg.pad_token; COATI2 vocabularies do not have it at 0)."""
     def length(tok, y):
-        live = tok != PAD
+        live = tok != pad
         if y is not None:
             live = live | (y >= 0)
         T = tok.shape[1]

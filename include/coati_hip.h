@@ -213,6 +213,9 @@ int coati_silu(const float* x, float* y, int64_t n, void* stream);
 /* SwiGLU gate of the COATI2 heads (simple_coati2/transformer_only.py:38-42): x, gate = u.chunk(2, -1); g = silu(gate) * x, i.e.
    g[b * ldg + j] = u[b * ldu + j] * silu(u[b * ldu + N + j]) for b < B, j < N; f32, ldu >= 2N, ldg >= N */
 int coati_swiglu(const float* u, int64_t ldu, float* g, int64_t ldg, int B, int N, void* stream);
+/* its backward: u as above, dg [B, N] (stride lddg >= N) -> du [B, 2N] (stride lddu >= 2N),
+   du[b, j] = dg[b, j] * silu(gate[b, j]) and du[b, N + j] = dg[b, j] * x[b, j] * s (1 + gate (1 - s)), s = sigmoid(gate[b, j]); f32 */
+int coati_swiglu_bwd(const float* u, int64_t ldu, const float* dg, int64_t lddg, float* du, int64_t lddu, int B, int N, void* stream);
 /* Segmented weighted mean (batched purify_vector, coati/generative/coati_purifications.py:51-97): out[g] = sum over rows i in
    [off[g], off[g+1]) of w[i] * x[i] / sum w[i] (w null: every weight 1); an empty group copies fallback[g].  x rows of E f32 with
    stride ldx; off [G + 1] int32 (non-decreasing, off[G] <= rows of x); fallback / out [G, E] f32.  One workgroup per group, the rows
@@ -408,7 +411,8 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
  * smiles_to_coati.* and coati_to_token.net.*.  Needs use_point_encoder = 0, use_fp8 = 0, norm_embed = 0 and
  * n_embd_common == n_hidden_xformer; the point-encoder and clip-head fields of cfg are ignored.  On such an engine
  * coati_engine_encode runs smiles_to_coati behind the encoder pass (raw_tokens only); forward, forward_decoder, backward,
- * optimizer_step, infonce, score and logits refuse to run; the decode entries work unchanged. */
+ * optimizer_step, infonce, score, score_grad and logits refuse to run (scoring: coati_engine_score_coati2 / coati_engine_score_grad_coati2);
+ * the decode entries work unchanged. */
 int coati_engine_create_coati2(const coati_config* cfg, int enc_to_coati, coati_engine** out);
 /* the token head coati_to_token = SwiGLUResNet(E, E) on h [B,E] f32 -> h_token [B,E] f32 (must not overlap h).  Scratch from the workspace:
  * coati_engine_workspace_bytes(e, B, 1, 1, 1, B) bytes.  Only on a COATI2 engine. */
@@ -436,6 +440,24 @@ int coati_engine_score(coati_engine* e, void* workspace, int64_t workspace_bytes
 int coati_engine_score_grad(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_clip,
                             const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll, float* dh_clip,
                             float* scal, void* stream);
+
+/* COATI2 likelihood scoring: coati_engine_score on an engine of coati_engine_create_coati2.  nll[b] = the summed cross-entropy of
+ * tokens [B,T2] against y_next [B,T2] (-1 = ignored) with the token head's image (coati_to_token = SwiGLUResNet(E, E), what hcoati_to_2d decodes from) of an
+ * embedding injected at the [UNK] positions.  Exactly one of raw_tokens [B,T1] (the embedding is smiles_to_coati of the encoder pass, any
+ * enc_to_coati; scal[6] bit 0 as in coati_engine_encode) and h_coati [B,E] f32 (T1 is ignored).  Packed rows, the error word, the
+ * determinism and the workspace as in coati_engine_score; nothing is kept for another entry.  A COATI1 engine is refused. */
+int coati_engine_score_coati2(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T1, int T2, const int64_t* raw_tokens,
+                              const float* h_coati, const int64_t* tokens, const int64_t* y_next, int64_t rows1, int64_t rows2, float* nll,
+                              float* scal, void* stream);
+
+/* The COATI2 likelihood's gradient w.r.t. the embedding: coati_engine_score_grad on an engine of coati_engine_create_coati2.  nll[b] is
+ * bit for bit what coati_engine_score_coati2(h_coati = ...) returns for the same arguments; dh_coati[b] = weights[b] * d nll[b] /
+ * d h_coati[b] ([B,E] f32; weights [B] f32 or null = ones), through the decoder pass and the token head (LayerNorm -> Linear -> SwiGLU ->
+ * Linear, + x), summed over every [UNK] position of row b.  rows2 > 0: packed decoder rows.  The model is a constant: no parameter
+ * gradient is formed and no parameter is written.  A COATI1 engine is refused.  Workspace as for coati_engine_score_coati2. */
+int coati_engine_score_grad_coati2(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_coati,
+                                   const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll,
+                                   float* dh_coati, float* scal, void* stream);
 
 /* encode_tokens on PACKED rows (coati_engine_encode's token tower, COATI1 and COATI2): the encoder pass runs on the concatenation of the
  * rows' real prefixes, rows1 = sum over rows of (1 + last non-[PAD] position) of raw_tokens [B,T1], counted by the caller on the host.
