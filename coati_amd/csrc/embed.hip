@@ -332,6 +332,17 @@ int launch_bad_rows(const long long* tokens, unsigned char* bad, int B, int T, h
 // cross-entropy finish (lmhead): merge per-tile (max, sumexp) partials into lse[row]; target logit by a
 // direct bf16 dot product (same operands the MFMA saw); accumulate sum(lse - logit_t) and the count.
 // ------------------------------------------------------------------------------------------------------
+// logit[row][tgt] as a bf16 dot product over one wave (every lane ends with it)
+__device__ __forceinline__ float ce_target_logit(const bf16_t* __restrict__ a, long long lda, const bf16_t* __restrict__ W, long long ldw,
+                                                 long long tgt, long long row, int C, int lane) {
+  float dot = 0.f;
+  for (int c = lane * 4; c < C; c += 256) {
+    const uint2 ua = *reinterpret_cast<const uint2*>(a + row * lda + c);
+    const uint2 uw = *reinterpret_cast<const uint2*>(W + tgt * ldw + c);
+    dot += bflo(ua.x) * bflo(uw.x) + bfhi(ua.x) * bfhi(uw.x) + bflo(ua.y) * bflo(uw.y) + bfhi(ua.y) * bfhi(uw.y);
+  }
+  return wave_sum(dot);
+}
 // One row, one wave: lse of the row (written to *lse_out by lane 0 when given) and, when the target is in range, lse - logit[target]
 // in every lane (*valid = true).  Shared by ce_finish (batch sums) and ce_seq (per-sequence sums): the two see the same numbers.
 __device__ __forceinline__ float ce_row(const float2* __restrict__ partial, int tiles_n, const bf16_t* __restrict__ a, long long lda,
@@ -350,14 +361,7 @@ __device__ __forceinline__ float ce_row(const float2* __restrict__ partial, int 
   if (lse_out != nullptr && lane == 0) *lse_out = l;
   *valid = tgt >= 0 && tgt < V;
   if (!*valid) return 0.f;
-  float dot = 0.f;
-  for (int c = lane * 4; c < C; c += 256) {
-    const uint2 ua = *reinterpret_cast<const uint2*>(a + row * lda + c);
-    const uint2 uw = *reinterpret_cast<const uint2*>(W + tgt * ldw + c);
-    dot += bflo(ua.x) * bflo(uw.x) + bfhi(ua.x) * bfhi(uw.x) + bflo(ua.y) * bflo(uw.y) + bfhi(ua.y) * bfhi(uw.y);
-  }
-  dot = wave_sum(dot);
-  return l - dot;
+  return l - ce_target_logit(a, lda, W, ldw, tgt, row, C, lane);
 }
 
 __global__ __launch_bounds__(256) void ce_finish_kernel(const float2* __restrict__ partial, int tiles_n,
@@ -393,6 +397,71 @@ int launch_ce_finish(const float2* partial, int tiles_n, const bf16_t* a, long l
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(ce_finish_kernel, dim3(blocks), dim3(256), 0, s, partial, tiles_n, a, lda, W, ldw, target, lse, scal, M, C, V);
   COATI_LAUNCH_CHECK("ce_finish");
+  return COATI_OK;
+}
+
+// The finish of EPI_CE_LSE (gemm_rb16.hip): the lm_head kernel has left lse[row] itself, so nothing per tile is read here -- one wave per
+// row with a target: a[row] . W[target] and the two sums.  Rows without a target (outside [0, V)) cost one 8-byte load.
+__global__ __launch_bounds__(256) void ce_lse_finish_kernel(const bf16_t* __restrict__ a, long long lda, const bf16_t* __restrict__ W, long long ldw,
+                                                            const long long* __restrict__ target, const float* __restrict__ lse,
+                                                            float* __restrict__ scal, int M, int C, int V) {
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float loss_acc = 0.f, cnt_acc = 0.f;
+  for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
+    const long long tgt = target[row];
+    if (tgt >= 0 && tgt < V) {
+      loss_acc += lse[row] - ce_target_logit(a, lda, W, ldw, tgt, row, C, lane);
+      cnt_acc += 1.f;
+    }
+  }
+  if (lane == 0) { red[0][wave] = loss_acc; red[1][wave] = cnt_acc; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(scal + 0, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    atomicAdd(scal + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+  }
+}
+
+int launch_ce_lse_finish(const bf16_t* a, long long lda, const bf16_t* W, long long ldw, const long long* target, const float* lse,
+                         float* scal, int M, int C, int V, hipStream_t s) {
+  COATI_CHECK_ARG(a && W && target && lse && scal, "ce_lse_finish: null operand");
+  COATI_CHECK_SHAPE(M > 0 && C % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "ce_lse_finish: shape / alignment");
+  int blocks = cdiv(M, 4);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(ce_lse_finish_kernel, dim3(blocks), dim3(256), 0, s, a, lda, W, ldw, target, lse, scal, M, C, V);
+  COATI_LAUNCH_CHECK("ce_lse_finish");
+  return COATI_OK;
+}
+
+__global__ __launch_bounds__(256) void ce_lse_finish_picked_kernel(const long long* __restrict__ target, const float* __restrict__ lse,
+                                                                   const float* __restrict__ tl, float* __restrict__ scal, int M, int V) {
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float loss_acc = 0.f, cnt_acc = 0.f;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < M; row += gridDim.x * 256) {
+    const long long tgt = target[row];
+    if (tgt >= 0 && tgt < V) {
+      loss_acc += lse[row] - tl[row];
+      cnt_acc += 1.f;
+    }
+  }
+  loss_acc = wave_sum(loss_acc);
+  cnt_acc = wave_sum(cnt_acc);
+  if (lane == 0) { red[0][wave] = loss_acc; red[1][wave] = cnt_acc; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(scal + 0, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    atomicAdd(scal + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+  }
+}
+
+int launch_ce_lse_finish_picked(const long long* target, const float* lse, const float* tl, float* scal, int M, int V, hipStream_t s) {
+  COATI_CHECK_ARG(target && lse && tl && scal && M > 0, "ce_lse_finish_picked: null operand");
+  int blocks = cdiv(M, 256);
+  if (blocks > 256) blocks = 256;
+  hipLaunchKernelGGL(ce_lse_finish_picked_kernel, dim3(blocks), dim3(256), 0, s, target, lse, tl, scal, M, V);
+  COATI_LAUNCH_CHECK("ce_lse_finish_picked");
   return COATI_OK;
 }
 

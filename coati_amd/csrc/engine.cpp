@@ -560,7 +560,7 @@ static int row_split_plan(const GemmArgs& a, int a_f32, int epi) {
   if (!row_split_on() || a.m_dev != nullptr || a_f32 || a.M <= 65536 || a.q8_out != nullptr) return 0;
   if (!(a.K == 256 || a.N == 256)) return 0;
   if (epi != EPI_BF16 && epi != EPI_RES_F32 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL &&
-      epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_LNBWD) return 0;
+      epi != EPI_CE_LSE && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_LNBWD) return 0;
   // a launch starts on a 16-row slab and, in the padded layout of the rotary epilogue (row m sits at position m % rope_T), on a sequence
   // boundary
   long long unit = 16;
@@ -589,6 +589,8 @@ static void advance_rows(GemmArgs& a, long long r0, int epi, int lnb_partial_row
   a.aux_in = adv(a.aux_in, r0 * a.ld_aux * aux_in_b);
   a.aux_out = const_cast<void*>(adv(a.aux_out, r0 * a.ld_aux * aux_out_b));
   if (a.lse) a.lse += r0;
+  if (a.lse_out) a.lse_out += r0;
+  if (a.tl_out) a.tl_out += r0;
   if (a.target) a.target += r0;
   if (a.row_scale) a.row_scale += r0;
   if (a.partial) a.partial += r0 * cdiv(a.N, a.partial_tile > 0 ? a.partial_tile : 128);
@@ -1764,6 +1766,72 @@ static int lmhead_ce_partial(coati_engine* e, hipStream_t s, int* tiles_v) {
   return gemm_rows(a, 0, EPI_CE_PARTIAL, s);
 }
 
+// The training forward's lm_head with the row statistics kept in registers (gemm_rb16.hip EPI_CE_LSE): lse[row] comes out of the product's
+// launch(es), the finish reads no per-tile array.  Taken where the 16-row-slab kernel would have taken the partial product (every launch of a
+// row split); COATI_CE_LSE=0 switches it off (A/B).
+static bool ce_lse_on() {
+  static const bool on = []() { const char* v = getenv("COATI_CE_LSE"); return !(v && v[0] == '0'); }();
+  return on;
+}
+// the target logit picked inside the product's launch (COATI_CE_PICK=0: recomputed by the finish as a dot product)
+static bool ce_pick_on() {
+  static const bool on = []() { const char* v = getenv("COATI_CE_PICK"); return !(v && v[0] == '0'); }();
+  return on;
+}
+static GemmArgs lmhead_ce_lse_args(coati_engine* e) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer;
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = e->p2.M; a.N = c.n_tok; a.K = C; a.lse_out = e->ce_lse;
+  if (ce_pick_on()) {   // the target logits go where the other path keeps its per-tile partials
+    a.target = e->p2.packed ? e->p2.ypk : e->y_next;
+    a.tl_out = reinterpret_cast<float*>(e->ce_partial);
+  }
+  return a;
+}
+static bool lmhead_ce_lse_taken(coati_engine* e) {
+  if (!ce_lse_on()) return false;
+  const GemmArgs a = lmhead_ce_lse_args(e);
+  const int rows = row_split_plan(a, 0, EPI_CE_LSE);
+  for (long long r0 = 0; r0 < a.M; r0 += rows ? rows : a.M) {
+    GemmArgs b = a;
+    b.M = (int)std::min<long long>(rows ? rows : a.M, a.M - r0);
+    b.partial_tile = 64;
+#ifdef COATI_EXPERIMENTAL
+    if (gemm_t32_supported(b, 0, EPI_CE_PARTIAL)) return false;
+#endif
+    if (!gemm_rb16_supported(b, 0, EPI_CE_PARTIAL)) return false;
+  }
+  return true;
+}
+static int lmhead_ce_lse(coati_engine* e, hipStream_t s) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, M2 = e->p2.M;
+  const GemmArgs a = lmhead_ce_lse_args(e);
+  {
+    ProfScope ps(e, SITE_LMHEAD_FWD, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2);   // logits never leave the chip
+    COATI_TRY(gemm_rows(a, 0, EPI_CE_LSE, s));
+  }
+  if (a.tl_out) return launch_ce_lse_finish_picked(a.target, e->ce_lse, a.tl_out, e->scal, M2, c.n_tok, s);
+  return launch_ce_lse_finish(e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next, e->ce_lse, e->scal, M2, C, c.n_tok, s);
+}
+
+// lm_head + cross-entropy as an operator: lse[M] of A W^T through the same launches as the engine (gemm_rows: above 65 536 rows, two launches
+// on equal row ranges), then the loss sum and the target count into scal[0], scal[1].  tl (optional, [M]): the product also picks the
+// target logits and the finish reads them instead of recomputing them
+int coati_lmhead_ce_lse(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int V, int K, const int64_t* target,
+                        float* lse, float* tl, float* scal, void* stream) {
+  COATI_CHECK_ARG(A && W && target && lse && scal, "lmhead_ce_lse: null operand");
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = A; a.lda = lda; a.B = W; a.ldb = ldw; a.M = M; a.N = V; a.K = K; a.lse_out = lse;
+  a.target = reinterpret_cast<const long long*>(target); a.tl_out = tl;
+  COATI_TRY(gemm_rows(a, 0, EPI_CE_LSE, (hipStream_t)stream));
+  if (tl) return launch_ce_lse_finish_picked(a.target, lse, tl, scal, M, V, (hipStream_t)stream);
+  return launch_ce_lse_finish(A, lda, W, ldw, reinterpret_cast<const long long*>(target), lse, scal, M, K, V, (hipStream_t)stream);
+}
+
 // decoder pass with injection + lm_head / AR cross-entropy: the second half of coati_engine_forward
 static int forward_decoder_impl(coati_engine* e, hipStream_t s) {
   const coati_config& c = e->cfg;
@@ -1772,7 +1840,9 @@ static int forward_decoder_impl(coati_engine* e, hipStream_t s) {
   // ---- decoder pass with injection (smiles_xformer.py:426-452) ----
   COATI_TRY(xformer_fwd(e, e->p2, e->cliptok, s));
   // ---- lm_head + AR cross-entropy, logits never materialised (smiles_xformer.py:453, train_coati.py:260-265) ----
-  if (e->y_next) {
+  if (e->y_next && lmhead_ce_lse_taken(e)) {
+    COATI_TRY(lmhead_ce_lse(e, s));
+  } else if (e->y_next) {
     int tiles_v = 0;
     COATI_TRY(lmhead_ce_partial(e, s, &tiles_v));
     COATI_TRY(launch_ce_finish(e->ce_partial, tiles_v, e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next, e->ce_lse, scal, e->p2.M, C, c.n_tok, s));

@@ -263,13 +263,18 @@ static int launch_nt_t(const GemmArgs& a, hipStream_t s) {
 
 int launch_gemm_nt(const GemmArgs& a, int a_f32, int epi, hipStream_t s) {
   COATI_CHECK_ARG(a.A && a.B, "gemm_nt: null operand");
-  COATI_CHECK_ARG(a.C || epi == EPI_CE_PARTIAL, "gemm_nt: null output");
+  COATI_CHECK_ARG(a.C || epi == EPI_CE_PARTIAL || epi == EPI_CE_LSE, "gemm_nt: null output");
   COATI_CHECK_SHAPE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % BK == 0, "gemm_nt: K=%d must be a positive multiple of %d", a.K, BK);
   COATI_CHECK_SHAPE(a.lda % (a_f32 ? 4 : 8) == 0 && a.ldb % 8 == 0, "gemm_nt: lda/ldb alignment (lda=%lld ldb=%lld)", a.lda, a.ldb);
   const bool out_f32 = (epi == EPI_F32 || epi == EPI_RES_F32 || epi == EPI_ACC_F32 || epi == EPI_LNBWD);
   if (epi == EPI_LNBWD) {   // the ring GEMM's fused LayerNorm backward: no other kernel has it (callers ask gemm_ring_lnbwd_supported first)
     COATI_CHECK_ARG(!a_f32, "gemm_nt: EPI_LNBWD takes a bf16 A operand");
     return launch_gemm_ring256(a, epi, s);
+  }
+  if (epi == EPI_CE_LSE) {   // the row statistics kept in registers over all tiles: the 16-row-slab kernel only
+    COATI_CHECK_ARG(a.lse_out && (a.tl_out == nullptr || a.target != nullptr), "gemm_nt: EPI_CE_LSE needs lse_out (and target with tl_out)");
+    COATI_CHECK_SHAPE(gemm_rb16_supported(a, a_f32, epi), "gemm_nt: EPI_CE_LSE takes bf16 operands, K = 256, no bias and at most 65 536 rows per launch (M=%d K=%d)", a.M, a.K);
+    return launch_gemm_rb16(a, epi, s);
   }
   if (epi != EPI_CE_PARTIAL)
     COATI_CHECK_SHAPE(a.ldc % (out_f32 ? 4 : 8) == 0, "gemm_nt: ldc=%lld alignment", a.ldc);
@@ -866,19 +871,17 @@ struct W2Frags { bf16x8 a[4], b[2]; };
 // (A split form that also used the 64 idle CUs -- three quarters of M on a tile's main workgroup, the last quarter on a helper,
 // ordered commits through ticket counters -- was built in round 2 and measured no faster (2.14 vs 2.04 ms): the launch is bound
 // by what the memory system delivers, not by the number of CUs.  Removed in round 3; see DESIGN.md.)
-template <int NS>
-__global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile* __restrict__ table, int M_rt) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const WgradTile& d = table[xcd_swizzle(blockIdx.x, gridDim.x)];
-  WgradArgs p = d.p;
-  if (M_rt > 0) p.M = M_rt;   // the rows of THIS launch (see wgrad_dma_table_kernel)
-  const int tiles_k = d.tiles_k, tile = d.tile;
+// SPLIT (round 7, the lm_head's dW[V, 256]: 41 tiles for 256 CUs): the workgroup streams the stages c_begin .. c_end of M only and the
+// slices of a tile meet in fp32 atomics; no bias; N need not be a multiple of 256 -- the A columns past N come from the zero page and
+// the rows past n_out are not committed.
+template <int NS, bool SPLIT>
+__device__ __forceinline__ void wgrad256_body(const WgradArgs& p, int tiles_k, int tile, int c_begin, int c_end, unsigned char* smem) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const int tile_n = tile / tiles_k, tile_k = tile - tile_n * tiles_k;
   const int n0 = tile_n * 256, k0 = tile_k * 256;
-  const int c_begin = 0;
-  const int c_end = (p.M + W2_CH - 1) / W2_CH;
+  if (SPLIT && c_begin >= c_end) return;
+  const int m_end = (SPLIT && c_end * W2_CH < p.M) ? c_end * W2_CH : p.M;
   const bf16_t* A = reinterpret_cast<const bf16_t*>(p.A);
 
   // DMA sources of this lane: piece "rows 4 wave .. + 3" of block b = 0..3 (A0, A1, B0, B1); LDS slot (row & 3 = lane >> 4,
@@ -895,19 +898,21 @@ __global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile*
   const bf16_t* ab = A + n0 + (long long)c_begin * W2_CH * p.lda;       // row 0 of the next stage (scalar)
   const bf16_t* bb = p.B + k0 + (long long)c_begin * W2_CH * p.ldb;
   const long long ab_step = (long long)W2_CH * p.lda, bb_step = (long long)W2_CH * p.ldb;
+  const bool a_full = !SPLIT || n0 + 256 <= p.N;   // (scalar) the tile's 256 A columns exist
+  const bool aok[2] = {!SPLIT || n0 + qg * 8 < p.N, !SPLIT || n0 + 128 + qg * 8 < p.N};   // (N % 8 == 0: a 16-B chunk is inside or outside as a whole)
   auto issue = [&](int slot) __attribute__((always_inline)) {
     const unsigned S = ldsw + slot * W2_STAGE_BYTES;
-    if ((cnext + 1) * W2_CH <= p.M) {
+    if (a_full && (cnext + 1) * W2_CH <= m_end) {
       wd_dma16s(ab, offa, S);
       wd_dma16s(ab, offa + 256u, S + W2_BLK_BYTES);
       wd_dma16s(bb, offb, S + 2 * W2_BLK_BYTES);
       wd_dma16s(bb, offb + 256u, S + 3 * W2_BLK_BYTES);
     } else {
       const int m = cnext * W2_CH + 4 * wave + rsub;
-      const bool ok = m < p.M;
+      const bool ok = m < m_end;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        wd_dma16(ok ? A + n0 + 128 * h + qg * 8 + (long long)m * p.lda : zero, S + h * W2_BLK_BYTES);
+        wd_dma16((ok && aok[h]) ? A + n0 + 128 * h + qg * 8 + (long long)m * p.lda : zero, S + h * W2_BLK_BYTES);
         wd_dma16(ok ? p.B + k0 + 128 * h + qg * 8 + (long long)m * p.ldb : zero, S + (2 + h) * W2_BLK_BYTES);
       }
     }
@@ -999,8 +1004,8 @@ __global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile*
   fetch(0, 0, f0);
   auto step = [&](auto slot_c) __attribute__((always_inline)) {
     constexpr int SL = decltype(slot_c)::value, SN = (SL + 1) % NS;
-    const bool turn = bias_ctr == 0;
-    bias_ctr = (bias_ctr == 0 ? tiles_k : bias_ctr) - 1;
+    const bool turn = !SPLIT && bias_ctr == 0;
+    if (!SPLIT) bias_ctr = (bias_ctr == 0 ? tiles_k : bias_ctr) - 1;
     if (turn) bias_read(SL);
     fetch(SL, 1, f1);
     mma(f0);
@@ -1034,6 +1039,21 @@ __global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile*
   __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) + lgkmcnt(0): the over-issued (zero-page) DMAs have landed, the ring is free
   __builtin_amdgcn_s_barrier();
 
+  if constexpr (SPLIT) {
+    // the slices of a tile meet in atomics; the rows past n_out (the lm_head's padded vocabulary columns) are not committed
+    const int nout = p.n_out > 0 ? p.n_out : p.N;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int n = n0 + wm * 128 + i * 32 + frag_row(r, lane);
+          const int k = k0 + wn * 64 + j * 32 + (lane & 31);
+          if (n < nout) atomicAdd(p.dW + (long long)n * p.ldw + k, acc[i][j][r]);
+        }
+    return;
+  }
   // bias partials: [4 row quarters][256 columns] through the (idle) ring; all workgroups of a tile row add into one slice
   float* const bsum = reinterpret_cast<float*>(smem);
   bsum[rq * 256 + 2 * cp] = cs0;
@@ -1055,6 +1075,30 @@ __global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile*
         const int k = k0 + wn * 64 + j * 32 + (lane & 31);
         p.dW[(long long)n * p.ldw + k] += acc[i][j][r];
       }
+}
+
+template <int NS>
+__global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile* __restrict__ table, int M_rt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const WgradTile& d = table[xcd_swizzle(blockIdx.x, gridDim.x)];
+  WgradArgs p = d.p;
+  if (M_rt > 0) p.M = M_rt;   // the rows of THIS launch (see wgrad_dma_table_kernel)
+  wgrad256_body<NS, false>(p, d.tiles_k, d.tile, 0, (p.M + W2_CH - 1) / W2_CH, smem);
+}
+
+// One problem, 256 x 256 tiles, M split over the workgroups of a tile so that one round fills the machine (the lm_head's weight gradient:
+// 41 tiles x 6 slices).  Consecutive workgroups (one XCD's share under xcd_swizzle) take the same slice of M: they share its B panel.
+template <int NS>
+__global__ __launch_bounds__(512, 1) void wgrad256_split_kernel(WgradArgs p, int tiles_k, int chunks_per_split, int n_splits) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tiles = gridDim.x / n_splits;
+  const int wg = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int split = wg / tiles, tile = wg - split * tiles;
+  const int nchunks = (p.M + W2_CH - 1) / W2_CH;
+  const int c_begin = split * chunks_per_split;
+  int c_end = c_begin + chunks_per_split;
+  if (c_end > nchunks) c_end = nchunks;
+  wgrad256_body<NS, true>(p, tiles_k, tile, c_begin, c_end, smem);
 }
 
 bool wgrad_table_tile256_ok(const WgradArgs& a) {
@@ -1148,6 +1192,40 @@ static int launch_wgrad256_t(const WgradTile* dev_table, int n_tiles, hipStream_
   return COATI_OK;
 }
 
+// the single-problem split form of the 256-wide kernel: bf16 operands without a bias whose 256-wide tiles alone would leave most CUs idle
+// and whose 128-wide tiles need two rounds (the lm_head: dlogits[M, Vpad]^T a[M, 256], 41 tiles, 162 of the narrow ones).
+// COATI_WGRAD256_SPLIT=0 switches it off (A/B)
+static bool wgrad256_split_taken(const WgradArgs& a) {
+  static const bool on = []() { const char* v = getenv("COATI_WGRAD256_SPLIT"); return !(v && v[0] == '0'); }();
+  if (!on || a.dbias != nullptr || a.m_dev != nullptr || a.K % 256 != 0 || a.N % 8 != 0) return false;
+  if (40LL * a.lda >= (1LL << 30) || 40LL * a.ldb >= (1LL << 30)) return false;
+  const int tiles128 = cdiv(a.N, BM) * cdiv(a.K, BN), tiles = cdiv(a.N, 256) * (a.K / 256);
+  return tiles128 > 128 && tiles128 <= 256 && tiles >= 32;   // (few rows: slices of fewer stages, down to none -- those workgroups leave at once)
+}
+
+static int launch_wgrad256_split(const WgradArgs& a, hipStream_t s) {
+  static bool attr_set = false;
+  constexpr int NS = 4;
+  auto kern = wgrad256_split_kernel<NS>;
+  constexpr int lds = NS * W2_STAGE_BYTES;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) {
+      coati_set_error("wgrad(256 split): hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+      return COATI_EHIP;
+    }
+    attr_set = true;
+  }
+  const int tiles_k = a.K / 256, tiles = cdiv(a.N, 256) * tiles_k;
+  const int nchunks = cdiv(a.M, W2_CH);
+  int splits = 256 / tiles;   // one round of at most one workgroup per CU
+  const int cps = cdiv(nchunks, splits);
+  splits = cdiv(nchunks, cps);
+  hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(512), lds, s, a, tiles_k, cps, splits);
+  COATI_LAUNCH_CHECK("wgrad256_split");
+  return COATI_OK;
+}
+
 int launch_wgrad_table(const WgradTile* dev_table, int n_tiles, hipStream_t s, int tile_size, int M_rt) {
   COATI_CHECK_ARG(dev_table && n_tiles > 0, "wgrad_table: empty table");
   if (tile_size == 256) {
@@ -1224,6 +1302,7 @@ int launch_wgrad(const WgradArgs& a, int a_f32, hipStream_t s) {
   if (a_f32) return a.dbias ? launch_wgrad_t<float, true>(a, s) : launch_wgrad_t<float, false>(a, s);
   // bf16 A: the LDS-DMA kernel (one 512-thread workgroup per CU) when the launch gives every CU a tile and a slice of at
   // least 16 stages; otherwise (few rows: GNN node level; many tiles: lm_head) the register-staged kernel.
+  if (wgrad256_split_taken(a)) return launch_wgrad256_split(a, s);
   constexpr int dma = 3;   // ring depth (4 was measured equal, round 2)
   const int tiles = cdiv(a.N, BM) * cdiv(a.K, BN);
   // tiles <= 64: one round of 256 workgroups; 129..256 tiles (lm_head: 162): two rounds of up to 512; in between the

@@ -7,6 +7,12 @@ __device__ __forceinline__ int frag_row(int r, int lane) { return (r & 3) + 8 * 
 
 // ---- epilogue on 8 consecutive columns of one row ----------------------------------------------------
 // register-resident pre-loaded extra operand of one task (tiled kernel): see `staged` below for the meaning per epilogue
+// per-row operands of EPI_CE_BWD / EPI_CE_BWD_ROW a caller holds in registers for all tiles of a row (`staged`)
+struct CeRow {
+  long long tgt;
+  float lse, inv;
+};
+
 struct EpiPre {
   float4 f0, f1;
   uint4 h;
@@ -26,6 +32,7 @@ __device__ __forceinline__ void epilogue8(const GemmArgs& p, int row, int col0, 
   //   EPI_MUL_AUX        -> uint2 = the 8 saved 8-bit NewGELU' codes aux_in[row, col0..col0+7]
   //   EPI_EDGE_DPRE      -> float[8 + ...]: staged[e] = w1c of column col0+e, staged[64 + e] = b1 of column col0+e
   //   EPI_RES_F32        -> float4[2] = aux_in[row, col0..col0+7];   EPI_ACC_F32 -> float4[2] = C[row, col0..col0+7]
+  //   EPI_CE_BWD(_ROW)   -> CeRow = target[row], lse[row] and the row's factor (instead of three loads per call)
   const float* rope_row = (EPI == EPI_QKV_ROPE) ? reinterpret_cast<const float*>(staged) : nullptr;
   const int N = p.N;
   if (p.bias != nullptr) {
@@ -190,15 +197,21 @@ __device__ __forceinline__ void epilogue8(const GemmArgs& p, int row, int col0, 
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = v[e] * ((EPI == EPI_DGELU) ? dgelu_f(x[e]) : dsilu_f(x[e]));
   } else if (EPI == EPI_CE_BWD || EPI == EPI_CE_BWD_ROW) {
-    const long long tgt = p.target[row];
-    float inv;
-    if (EPI == EPI_CE_BWD_ROW) {   // per-sequence gradient: the row's own factor (launch_ce_seq_bwd: 0 where the row has no target)
-      inv = p.row_scale[row];
+    long long tgt;
+    float inv, l;
+    if (staged) {
+      const CeRow* cr = reinterpret_cast<const CeRow*>(staged);
+      tgt = cr->tgt; inv = cr->inv; l = cr->lse;
     } else {
-      const float cnt = p.scal[1];
-      inv = (tgt >= 0 && cnt > 0.f) ? 1.0f / cnt : 0.f;
+      tgt = p.target[row];
+      if (EPI == EPI_CE_BWD_ROW) {   // per-sequence gradient: the row's own factor (launch_ce_seq_bwd: 0 where the row has no target)
+        inv = p.row_scale[row];
+      } else {
+        const float cnt = p.scal[1];
+        inv = (tgt >= 0 && cnt > 0.f) ? 1.0f / cnt : 0.f;
+      }
+      l = p.lse[row];
     }
-    const float l = p.lse[row];
     // (softmax(v) - onehot) / count in few VALU slots (they add to the tile time): the target's position relative to this lane's 8
     // columns as ONE 32-bit value (anything outside 0..7 never matches).  exp(v - lse) keeps the subtraction FIRST: folded into
     // exp2(fma(v, log2e, -lse log2e)) the argument carries the rounding of two numbers of size ~ 30, i.e. 1e-6 of absolute error

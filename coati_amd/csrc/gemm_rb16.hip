@@ -27,6 +27,7 @@
 // Two weight tiles per workgroup barrier (2 x 64 KiB of tile buffers, the first tile's stores in flight during the second tile's MFMA
 // phase, half the barriers and DMA waits) were built and measured too: 42.3 / 75.6 / 35.5 us against 42.0 / 72.8 / 36.5 on the three
 // shapes of tools/rb16_ablate.py, 22.24 ms per step either way -- the barrier count is not the lever.
+#include <algorithm>
 #include <cstdlib>
 #include "gemm_epi.h"
 
@@ -209,6 +210,31 @@ __global__ __launch_bounds__(64 * R16_MAXW, 1) void gemm_rb16_kernel(GemmArgs p,
   const bool rowok = row_l < p.M;
 #endif
 
+  // EPI_CE_BWD / _ROW: the row's target, lse and factor are the same for every tile: registers for the whole kernel (the epilogue loaded
+  // them from memory twice per tile, behind stores the compiler cannot move them across)
+  CeRow ce_row = {-1, 0.f, 0.f};
+  if constexpr (EPI == EPI_CE_BWD || EPI == EPI_CE_BWD_ROW) {
+    ce_row.tgt = p.target[rc];
+    ce_row.lse = p.lse[rc];
+    if constexpr (EPI == EPI_CE_BWD_ROW) {
+      ce_row.inv = p.row_scale[rc];
+    } else {
+      const float cnt = p.scal[1];
+      ce_row.inv = (ce_row.tgt >= 0 && cnt > 0.f) ? 1.0f / cnt : 0.f;
+    }
+  }
+  // EPI_CE_LSE: running (max, sum exp(v - max)) of row fr over this lane's 16 columns of every tile walked so far
+  float ce_mx = -INFINITY, ce_sm = 0.f;
+  // ... and, with tl_out, the row's target column (-1: none) and its logit once the tile that holds it has passed
+  int ce_tgt = -1;
+  float ce_tl = 0.f;
+  if constexpr (EPI == EPI_CE_LSE) {
+    if (p.tl_out != nullptr) {
+      const long long t = p.target[rc];
+      ce_tgt = (rowok && t >= 0 && t < p.N) ? (int)t : -1;
+    }
+  }
+
   auto tile = [&](int jt, int jn, const bf16_t* cur, bf16_t* nxt) {
 #if !(R16_ABLATE & 1)     // probe builds (tools/rb16_ablate.py): bit 0 = no weight stream behind the first tile
     load_tile(jn * R16_BN, nxt);
@@ -292,6 +318,48 @@ __global__ __launch_bounds__(64 * R16_MAXW, 1) void gemm_rb16_kernel(GemmArgs p,
       sm += __shfl_xor(sm, 16, 64);
       sm += __shfl_xor(sm, 32, 64);
       if (rowok && kq == 0) p.partial[(long long)row_l * ntiles + jt] = make_float2(mx, sm);
+    } else if constexpr (EPI == EPI_CE_LSE) {
+      // the same statistics kept in the lane over ALL tiles (a wave walks every tile of its 16 rows): no shuffle and no store per tile; the
+      // sum is rescaled when the maximum moves (exp(-inf) = 0 covers the first tile).  The four lanes of a row meet once, behind the loop
+      if ((jt + 1) * R16_BN <= p.N) {
+        float t = fmaxf(v0[0], v1[0]);
+#pragma unroll
+        for (int e = 1; e < 8; ++e) t = fmaxf(t, fmaxf(v0[e], v1[e]));
+        const float mn = fmaxf(ce_mx, t);
+        float ts = 0.f;   // the tile's 16 terms on their own, then ONE addition to the running sum: its chain has ntiles links, not 16 ntiles
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ts += __expf(v0[e] - mn) + __expf(v1[e] - mn);   // (subtraction first: see EPI_CE_BWD in gemm_epi.h)
+        ce_sm = fmaf(ce_sm, __expf(ce_mx - mn), ts);
+        ce_mx = mn;
+      } else {
+        float t = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          if (c0 + e < p.N) t = fmaxf(t, v0[e]);
+          if (c1 + e < p.N) t = fmaxf(t, v1[e]);
+        }
+        const float mn = fmaxf(ce_mx, t);
+        if (mn > -INFINITY) {   // (a lane without a valid column in the first tile it walks has nothing to rescale: -inf - -inf)
+          float ts = 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            if (c0 + e < p.N) ts += __expf(v0[e] - mn);
+            if (c1 + e < p.N) ts += __expf(v1[e] - mn);
+          }
+          ce_sm = fmaf(ce_sm, __expf(ce_mx - mn), ts);
+          ce_mx = mn;
+        }
+      }
+      // the target logit: a tile holds the target of one of the wave's 16 rows one time in ten -- the 16 selects are skipped otherwise
+      const int rel = ce_tgt - jt * R16_BN;
+      if (__builtin_amdgcn_ballot_w64((unsigned)rel < (unsigned)R16_BN) != 0) {
+        const int h0 = rel - colA, h1 = rel - colB;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          ce_tl = h0 == e ? v0[e] : ce_tl;
+          ce_tl = h1 == e ? v1[e] : ce_tl;
+        }
+      }
     } else if constexpr (EPI == EPI_QKV_ROPE) {
       // RotaryEmbedding.rotary_embed (basic_transformer.py:83-100) on one head of 16: v0 = dims 0..7, v1 = dims 8..15 of the same
       // head: y_i = x_i c_i - x_{i+8} s_i ; y_{i+8} = x_{i+8} c_i + x_i s_i.  The v block (columns >= 2C) is stored as it is
@@ -335,6 +403,9 @@ __global__ __launch_bounds__(64 * R16_MAXW, 1) void gemm_rb16_kernel(GemmArgs p,
       const uint2 x0 = make_uint2(xq.x, xq.y), x1 = make_uint2(xq.z, xq.w);
       epilogue8<EPI>(q, row_l, c0, v0, rowok, jt, ntiles, &x0);
       epilogue8<EPI>(q, row_l, c1, v1, rowok, jt, ntiles, &x1);
+    } else if constexpr (EPI == EPI_CE_BWD || EPI == EPI_CE_BWD_ROW) {
+      epilogue8<EPI>(q, row_l, c0, v0, rowok, jt, ntiles, &ce_row);
+      epilogue8<EPI>(q, row_l, c1, v1, rowok, jt, ntiles, &ce_row);
     } else {
       epilogue8<EPI>(q, row_l, c0, v0, rowok, jt, ntiles);
       epilogue8<EPI>(q, row_l, c1, v1, rowok, jt, ntiles);
@@ -345,6 +416,20 @@ __global__ __launch_bounds__(64 * R16_MAXW, 1) void gemm_rb16_kernel(GemmArgs p,
     const int jn = jt + 1 == ntiles ? 0 : jt + 1;
     r16_call_restrict(tile, jt, jn, Bs + (j & 1) * R16_TILE_HALFS, Bs + ((j + 1) & 1) * R16_TILE_HALFS);
     jt = jn;
+  }
+  if constexpr (EPI == EPI_CE_LSE) {
+    // the row's four lanes (kq = 0..3) hold disjoint column sets: one merge, independent of the order the tiles were walked in
+    float mx = fmaxf(ce_mx, __shfl_xor(ce_mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sm = ce_mx > -INFINITY ? ce_sm * __expf(ce_mx - mx) : 0.f;   // (N < 64: a lane may own no valid column at all)
+    sm += __shfl_xor(sm, 16, 64);
+    sm += __shfl_xor(sm, 32, 64);
+    if (rowok && kq == 0) p.lse_out[row_l] = mx + __logf(sm);
+    if (p.tl_out != nullptr) {   // (one of the four lanes holds it, the others 0)
+      float tl = ce_tl + __shfl_xor(ce_tl, 16, 64);
+      tl += __shfl_xor(tl, 32, 64);
+      if (rowok && kq == 0) p.tl_out[row_l] = tl;
+    }
   }
 #if R16_ABLATE & 16
 #undef p
@@ -687,15 +772,16 @@ static int rb16_min_waves() {
 
 bool gemm_rb16_supported(const GemmArgs& a, int a_f32, int epi) {
   if (a_f32 || a.K != R16_K || a.m_dev != nullptr) return false;
-  if (epi != EPI_BF16 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW) return false;
+  if (epi != EPI_BF16 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_CE_LSE) return false;
   if (epi == EPI_CE_PARTIAL && a.partial_tile != 64) return false;
   if (epi == EPI_QKV_ROPE && a.rope_hs == 32) return false;
-  if (a.N % 16 != 0 && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_CE_PARTIAL) return false;
+  if (a.N % 16 != 0 && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_CE_PARTIAL && epi != EPI_CE_LSE) return false;
   if (a.bias != nullptr && cdiv(a.N, R16_BN) * R16_BN > R16_BIAS_MAX) return false;
   if (a.q8_out != nullptr) return false;                              // (the fused MXFP8 emission assumes epilogue8's lane layout)
   if (epi == EPI_GELU_GRAD && a.n_store > a.N) return false;
   if (epi == EPI_QKV_ROPE && (a.rope_C % 32 != 0 || a.rope_pos != nullptr)) return false;   // 64-column tiles must not straddle 2C
   const int W = rb16_waves(a.M);
+  if (epi == EPI_CE_LSE) return a.bias == nullptr && W <= R16_MAXW;   // no other kernel has it: any row count up to 65 536 (short workgroups are padded to 8 waves)
   return W >= rb16_min_waves() && W <= R16_MAXW;   // 36 865 .. 65 536 rows: below, the 32-row kernel or the tiled one; above, the 32-row kernel
 }
 
@@ -711,9 +797,10 @@ static int launch_rb16_t(const GemmArgs& a, hipStream_t s) {
     }
     attr_set = true;
   }
-  const int W = rb16_waves(a.M);
+  // (EPI_CE_LSE below 8 waves' worth of rows: load_tile covers a tile in 4 turns of >= 8 waves; the waves past M are masked like a ragged last slab)
+  const int W = EPI == EPI_CE_LSE ? std::max(rb16_waves(a.M), 8) : rb16_waves(a.M);
   const int blocks = cdiv(cdiv(a.M, 16), W);
-  const int rot = (EPI == EPI_MUL_AUX);
+  const int rot = (EPI == EPI_MUL_AUX || EPI == EPI_CE_LSE);
   const size_t bias_bytes = a.bias != nullptr ? (size_t)cdiv(a.N, R16_BN) * R16_BN * 4 : 0;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * W), tile_bytes + bias_bytes, s, a, W, rot);
   COATI_LAUNCH_CHECK("gemm_rb16");
@@ -732,6 +819,7 @@ int launch_gemm_rb16(const GemmArgs& a, int epi, hipStream_t s) {
     case EPI_GELU_GRAD: return ln ? launch_rb16_t<EPI_GELU_GRAD, true>(a, s) : launch_rb16_t<EPI_GELU_GRAD, false>(a, s);
     case EPI_MUL_AUX: return launch_rb16_t<EPI_MUL_AUX, false>(a, s);
     case EPI_CE_PARTIAL: return launch_rb16_t<EPI_CE_PARTIAL, false>(a, s);
+    case EPI_CE_LSE: return launch_rb16_t<EPI_CE_LSE, false>(a, s);
     case EPI_CE_BWD: return launch_rb16_t<EPI_CE_BWD, false>(a, s);
     case EPI_CE_BWD_ROW: return launch_rb16_t<EPI_CE_BWD_ROW, false>(a, s);
     default:

@@ -26,7 +26,9 @@ enum CoatiEpi {
                        // lnb_partial[workgroup][2N] = the workgroup's dgamma | dbeta sums (added up by launch_ln_finish_batched)
   EPI_CE_BWD_ROW = 15, // C(bf16) = (exp(acc - lse[row]) - [col==target[row]]) * row_scale[row]: EPI_CE_BWD with a per-row factor in place of
                        // 1 / count (the per-sequence likelihood gradient, launch_ce_seq_bwd writes lse and row_scale)
-  EPI_COUNT = 16
+  EPI_CE_LSE = 16,     // K = 256, 16-row-slab kernel only: lse_out[row] = log sum over the N columns of exp(acc); the running (max, sum) of a row stays in
+                       // the lanes that walk its tiles, nothing is written per tile (launch_ce_lse_finish adds up the loss)
+  EPI_COUNT = 17
 };
 
 struct GemmArgs {
@@ -100,6 +102,10 @@ struct GemmArgs {
   long long chain_ldc;
   // EPI_CE_BWD_ROW
   const float* row_scale;   // [M]: the factor of row m's (softmax - onehot); 0 for a row without target
+  // EPI_CE_LSE
+  float* lse_out;           // [M]
+  float* tl_out;            // optional [M] (needs target): the logit of the row's target column, picked out of the accumulators by the lane that
+                            // owns it in the tile where it falls (0 for a target outside [0, N)); null: the finish recomputes it as a dot product
 };
 
 int launch_gemm_nt(const GemmArgs& a, int a_f32, int epi, hipStream_t s);
@@ -352,6 +358,12 @@ int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* t
 int launch_ce_finish(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W,
                      long long ldw, const long long* target, float* lse, float* scal, int M, int C, int V,
                      hipStream_t s);
+// the finish of EPI_CE_LSE: lse[M] is there already; adds sum(lse - logit[target]) and the target count into scal[0], scal[1] (target logit
+// by the same bf16 dot product, targets outside [0, V) ignored)
+int launch_ce_lse_finish(const bf16_t* a, long long lda, const bf16_t* W, long long ldw, const long long* target, const float* lse,
+                         float* scal, int M, int C, int V, hipStream_t s);
+// the same when the product has also left the target logits tl[M] (GemmArgs::tl_out): one thread per row
+int launch_ce_lse_finish_picked(const long long* target, const float* lse, const float* tl, float* scal, int M, int V, hipStream_t s);
 // per-sequence sums of lse - logit[target] (one workgroup per sequence, fixed-order reduction: deterministic) into nll[B]; rows of sequence
 // b: b * T .. b * T + T, or off[b] .. off[b + 1] when off is given (packed rows, target = the packed targets)
 int launch_ce_seq(const float2* partial, int tiles_n, const bf16_t* a, long long lda, const bf16_t* W, long long ldw,

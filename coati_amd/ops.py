@@ -353,6 +353,19 @@ def ce_fwd(a, W, target):
     return lse, scal
 
 
+def ce_lse_fwd(a, W, target, pick=True):
+    """ce_fwd with the row statistics kept in registers (K = 256, the 16-row-slab kernel): the product writes lse [M] itself, the finish
+    reads no per-tile array.  Above 65 536 rows the product runs as two launches on equal row ranges.  pick: the product also picks each
+    row's target logit out of its accumulators (False: the finish recomputes it as a dot product).  Returns (lse, scal) as ce_fwd."""
+    M, K = a.shape
+    V = W.shape[0]
+    lse = torch.empty(M, device=a.device, dtype=torch.float32)
+    scal = torch.zeros(16, device=a.device, dtype=torch.float32)
+    tl = torch.empty(M, device=a.device, dtype=torch.float32) if pick else None
+    _lib.call("coati_lmhead_ce_lse", ptr(a), a.stride(0), ptr(W), W.stride(0), M, V, K, ptr(target), ptr(lse), ptr(tl), ptr(scal), stream())
+    return lse, scal
+
+
 def ce_bwd(a, W, target, lse, scal):
     M, K = a.shape
     V = W.shape[0]

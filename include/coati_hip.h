@@ -101,6 +101,11 @@ int coati_gemm_ce_partial(const uint16_t* A, int64_t lda, const uint16_t* W, int
                           void* partial, void* stream);
 int coati_ce_finish(const void* partial, int tiles_n, const uint16_t* A, int64_t lda, const uint16_t* W,
                     int64_t ldw, const int64_t* target, float* lse, float* scal, int M, int K, int V, void* stream);
+/* The same with the row statistics kept in registers (K = 256): lse[M] comes out of the product itself, no per-tile array; above
+ * 65 536 rows the product runs as two launches on equal row ranges.  scal[0], scal[1] as coati_ce_finish.  tl[M] (may be NULL):
+ * scratch; when given the product also picks each row's target logit into it and the finish reads that instead of a dot product. */
+int coati_lmhead_ce_lse(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int V, int K, const int64_t* target,
+                        float* lse, float* tl, float* scal, void* stream);
 /* dlogits[M, n_store] (bf16) = (softmax(A W^T) - onehot(target)) / scal[1]; rows with target -1 are zero. */
 int coati_gemm_ce_bwd(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, int M, int V, int K,
                       uint16_t* dlogits, int64_t ldd, int n_store, const float* lse, const int64_t* target,
