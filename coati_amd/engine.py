@@ -82,11 +82,14 @@ class Engine:
         self.cfg = cfg
         self.device = torch.device(device)
         self.l = _lib.lib()
-        c = _lib.CoatiConfig(cfg.n_layer_xformer, cfg.n_layer_e3gnn, cfg.n_hidden_xformer, cfg.n_hidden_e3nn,
-                             cfg.n_embd_common, cfg.n_head, cfg.n_seq, cfg.n_tok, cfg.msg_cutoff, cfg.pad_token,
-                             cfg.stop_token, cfg.unk_token, 1 if cfg.fp8 else 0, 1 if cfg.norm_clips else 0,
-                             1 if cfg.token_mlp else 0, 1 if cfg.use_point_encoder else 0, 1 if cfg.biases else 0, 1 if cfg.norm_embed else 0,
-                             1 if cfg.torch_emb else 0, 1 if cfg.old_architecture else 0, 1 if cfg.residual else 0)
+        # by field name: the order of coati_config's fields is the header's alone
+        c = _lib.CoatiConfig(n_layer_xformer=cfg.n_layer_xformer, n_layer_e3gnn=cfg.n_layer_e3gnn, n_hidden_xformer=cfg.n_hidden_xformer,
+                             n_hidden_e3nn=cfg.n_hidden_e3nn, n_embd_common=cfg.n_embd_common, n_head=cfg.n_head, n_seq=cfg.n_seq,
+                             n_tok=cfg.n_tok, msg_cutoff=cfg.msg_cutoff, pad_token=cfg.pad_token, stop_token=cfg.stop_token,
+                             unk_token=cfg.unk_token, use_fp8=1 if cfg.fp8 else 0, norm_clips=1 if cfg.norm_clips else 0,
+                             token_mlp=1 if cfg.token_mlp else 0, use_point_encoder=1 if cfg.use_point_encoder else 0,
+                             biases=1 if cfg.biases else 0, norm_embed=1 if cfg.norm_embed else 0, torch_emb=1 if cfg.torch_emb else 0,
+                             old_architecture=1 if cfg.old_architecture else 0, residual=1 if cfg.residual else 0)
         h = ctypes.c_void_p()
         if cfg.enc_to_coati is None:
             _lib.check(self.l.coati_engine_create(ctypes.byref(c), ctypes.byref(h)), "coati_engine_create")

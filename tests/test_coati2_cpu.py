@@ -5,13 +5,11 @@ import ctypes
 import json
 import os
 import pickle
-import re
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden")
 
 
@@ -72,12 +70,10 @@ def test_tokenizer_pickles():
 
 
 def test_header_declares_and_library_exports_coati2_entries():
-    with open(os.path.join(ROOT, "include", "coati_hip.h")) as f:
-        header = f.read()
     from coati_amd import _lib
     l = _lib.lib()
     for name in ("coati_swiglu", "coati_engine_create_coati2", "coati_engine_token_head"):
-        assert re.search(r"\bint " + name + r"\(", header), name
+        assert name in _lib.PROTOTYPES and _lib.PROTOTYPES[name][0] is ctypes.c_int, name
         assert hasattr(l, name), name
         assert name in _lib.exported_symbols()
 

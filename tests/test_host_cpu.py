@@ -16,7 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_cabi_exports_every_declared_symbol():
     from coati_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "coati_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "coati_hip.h")).read(), flags=re.S)
+    # a count of its own, independent of the header reader the binding is made with (coati_amd/_abi.py): a prototype the reader cannot
+    # see is a failure here, not a gap in the binding
+    everything = re.findall(r"\b(coati_[a-z0-9_]+)\s*\(", hdr)
+    assert len(everything) == len(set(everything)) == len(_lib.PROTOTYPES) and set(everything) == set(_lib.PROTOTYPES)
     if os.environ.get("COATI_AMD_EXPERIMENTAL") != "1":
         hdr = re.sub(r"#ifdef COATI_EXPERIMENTAL.*?#endif", "", hdr, flags=re.S)      # operators of csrc/experimental/: not in the default library
     declared = set(re.findall(r"\b(coati_[a-z0-9_]+)\s*\(", hdr))
