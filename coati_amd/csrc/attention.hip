@@ -332,12 +332,10 @@ int launch_attn_fwd(const bf16_t* qkv, bf16_t* y, float* lse, int B, int T, int 
   COATI_CHECK_ARG(qkv && y && lse, "attn_fwd: null operand");
   COATI_CHECK_SHAPE(B > 0 && T > 0 && T <= 256 && n_head > 0 && (head_size == 16 || head_size == 32),
                     "attn_fwd: unsupported shape B=%d T=%d nh=%d hs=%d", B, T, n_head, head_size);
-  // round 6: head size 16, T <= 128 on 16-row causal granularity (attention16.hip); COATI_ATTN_BLOCK32=1 keeps the 32-row kernels for A/B runs
-  static const bool block32 = getenv("COATI_ATTN_BLOCK32") != nullptr;
-  if (head_size == 16 && T <= 128 && !block32) return launch_attn16_fwd(qkv, y, lse, B, T, n_head, s, seq_off, seq_ord);
+  // round 6: head size 16, T <= 128 on 16-row causal granularity (attention16.hip)
+  if (head_size == 16 && T <= 128) return launch_attn16_fwd(qkv, y, lse, B, T, n_head, s, seq_off, seq_ord);
   const int nb = (T + 31) / 32;
 #define FWD_CASE(H, N) if (head_size == H && nb == N) return launch_attn_fwd_t<H, N>(qkv, y, lse, B, T, n_head, s, seq_off);
-  FWD_CASE(16, 1) FWD_CASE(16, 2) FWD_CASE(16, 3) FWD_CASE(16, 4)
   FWD_CASE(32, 1) FWD_CASE(32, 2) FWD_CASE(32, 3) FWD_CASE(32, 4)
 #undef FWD_CASE
   return head_size == 16 ? launch_attn_fwd_t<16, 0>(qkv, y, lse, B, T, n_head, s, seq_off) : launch_attn_fwd_t<32, 0>(qkv, y, lse, B, T, n_head, s, seq_off);
@@ -804,32 +802,23 @@ int launch_attn_bwd(const bf16_t* qkv, const bf16_t* y, const bf16_t* dy, const 
   COATI_CHECK_ARG(qkv && y && dy && lse && dscratch && dqkv && cos_t && sin_t, "attn_bwd: null operand");
   COATI_CHECK_SHAPE(B > 0 && T > 0 && T <= 256 && n_head > 0 && (head_size == 16 || head_size == 32),
                     "attn_bwd: unsupported shape B=%d T=%d nh=%d hs=%d", B, T, n_head, head_size);
-  static const bool block32 = getenv("COATI_ATTN_BLOCK32") != nullptr;
-  if (head_size == 16 && T <= 128 && !block32) return launch_attn16_bwd(qkv, y, dy, lse, dqkv, cos_t, sin_t, B, T, n_head, s, seq_off, seq_ord);
-  // T <= 128: the single-sweep kernel (grande: 120 vs 141 us); longer sequences: the two kernels below
+  if (head_size == 16 && T <= 128) return launch_attn16_bwd(qkv, y, dy, lse, dqkv, cos_t, sin_t, B, T, n_head, s, seq_off, seq_ord);
+  // T <= 128, head size 32 only (head size 16 has returned above): the single-sweep kernel (grande: 120 vs 141 us); longer sequences: the
+  // two kernels below
   if (T <= 128) {
     const int nb = (T + 31) / 32;
     if (seq_off != nullptr) {   // packed rows: sequences of 1-2 blocks in one launch, of 3-4 blocks in another (ONE launch over 1-3 blocks, round 4: 2.44 vs 2.19 ms per step -- the short sequences lose the 4-workgroups-per-CU register budget)
 #define VL(H, HI, LO) return launch_attn_bwd_fused_varlen_t<H, HI, LO>(qkv, y, dy, lse, dqkv, cos_t, sin_t, B, T, n_head, s, seq_off)
 #define VL2(H, HI, LO) COATI_TRY((launch_attn_bwd_fused_varlen_t<H, HI, LO>(qkv, y, dy, lse, dqkv, cos_t, sin_t, B, T, n_head, s, seq_off)))
-      if (head_size == 16) {
-        if (nb == 1) VL(16, 1, 1);
-        if (nb == 2) VL(16, 2, 1);
-        VL2(16, 2, 1);
-        if (nb == 3) VL(16, 3, 3);
-        VL(16, 4, 3);
-      } else {
-        if (nb == 1) VL(32, 1, 1);
-        if (nb == 2) VL(32, 2, 1);
-        VL2(32, 2, 1);
-        if (nb == 3) VL(32, 3, 3);
-        VL(32, 4, 3);
-      }
+      if (nb == 1) VL(32, 1, 1);
+      if (nb == 2) VL(32, 2, 1);
+      VL2(32, 2, 1);
+      if (nb == 3) VL(32, 3, 3);
+      VL(32, 4, 3);
 #undef VL
 #undef VL2
     }
 #define FUSED_CASE(H, N) if (head_size == H && nb == N) return launch_attn_bwd_fused_t<H, N>(qkv, y, dy, lse, dqkv, cos_t, sin_t, B, T, n_head, s, seq_off);
-    FUSED_CASE(16, 1) FUSED_CASE(16, 2) FUSED_CASE(16, 3) FUSED_CASE(16, 4)
     FUSED_CASE(32, 1) FUSED_CASE(32, 2) FUSED_CASE(32, 3) FUSED_CASE(32, 4)
 #undef FUSED_CASE
   }

@@ -226,7 +226,6 @@ struct coati_engine {
   // side stream: the point encoder (independent of the transformer passes) runs concurrently with them
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool overlap = getenv("COATI_NO_OVERLAP") == nullptr;   // (A/B switch: the point encoder on the main stream)
   bool gnn_bwd_done = false;   // staged backward: stage 2 already ran the point-encoder backward on the side stream
   bool gnn_side_pending = false;   // stage 4 forked it; stage 5 joins
   // profiling
@@ -551,13 +550,8 @@ struct ProfScope {
 // write-out) serve 40 961 .. 57 344 rows; above 65 536 rows launch_gemm_nt falls back to the 32-row-slab and multi-round kernels and the
 // step is 8.5 % slower PER ROW (batch_sweep, round 5).  Every one of these products is row-wise, so M rows run as n launches of the fast form on
 // equal row ranges: the plan below (rows per launch; 0 = one launch as before) and gemm_rows() which advances every per-row operand.
-// COATI_ROW_SPLIT=0 switches it off (A/B).
-static bool row_split_on() {
-  static const bool on = []() { const char* v = getenv("COATI_ROW_SPLIT"); return !(v && v[0] == '0'); }();
-  return on;
-}
 static int row_split_plan(const GemmArgs& a, int a_f32, int epi) {
-  if (!row_split_on() || a.m_dev != nullptr || a_f32 || a.M <= 65536 || a.q8_out != nullptr) return 0;
+  if (a.m_dev != nullptr || a_f32 || a.M <= 65536 || a.q8_out != nullptr) return 0;
   if (!(a.K == 256 || a.N == 256)) return 0;
   if (epi != EPI_BF16 && epi != EPI_RES_F32 && epi != EPI_QKV_ROPE && epi != EPI_GELU_GRAD && epi != EPI_MUL_AUX && epi != EPI_CE_PARTIAL &&
       epi != EPI_CE_LSE && epi != EPI_CE_BWD && epi != EPI_CE_BWD_ROW && epi != EPI_LNBWD) return 0;
@@ -639,16 +633,6 @@ static bool lnbwd_rows_supported(const GemmArgs& a, int* nwg) {
   return true;
 }
 
-// A/B switch of the point encoder's fused forward edge launch (COATI_GNN_EDGE_FUSED=0: the three launches)
-static bool gnn_edge_fused_on() {
-  static const bool on = []() { const char* v = getenv("COATI_GNN_EDGE_FUSED"); return !(v && v[0] == '0'); }();
-  return on;
-}
-// A/B switch of the attention launch order (COATI_ATTN_LPT=0: sequences in batch order)
-static bool lpt_on() {
-  static const bool on = []() { const char* v = getenv("COATI_ATTN_LPT"); return !(v && v[0] == '0'); }();
-  return on;
-}
 int gemm(coati_engine* e, int site, const void* A, int a_f32, int64_t lda, const bf16_t* Bm, int64_t ldb, int M,
          int N, int K, void* Cm, int64_t ldc, const float* bias, int epi, const void* aux_in, void* aux_out,
          int64_t ld_aux, hipStream_t s) {
@@ -908,7 +892,7 @@ int xformer_fwd(coati_engine* e, XPass& p, const float* injection, hipStream_t s
       COATI_TRY(gemm8(e, SITE_QKV_FWD, w, 0, p.a1[l], C, M, 3 * C, C, a, EPI_QKV_ROPE, s));
       {
         ProfScope ps(e, SITE_ATTN_FWD, 4.0 * M * (double)p.T * C, s, (double)M * 4 * C * 2 + (double)M * c.n_head * 4);
-        COATI_TRY(launch_attn_fwd(p.qkv[l], p.y[l], p.lse[l], p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed && lpt_on() ? p.ord : nullptr));
+        COATI_TRY(launch_attn_fwd(p.qkv[l], p.y[l], p.lse[l], p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed ? p.ord : nullptr));
       }
       memset(&a, 0, sizeof(a));
       a.C = p.xmid[l]; a.ldc = C; a.bias = e->P + w.projb; a.aux_in = p.x[l]; a.ld_aux = C;
@@ -947,7 +931,7 @@ int xformer_fwd(coati_engine* e, XPass& p, const float* injection, hipStream_t s
     if (!ab) {
       {
         ProfScope ps(e, SITE_ATTN_FWD, 4.0 * M * (double)p.T * C, s, (double)M * 4 * C * 2 + (double)M * c.n_head * 4);   // qkv in, y + lse out
-        COATI_TRY(launch_attn_fwd(p.qkv[l], p.y[l], p.lse[l], p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed && lpt_on() ? p.ord : nullptr));
+        COATI_TRY(launch_attn_fwd(p.qkv[l], p.y[l], p.lse[l], p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed ? p.ord : nullptr));
       }
       COATI_TRY(gemm(e, SITE_PROJ_FWD, p.y[l], 0, C, e->S + w.projw, C, M, C, C, p.xmid[l], C, e->P + w.projb, EPI_RES_F32, p.x[l], nullptr, C, s));
     }
@@ -1207,7 +1191,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
     if (wg_each) COATI_TRY(wgrad(e, SITE_XF_WGRAD, dxb, 0, C, p.y[l], C, M, C, C, e->G + w.projw, C, e->G + w.projb, 0, s));
     {
       ProfScope ps(e, SITE_ATTN_BWD, 10.0 * M * (double)p.T * C, s, (double)M * 8 * C * 2 + (double)M * c.n_head * 8);   // qkv, y, dy in; dqkv out
-      COATI_TRY(launch_attn_bwd(p.qkv[l], p.y[l], e->dyb, p.lse[l], e->attnD, dqkv, e->cos_t, e->sin_t, p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed && lpt_on() ? p.ord : nullptr));
+      COATI_TRY(launch_attn_bwd(p.qkv[l], p.y[l], e->dyb, p.lse[l], e->attnD, dqkv, e->cos_t, e->sin_t, p.B, p.T, c.n_head, C / c.n_head, s, p.packed ? p.off : nullptr, p.packed ? p.ord : nullptr));
     }
     if (c.use_fp8) {
       GemmArgs a;
@@ -1266,7 +1250,7 @@ int gnn_fwd(coati_engine* e, const long long* atoms, const float* coords, hipStr
   for (int l = 0; l < Lg; ++l) {
     const GLayerP& w = e->gl[l];
     COATI_TRY(gemm(e, SITE_GNN_NODE_GEMM, e->g_hcat[l], 0, 2 * H, e->S + w.w1ab, H, BA, 2 * H, H, e->g_P[l], 2 * H, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
-    if (H == 256 && gnn_edge_fused_on()) {
+    if (H == 256) {
       // the three edge steps as ONE weight-resident launch (gemm_rb16.hip gnn_edge_fwd_fused_kernel): per edge the gathered sender row + bk + d2 + w
       // in, e1 and s2 out (once each, for the backward); per receiver its Pa row in, the segment sum out; the weight once
       ProfScope ps(e, SITE_GNN_EDGE_GEMM, 0, s, (double)BA * (H * 2 + 4 + H * 2) + (double)H * H * 2, (double)H * 2 + 12 + (double)H * 4, 2.0 * H * H + 6.0 * H);
@@ -1437,8 +1421,8 @@ int head_linear_bwd(coati_engine* e, SgemmBatch& sb, const float* dY, const floa
 
 int ensure_side(coati_engine* e) {
   if (e->side) return COATI_OK;
-  // (a high-priority side stream was tried in round 2: no change -- 34.8 ms either way; with COATI_NO_OVERLAP=1 the step
-  // takes 34.85 ms: the transformer's kernels hold every CU's LDS, so the point encoder's kernels run in their tails)
+  // (a high-priority side stream was tried in round 2: no change -- 34.8 ms either way; with the point encoder on the main
+  // stream the step takes 34.85 ms: the transformer's kernels hold every CU's LDS, so the point encoder's kernels run in their tails)
   if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) {
@@ -1768,30 +1752,18 @@ static int lmhead_ce_partial(coati_engine* e, hipStream_t s, int* tiles_v) {
 
 // The training forward's lm_head with the row statistics kept in registers (gemm_rb16.hip EPI_CE_LSE): lse[row] comes out of the product's
 // launch(es), the finish reads no per-tile array.  Taken where the 16-row-slab kernel would have taken the partial product (every launch of a
-// row split); COATI_CE_LSE=0 switches it off (A/B).
-static bool ce_lse_on() {
-  static const bool on = []() { const char* v = getenv("COATI_CE_LSE"); return !(v && v[0] == '0'); }();
-  return on;
-}
-// the target logit picked inside the product's launch (COATI_CE_PICK=0: recomputed by the finish as a dot product)
-static bool ce_pick_on() {
-  static const bool on = []() { const char* v = getenv("COATI_CE_PICK"); return !(v && v[0] == '0'); }();
-  return on;
-}
+// row split).  The product also picks the target logits: they go where the other path keeps its per-tile partials
 static GemmArgs lmhead_ce_lse_args(coati_engine* e) {
   const coati_config& c = e->cfg;
   const int C = c.n_hidden_xformer;
   GemmArgs a;
   memset(&a, 0, sizeof(a));
   a.A = e->p2.af; a.lda = C; a.B = e->S + e->lmhead; a.ldb = C; a.M = e->p2.M; a.N = c.n_tok; a.K = C; a.lse_out = e->ce_lse;
-  if (ce_pick_on()) {   // the target logits go where the other path keeps its per-tile partials
-    a.target = e->p2.packed ? e->p2.ypk : e->y_next;
-    a.tl_out = reinterpret_cast<float*>(e->ce_partial);
-  }
+  a.target = e->p2.packed ? e->p2.ypk : e->y_next;
+  a.tl_out = reinterpret_cast<float*>(e->ce_partial);
   return a;
 }
 static bool lmhead_ce_lse_taken(coati_engine* e) {
-  if (!ce_lse_on()) return false;
   const GemmArgs a = lmhead_ce_lse_args(e);
   const int rows = row_split_plan(a, 0, EPI_CE_LSE);
   for (long long r0 = 0; r0 < a.M; r0 += rows ? rows : a.M) {
@@ -1813,8 +1785,7 @@ static int lmhead_ce_lse(coati_engine* e, hipStream_t s) {
     ProfScope ps(e, SITE_LMHEAD_FWD, 2.0 * M2 * c.n_tok * C, s, (double)M2 * C * 2 + (double)c.n_tok * C * 2);   // logits never leave the chip
     COATI_TRY(gemm_rows(a, 0, EPI_CE_LSE, s));
   }
-  if (a.tl_out) return launch_ce_lse_finish_picked(a.target, e->ce_lse, a.tl_out, e->scal, M2, c.n_tok, s);
-  return launch_ce_lse_finish(e->p2.af, C, e->S + e->lmhead, C, e->p2.packed ? e->p2.ypk : e->y_next, e->ce_lse, e->scal, M2, C, c.n_tok, s);
+  return launch_ce_lse_finish_picked(a.target, e->ce_lse, a.tl_out, e->scal, M2, c.n_tok, s);
 }
 
 // lm_head + cross-entropy as an operator: lse[M] of A W^T through the same launches as the engine (gemm_rows: above 65 536 rows, two launches
@@ -1884,7 +1855,7 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
   HIPCHK(hipMemsetD32Async((hipDeviceptr_t)e->ones, 0x3f800000, B, s));   // ones[B] for bias column sums
 
   // ---- point encoder (clip_e2e.py:454-461): on the side stream, concurrent with the encoder pass ----
-  const bool ovl = e->overlap && (e->prof_mask == 0 || e->prof_keep_overlap) && c.use_point_encoder;
+  const bool ovl = (e->prof_mask == 0 || e->prof_keep_overlap) && c.use_point_encoder;
   if (!c.use_point_encoder) {
     // encode_points returns zeros (clip_e2e.py:462-463)
     HIPCHK(hipMemsetAsync(e->h_e3gnn, 0, (size_t)B * E * sizeof(float), s));
@@ -2304,7 +2275,7 @@ int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* 
   // stages 4 / 5 = the encoder stage in two halves (upper / lower half of the layers), so that the caller can start the
   // all-reduce of the upper layers' finished gradients underneath the lower half
   const int Lx = c.n_layer_xformer, Lmid = Lx / 2;
-  const bool ovl_bwd = (stage == 0 || stage == 2 || stage == 4) && e->overlap && (e->prof_mask == 0 || e->prof_keep_overlap) && c.use_point_encoder;
+  const bool ovl_bwd = (stage == 0 || stage == 2 || stage == 4) && (e->prof_mask == 0 || e->prof_keep_overlap) && c.use_point_encoder;
   if (stage == 0 || stage == 1) { e->gnn_bwd_done = false; e->gnn_side_pending = false; }
   if (ovl_bwd) {
     // the point-encoder backward only needs dhpoint (ready here) and writes its own gradient slice: side stream

@@ -1193,11 +1193,9 @@ static int launch_wgrad256_t(const WgradTile* dev_table, int n_tiles, hipStream_
 }
 
 // the single-problem split form of the 256-wide kernel: bf16 operands without a bias whose 256-wide tiles alone would leave most CUs idle
-// and whose 128-wide tiles need two rounds (the lm_head: dlogits[M, Vpad]^T a[M, 256], 41 tiles, 162 of the narrow ones).
-// COATI_WGRAD256_SPLIT=0 switches it off (A/B)
+// and whose 128-wide tiles need two rounds (the lm_head: dlogits[M, Vpad]^T a[M, 256], 41 tiles, 162 of the narrow ones)
 static bool wgrad256_split_taken(const WgradArgs& a) {
-  static const bool on = []() { const char* v = getenv("COATI_WGRAD256_SPLIT"); return !(v && v[0] == '0'); }();
-  if (!on || a.dbias != nullptr || a.m_dev != nullptr || a.K % 256 != 0 || a.N % 8 != 0) return false;
+  if (a.dbias != nullptr || a.m_dev != nullptr || a.K % 256 != 0 || a.N % 8 != 0) return false;
   if (40LL * a.lda >= (1LL << 30) || 40LL * a.ldb >= (1LL << 30)) return false;
   const int tiles128 = cdiv(a.N, BM) * cdiv(a.K, BN), tiles = cdiv(a.N, 256) * (a.K / 256);
   return tiles128 > 128 && tiles128 <= 256 && tiles >= 32;   // (few rows: slices of fewer stages, down to none -- those workgroups leave at once)

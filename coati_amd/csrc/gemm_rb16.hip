@@ -764,11 +764,9 @@ static int rb16_waves(int M) {
   const int slabs = (M + 15) / 16;
   return (slabs + 255) / 256;
 }
-// fewest waves per workgroup the kernel is chosen for (probe knob COATI_RB16_MINW, >= 8: load_tile covers a tile in 4 turns; default 9 = 36 865 rows)
-static int rb16_min_waves() {
-  static const int v = []() { const char* e = getenv("COATI_RB16_MINW"); const int w = e ? atoi(e) : 9; return w < 8 ? 8 : w; }();
-  return v;
-}
+// fewest waves per workgroup the kernel is chosen for: 9 = 36 865 rows (never below 8: load_tile covers a tile in 4 turns; every lower
+// threshold measured slower, profiles/r06_small_batch_thresholds.txt)
+constexpr int R16_MIN_WAVES = 9;
 
 bool gemm_rb16_supported(const GemmArgs& a, int a_f32, int epi) {
   if (a_f32 || a.K != R16_K || a.m_dev != nullptr) return false;
@@ -782,7 +780,7 @@ bool gemm_rb16_supported(const GemmArgs& a, int a_f32, int epi) {
   if (epi == EPI_QKV_ROPE && (a.rope_C % 32 != 0 || a.rope_pos != nullptr)) return false;   // 64-column tiles must not straddle 2C
   const int W = rb16_waves(a.M);
   if (epi == EPI_CE_LSE) return a.bias == nullptr && W <= R16_MAXW;   // no other kernel has it: any row count up to 65 536 (short workgroups are padded to 8 waves)
-  return W >= rb16_min_waves() && W <= R16_MAXW;   // 36 865 .. 65 536 rows: below, the 32-row kernel or the tiled one; above, the 32-row kernel
+  return W >= R16_MIN_WAVES && W <= R16_MAXW;   // 36 865 .. 65 536 rows: below, the 32-row kernel or the tiled one; above, the 32-row kernel
 }
 
 template <int EPI, bool LN>

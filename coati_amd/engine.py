@@ -48,10 +48,6 @@ class ModelConfig:
 ENC_TO_COATI = {"linear": 0, "swiglu_mlp": 1, "swiglu_resnet": 2}
 
 
-# COATI_PACK_ROWS=0 ignores the batches' packed-row counts: every step then runs on the padded [B, T] layout (A/B switch)
-import os as _os
-PACK_ROWS = _os.environ.get("COATI_PACK_ROWS", "1") != "0"
-
 SCAL_AR_SUM, SCAL_AR_COUNT, SCAL_CLIP1, SCAL_CLIP2, SCAL_NVALID, SCAL_GRADNORM, SCAL_ERR = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -259,7 +255,7 @@ class Engine:
         h_s = torch.empty(B, E, device=self.device, dtype=torch.float32)
         bad = torch.empty(B, device=self.device, dtype=torch.uint8)
         self._keep = (raw_tokens, tokens, atoms, coords, use_point, y_next)  # keep inputs alive until backward
-        if rows is not None and PACK_ROWS:
+        if rows is not None:
             r1, r2 = (int(x) for x in (rows.tolist() if isinstance(rows, torch.Tensor) else rows))   # keep the tensor on the host: a device tensor costs a sync
         else:
             r1 = r2 = 0
@@ -382,7 +378,7 @@ class Engine:
             assert weights.shape == (B,)
         self._ensure_workspace(B, T1, T2, 1)
         r1 = r2 = 0
-        if rows is not None and PACK_ROWS:
+        if rows is not None:
             r1, r2 = (int(x) for x in (rows.tolist() if isinstance(rows, torch.Tensor) else rows))
             if raw_tokens is None:
                 r1 = 0

@@ -506,3 +506,26 @@ def test_a_probe_build_does_not_pass_for_the_product(monkeypatch):
     assert not B.needs_build()
     monkeypatch.setattr(B, "FLAGS", B.FLAGS + ["-DR16_TURNS=3"])
     assert B.needs_build()
+
+
+def test_environment_table_lists_exactly_what_the_sources_read():
+    """INTEGRATION.md "Environment switches" against the sources: every COATI_* name that is a string literal argument of getenv( in
+    coati_amd/csrc/ or of os.environ.get( / os.environ[ in the package has a row, and no row names a variable nothing reads.  The default
+    library (csrc/ without experimental/) reads three: the two A/B switches whose other path a test runs as its reference, and the RCCL
+    path; a new switch there has to be argued for here."""
+    import glob
+    pkg = os.path.join(ROOT, "coati_amd")
+    cxx = {}
+    for ext in ("hip", "cpp", "h"):
+        for path in glob.glob(os.path.join(pkg, "csrc", "**", "*." + ext), recursive=True):
+            cxx[os.path.relpath(path, os.path.join(pkg, "csrc"))] = set(re.findall(r'\bgetenv\(\s*"(COATI_[A-Z0-9_]+)"', open(path).read()))
+    py = set()
+    for path in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
+        py |= set(re.findall(r'\b_?os\.environ(?:\.get\(|\[)\s*["\'](COATI_[A-Z0-9_]+)["\']', open(path).read()))
+    default_build = set().union(*(names for rel, names in cxx.items() if not rel.startswith("experimental" + os.sep)))
+    assert default_build == {"COATI_NO_TAIL", "COATI_NO_LNBWD_FUSE", "COATI_RCCL_LIB"}, sorted(default_build)
+    read = set().union(py, *cxx.values())
+    section = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    rows = [line.split("|")[1] for line in section.splitlines() if line.startswith("|")]
+    table = set(re.findall(r"COATI_[A-Z0-9_]+", " ".join(rows)))
+    assert table and read == table, (sorted(read - table), sorted(table - read))

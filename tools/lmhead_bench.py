@@ -1,5 +1,5 @@
 """The lm_head's three products at the bench's decoder-pass size, each timed alone: the forward (per-tile partials + finish against the
-row statistics kept in registers + finish), dlogits, and the weight gradient (COATI_WGRAD256_SPLIT=0: on 128-wide tiles).  COATI_T32=1 selects the 32-row-slab transposed kernel.   python tools/lmhead_bench.py [M] [V]"""
+row statistics kept in registers + finish), dlogits, and the weight gradient.  COATI_T32=1 selects the 32-row-slab transposed kernel.   python tools/lmhead_bench.py [M] [V]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -24,4 +24,4 @@ d = ops.ce_bwd(a, W, tgt, lse, scal)
 Vpad = d.shape[1]
 dW = torch.zeros(V, K, device=dev)
 wg_bytes = M * Vpad * 2 + M * K * 2 + V * K * 4
-row(f"lm_head wgrad       M={M} V={V}", timeit(lambda: ops.wgrad(d, a, dW, n_out=V)), 2.0 * M * Vpad * K, wg_bytes)   # (COATI_WGRAD256_SPLIT=0: the 128-wide kernel)
+row(f"lm_head wgrad       M={M} V={V}", timeit(lambda: ops.wgrad(d, a, dW, n_out=V)), 2.0 * M * Vpad * K, wg_bytes)
