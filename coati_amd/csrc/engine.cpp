@@ -133,7 +133,11 @@ struct coati_engine {
   int enc_to_coati = -1;
   struct Coati2Head { int64_t lnw = 0, lnb = 0, w1 = 0, b1 = 0, w2 = 0, b2 = 0; bool residual = false; } c2s, c2t;
   float* c2_u = nullptr;   // [B, 2E] scratch: the first Linear of a SwiGLU head
-  float* c2_du = nullptr;  // [B, 2E] its gradient (coati_engine_score_grad_coati2)
+  float* c2_du = nullptr;  // [B, 2E] its gradient (the head backward)
+  // What a SwiGLU head's forward leaves for its backward: LN(x) and its statistics, the first Linear's output, the SwiGLU's output.
+  // An engine that trains (c2_trains) carves one set per head -- a step needs both alive --, any other COATI2 engine points both at
+  // hs_ln / hs_mean / hs_rstd / c2_u / sa, which one head at a time uses
+  struct Coati2Save { float *ln = nullptr, *mean = nullptr, *rstd = nullptr, *u = nullptr, *g = nullptr; } c2s_sv, c2t_sv;
   // bound buffers
   float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;
   bf16_t* S = nullptr;
@@ -262,6 +266,11 @@ struct coati_engine {
 };
 
 namespace {
+
+// A COATI2 engine trains if and only if it was bound with gradient and both Adam buffers; bound without them it is inference-only and
+// every step entry refuses it, as it refuses a COATI1 engine of train = False where that one needs them
+bool c2_trains(const coati_engine* e) { return e->enc_to_coati >= 0 && e->G && e->Mo && e->Vo; }
+bool c2_refused(const coati_engine* e) { return e->enc_to_coati >= 0 && !c2_trains(e); }
 
 int64_t add_entry(coati_engine* e, const std::string& name, int rows, int cols) {
   const int64_t n = (int64_t)rows * (cols > 0 ? cols : 1);
@@ -737,7 +746,17 @@ size_t carve(coati_engine* e, Arena& ar, int B_, int T1_, int T2_, int A_, int B
   e->ones = ar.take<float>(B);
   e->stop_pos = ar.take<int>(B);
   e->err_flag = ar.take<int>(4);
-  if (e->enc_to_coati >= 0) { e->c2_u = ar.take<float>((size_t)B * 2 * E); e->c2_du = ar.take<float>((size_t)B * 2 * E); }
+  if (e->enc_to_coati >= 0) {
+    e->c2_u = ar.take<float>((size_t)B * 2 * E); e->c2_du = ar.take<float>((size_t)B * 2 * E);
+    e->c2s_sv.ln = e->hs_ln; e->c2s_sv.mean = e->hs_mean; e->c2s_sv.rstd = e->hs_rstd; e->c2s_sv.u = e->c2_u; e->c2s_sv.g = e->sa;
+    e->c2t_sv = e->c2s_sv;
+    if (c2_trains(e)) {   // (the linear smiles_to_coati keeps hs_ln / hs_mean / hs_rstd to itself: smiles_head_fwd)
+      for (coati_engine::Coati2Save* v : {&e->c2s_sv, &e->c2t_sv}) {
+        v->ln = ar.take<float>((size_t)B * C); v->mean = ar.take<float>(B); v->rstd = ar.take<float>(B);
+        v->u = ar.take<float>((size_t)B * 2 * E); v->g = ar.take<float>((size_t)B * E);
+      }
+    }
+  }
   // lm head
   const int tiles_v = cdiv(c.n_tok, 64);   // one (max, sum) pair per 64 columns: either GEMM kernel fits
   e->ce_partial = ar.take<float2>(M2 * tiles_v);
@@ -1483,15 +1502,46 @@ int smiles_head_fwd(coati_engine* e, float* out, hipStream_t s) {
 
 // a SwiGLU head of COATI2 (simple_coati2/transformer_only.py:19-42, 88-101) on [B, K] f32 rows x: LayerNorm -> Linear(K -> 2E) -> SwiGLU ->
 // Linear(E -> E) (+ x).  Every product is the exact-f32 sgemm without accumulation; the residual is a separate axpy (out must not overlap x)
-int coati2_head_fwd(coati_engine* e, const coati_engine::Coati2Head& h, const float* x, float* out, int B, hipStream_t s) {
+// sv: where LN(x), its statistics, the first Linear's output and the SwiGLU's output stay for coati2_head_bwd
+int coati2_head_fwd(coati_engine* e, const coati_engine::Coati2Head& h, const coati_engine::Coati2Save& sv, const float* x, float* out, int B,
+                    hipStream_t s) {
   const int C = e->cfg.n_hidden_xformer, E = e->cfg.n_embd_common;   // (E == C: the input width either way)
   const float* P = e->P;
-  COATI_TRY(launch_layernorm_fwd(x, C, P + h.lnw, P + h.lnb, nullptr, 0, e->hs_ln, C, e->hs_mean, e->hs_rstd, B, C, s));
-  COATI_TRY(launch_sgemm(e->hs_ln, C, 1, P + h.w1, 1, C, e->c2_u, 2 * E, B, 2 * E, C, P + h.b1, 1.f, 0, s));
-  COATI_TRY(launch_swiglu(e->c2_u, 2 * E, e->sa, E, B, E, s));
-  COATI_TRY(launch_sgemm(e->sa, E, 1, P + h.w2, 1, E, out, E, B, E, E, P + h.b2, 1.f, 0, s));
+  COATI_TRY(launch_layernorm_fwd(x, C, P + h.lnw, P + h.lnb, nullptr, 0, sv.ln, C, sv.mean, sv.rstd, B, C, s));
+  COATI_TRY(launch_sgemm(sv.ln, C, 1, P + h.w1, 1, C, sv.u, 2 * E, B, 2 * E, C, P + h.b1, 1.f, 0, s));
+  COATI_TRY(launch_swiglu(sv.u, 2 * E, sv.g, E, B, E, s));
+  COATI_TRY(launch_sgemm(sv.g, E, 1, P + h.w2, 1, E, out, E, B, E, E, P + h.b2, 1.f, 0, s));
   if (h.residual) COATI_TRY(launch_axpy(x, out, 1.f, (long long)B * E, s));
   return COATI_OK;
+}
+
+// The backward of a SwiGLU head behind coati2_head_fwd(h, sv, x, ...) of the same call: for y = Linear2(SwiGLU(Linear1(LN(x)))) and dy [B, E],
+//   dg = dy W2 ; du = swiglu_bwd(u, dg) ; dln = du W1 ; dx = (dres or 0) + LN-backward(dln)
+// dres carries whatever else flows into x -- dy itself for a head with the residual -- and may be dx.  wgrad: also dW2 += dy^T g,
+// db2 += colsum(dy), dW1 += du^T LN(x), db1 += colsum(du) and the LayerNorm's dgamma / dbeta into the gradient buffer (the three products
+// of a Linear share a launch: head_linear_bwd); without it no address inside the gradient buffer is formed (it may be null).  Exact-f32
+// products as in the forward; scratch: dsa, c2_du, dhs_ln
+int coati2_head_bwd(coati_engine* e, const coati_engine::Coati2Head& h, const coati_engine::Coati2Save& sv, const float* x, const float* dy,
+                    const float* dres, float* dx, int B, bool wgrad, hipStream_t s) {
+  const int C = e->cfg.n_hidden_xformer, E = e->cfg.n_embd_common;
+  const float* P = e->P;
+  if (wgrad) {
+    SgemmBatch sb;
+    COATI_TRY(head_linear_bwd(e, sb, dy, sv.g, h.w2, h.b2, e->dsa, B, E, E));
+    COATI_TRY(launch_sgemm_batch(sb, s));
+  } else {
+    COATI_TRY(launch_sgemm(dy, E, 1, P + h.w2, E, 1, e->dsa, E, B, E, E, nullptr, 1.f, 0, s));                 // dg[b,k] = sum_n dy[b,n] W2[n,k]
+  }
+  COATI_TRY(launch_swiglu_bwd(sv.u, 2 * E, e->dsa, E, e->c2_du, 2 * E, B, E, s));
+  if (wgrad) {
+    SgemmBatch sb;
+    COATI_TRY(head_linear_bwd(e, sb, e->c2_du, sv.ln, h.w1, h.b1, e->dhs_ln, B, 2 * E, C));
+    COATI_TRY(launch_sgemm_batch(sb, s));
+  } else {
+    COATI_TRY(launch_sgemm(e->c2_du, 2 * E, 1, P + h.w1, C, 1, e->dhs_ln, C, B, C, 2 * E, nullptr, 1.f, 0, s));  // dln[b,k] = sum_n du[b,n] W1[n,k]
+  }
+  return launch_layernorm_bwd(e->dhs_ln, 1, C, x, C, 0, sv.mean, sv.rstd, P + h.lnw, dres, dx, nullptr, wgrad ? e->G + h.lnw : nullptr,
+                              wgrad ? e->G + h.lnb : nullptr, wgrad ? e->ln_partial : nullptr, B, C, s);
 }
 
 // ---- what the C-ABI entries share: an entry is its argument checks, begin_call, and a short list of the stages below ----------
@@ -1537,7 +1587,7 @@ int stop_rows_head_fwd(coati_engine* e, float* out, hipStream_t s) {
   const int C = e->cfg.n_hidden_xformer;
   if (p.tail) HIPCHK(hipMemcpyAsync(e->hstop, p.t_xf, (size_t)p.B * C * sizeof(float), hipMemcpyDeviceToDevice, s));
   else COATI_TRY(launch_gather_rows(p.xf32, e->stop_pos, e->hstop, p.B, p.T, C, s, p.packed ? p.off : nullptr));
-  if (e->enc_to_coati > 0) return coati2_head_fwd(e, e->c2s, e->hstop, out, p.B, s);   // COATI2 SwiGLU smiles_to_coati
+  if (e->enc_to_coati > 0) return coati2_head_fwd(e, e->c2s, e->c2s_sv, e->hstop, out, p.B, s);   // COATI2 SwiGLU smiles_to_coati
   return smiles_head_fwd(e, out, s);
 }
 // encode_tokens (clip_e2e.py:448-452): the [STOP] positions, the encoder pass over e->p1.idx, the head
@@ -1827,9 +1877,11 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
                          const int64_t* raw_tokens, const int64_t* tokens, const int64_t* y_next,
                          const int64_t* atoms, const float* coords, const uint8_t* use_point, float* h_e3gnn,
                          float* h_smiles, uint8_t* bad_rows, float* scal, int train, int64_t rows1, int64_t rows2, void* stream) {
-  COATI_CHECK_ARG(e && e->P && e->S, "engine_forward: engine not bound");
-  COATI_CHECK_ARG(workspace && raw_tokens && tokens && atoms && coords && use_point && scal, "engine_forward: null argument");
-  COATI_CHECK_ARG(e->enc_to_coati < 0, "engine_forward: a COATI2 engine is inference-only (no training step)");
+  COATI_CHECK_ARG(e && !c2_refused(e), "engine_forward: a COATI2 engine bound without gradient and Adam buffers is inference-only (no training step)");
+  COATI_CHECK_ARG(e->P && e->S, "engine_forward: engine not bound");
+  const bool c2 = e->enc_to_coati >= 0;   // COATI2: no point encoder -- atoms / coords / use_point may be null, A is ignored
+  if (c2) A = 1;
+  COATI_CHECK_ARG(workspace && raw_tokens && tokens && (c2 || (atoms && coords && use_point)) && scal, "engine_forward: null argument");
   const bool stop_after_heads = (train & 2) != 0;   // train | 2: return behind the heads, coati_engine_forward_decoder runs the rest
   train &= 1;
   COATI_CHECK_ARG(!train || (e->G && y_next), "engine_forward: training needs grads and y_next");
@@ -1878,13 +1930,18 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
   COATI_TRY(point_head_fwd(e, e->h_e3gnn, s));
   // ---- smiles_to_clip ----
   COATI_TRY(stop_rows_head_fwd(e, e->h_smiles, s));
-  // ---- special token (clip_e2e.py:800-808) of either embedding: one batched launch ----
-  const float *ptok = nullptr, *stok = nullptr;
-  SgemmBatch sb;
-  COATI_TRY(special_token_add(e, sb, e->h_e3gnn, e->sa, e->ptok, &ptok, s));
-  COATI_TRY(special_token_add(e, sb, e->h_smiles, e->sb, e->stok, &stok, s));
-  COATI_TRY(launch_sgemm_batch(sb, s));
-  COATI_TRY(launch_select_rows(use_point, ptok, stok, e->cliptok, B, E, s));
+  if (c2) {
+    // ---- COATI2: the injected token is coati_to_token(h_coati) (transformer_only.py:144, 177) ----
+    COATI_TRY(coati2_head_fwd(e, e->c2t, e->c2t_sv, e->h_smiles, e->cliptok, B, s));
+  } else {
+    // ---- special token (clip_e2e.py:800-808) of either embedding: one batched launch ----
+    const float *ptok = nullptr, *stok = nullptr;
+    SgemmBatch sb;
+    COATI_TRY(special_token_add(e, sb, e->h_e3gnn, e->sa, e->ptok, &ptok, s));
+    COATI_TRY(special_token_add(e, sb, e->h_smiles, e->sb, e->stok, &stok, s));
+    COATI_TRY(launch_sgemm_batch(sb, s));
+    COATI_TRY(launch_select_rows(use_point, ptok, stok, e->cliptok, B, E, s));
+  }
   if (bad_rows) COATI_TRY(launch_bad_rows(e->p2.idx, bad_rows, B, T2, s));
   if (h_e3gnn) HIPCHK(hipMemcpyAsync(h_e3gnn, e->h_e3gnn, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (h_smiles) HIPCHK(hipMemcpyAsync(h_smiles, e->h_smiles, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1898,7 +1955,7 @@ int coati_engine_forward(coati_engine* e, void* workspace, int64_t workspace_byt
 }
 
 int coati_engine_forward_decoder(coati_engine* e, void* stream) {
-  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_forward_decoder: a COATI2 engine is inference-only (no training step)");
+  COATI_CHECK_ARG(e && !c2_refused(e), "engine_forward_decoder: a COATI2 engine bound without gradient and Adam buffers is inference-only (no training step)");
   COATI_CHECK_ARG(e->decoder_pending, "engine_forward_decoder: no forward stopped behind the heads (train | 2)");
   e->decoder_pending = false;
   return forward_decoder_impl(e, (hipStream_t)stream);
@@ -1948,7 +2005,7 @@ int coati_engine_token_head(coati_engine* e, void* workspace, int64_t workspace_
   const char *ph = reinterpret_cast<const char*>(h), *pt = reinterpret_cast<const char*>(h_token);
   COATI_CHECK_ARG(ph + bytes <= pt || pt + bytes <= ph, "engine_token_head: h_token must not overlap h");
   COATI_TRY(begin_call(e, "engine_token_head", workspace, workspace_bytes, B, 1, 1, 1, nullptr));
-  return coati2_head_fwd(e, e->c2t, h, h_token, B, (hipStream_t)stream);
+  return coati2_head_fwd(e, e->c2t, e->c2t_sv, h, h_token, B, (hipStream_t)stream);
 }
 
 // Likelihood scoring (clip_e2e.py:634-665 hclip_and_tokens_to_likelihood, :667-742 batch_smiles_to_s2s_likelihood): the embedding --
@@ -1991,10 +2048,10 @@ static int score_forward(coati_engine* e, const char* entry, bool coati2, void* 
     hclip = e->h_smiles;
   }
   // ---- special token: point_clip_to_special_tokens (clip_e2e.py:432-437), COATI2: coati_to_token (its LayerNorm's statistics and
-  // the first Linear's output stay in hs_mean / hs_rstd / hs_ln / c2_u for coati2_token_head_bwd) ----
+  // the first Linear's output stay in c2t_sv for coati2_token_head_bwd) ----
   const float* inj = nullptr;
   if (coati2) {
-    COATI_TRY(coati2_head_fwd(e, e->c2t, hclip, e->stok, B, s));
+    COATI_TRY(coati2_head_fwd(e, e->c2t, e->c2t_sv, hclip, e->stok, B, s));
     inj = e->stok;
   } else {
     SgemmBatch sb;
@@ -2085,24 +2142,18 @@ int coati_engine_score_coati2(coati_engine* e, void* workspace, int64_t workspac
   return publish_errors(e, scal, s);
 }
 
-// coati_to_token's backward to its input alone, behind coati2_head_fwd(e->c2t, ...) of the same call (hs_ln holds LN(h), hs_mean / hs_rstd
-// its statistics, c2_u the first Linear's output): for x -> LN -> Linear(E -> 2E) -> SwiGLU -> Linear(E -> E) + x and dtok [B, E],
-// dsa = dtok W2 ; du = swiglu_bwd(u, dsa) ; dln = du W1 ; dh = dtok + LN-backward(dln).  Exact-f32 products, no parameter gradient
+// coati_to_token's backward to its input alone, behind coati2_head_fwd(e->c2t, ...) of the same call: dh = dtok + the head's input
+// gradient (SwiGLUResNet: the residual), no parameter gradient
 static int coati2_token_head_bwd(coati_engine* e, const float* h, const float* dtok, float* dh, int B, hipStream_t s) {
-  const int E = e->cfg.n_embd_common;
-  const coati_engine::Coati2Head& t = e->c2t;
-  const float* P = e->P;
-  COATI_TRY(launch_sgemm(dtok, E, 1, P + t.w2, E, 1, e->dsa, E, B, E, E, nullptr, 1.f, 0, s));              // dsa[b,k] = sum_n dtok[b,n] W2[n,k]
-  COATI_TRY(launch_swiglu_bwd(e->c2_u, 2 * E, e->dsa, E, e->c2_du, 2 * E, B, E, s));
-  COATI_TRY(launch_sgemm(e->c2_du, 2 * E, 1, P + t.w1, E, 1, e->dhs_ln, E, B, E, 2 * E, nullptr, 1.f, 0, s));  // dln[b,k] = sum_n du[b,n] W1[n,k]
-  return launch_layernorm_bwd(e->dhs_ln, 1, E, h, E, 0, e->hs_mean, e->hs_rstd, P + t.lnw, dtok, dh, nullptr, nullptr, nullptr, nullptr, B, E, s);
+  return coati2_head_bwd(e, e->c2t, e->c2t_sv, h, dtok, dtok, dh, B, false, s);
 }
 
 // The COATI2 likelihood's gradient w.r.t. the embedding: coati_engine_score_grad with COATI2's token head.  nll as
 // coati_engine_score_coati2(h_coati = ...) gives it (the same bits), dh_coati[b] = weights[b] * d nll[b] / d h_coati[b] through the decoder
 // pass and coati_to_token, summed over the [UNK] positions of row b.  Launches: the scoring forward; dlogits with the per-row factor; the
 // lm_head's and the layers' input gradients; the [UNK] rows' gather; coati2_token_head_bwd.  The model is a constant: no parameter
-// gradient is formed and nothing of the engine's parameters moves (COATI2 engines are forward-only); have_fwd stays false.
+// gradient is formed and nothing of the engine's parameters, gradients or Adam state moves, on an engine that trains too; have_fwd
+// stays false.
 int coati_engine_score_grad_coati2(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_coati,
                                    const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll,
                                    float* dh_coati, float* scal, void* stream) {
@@ -2152,7 +2203,7 @@ int coati_engine_decoder_logits(coati_engine* e, void* workspace, int64_t worksp
 }
 
 int coati_engine_logits(coati_engine* e, float* logits, int64_t ldl, void* stream) {
-  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_logits: a COATI2 engine is inference-only (no training forward)");
+  COATI_CHECK_ARG(e && !c2_refused(e), "engine_logits: a COATI2 engine bound without gradient and Adam buffers is inference-only (no training forward)");
   COATI_CHECK_ARG(e->have_fwd && logits, "engine_logits: no forward to read");
   COATI_CHECK_ARG(!e->p2.packed, "engine_logits: the last forward ran on packed rows (logits of padded positions do not exist): run it with rows1 = rows2 = 0");
   return pass_logits(e, SITE_LMHEAD_FWD, logits, ldl, (hipStream_t)stream);
@@ -2203,9 +2254,11 @@ int coati_engine_infonce(coati_engine* e, const float* S_loc, const float* C_loc
 }
 
 int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* dh_e3gnn, int stage, void* stream) {
-  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "engine_backward: a COATI2 engine is inference-only (no backward)");
+  COATI_CHECK_ARG(e && !c2_refused(e), "engine_backward: a COATI2 engine bound without gradient and Adam buffers is inference-only (no backward)");
   COATI_CHECK_ARG(e->have_fwd && e->G, "engine_backward: no forward / gradient buffer");
   COATI_CHECK_ARG(stage >= 0 && stage <= 5, "engine_backward: bad stage");
+  const bool c2 = e->enc_to_coati >= 0;
+  COATI_CHECK_ARG(!c2 || dh_e3gnn == nullptr, "engine_backward: a COATI2 engine has no point encoder (dh_e3gnn must be null)");
   hipStream_t s = (hipStream_t)stream;
   const coati_config& c = e->cfg;
   const int C = c.n_hidden_xformer, H = c.n_hidden_e3nn, E = c.n_embd_common, B = e->B;
@@ -2229,8 +2282,15 @@ int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* 
     else HIPCHK(hipMemsetAsync(e->dhe, 0, (size_t)B * E * sizeof(float), s));
     if (dh_smiles) HIPCHK(hipMemcpyAsync(e->dhs, dh_smiles, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
     else HIPCHK(hipMemsetAsync(e->dhs, 0, (size_t)B * E * sizeof(float), s));
+    if (c2) {
+      // ---- COATI2: coati_to_token's backward with its parameter gradients; dhs = dh_smiles + dcliptok (the residual) + the head's
+      // input gradient.  Then smiles_to_coati: the SwiGLU variants here (swiglu_resnet: dhs flows on into dhstop), the linear one below ----
+      COATI_TRY(launch_axpy(e->dcliptok, e->dhs, 1.f, (long long)B * E, s));
+      COATI_TRY(coati2_head_bwd(e, e->c2t, e->c2t_sv, e->h_smiles, e->dcliptok, e->dhs, e->dhs, B, true, s));
+      if (e->enc_to_coati > 0)
+        COATI_TRY(coati2_head_bwd(e, e->c2s, e->c2s_sv, e->hstop, e->dhs, e->c2s.residual ? e->dhs : nullptr, e->dhstop, B, true, s));
+    } else if (c.token_mlp) {
     // ---- special-token head: cliptok = where(use_point, ptok, stok) ----
-    if (c.token_mlp) {
       HIPCHK(hipMemsetAsync(e->dptok, 0, (size_t)B * E * sizeof(float), s));
       HIPCHK(hipMemsetAsync(e->dstok, 0, (size_t)B * E * sizeof(float), s));
       COATI_TRY(launch_select_rows_bwd(e->use_point, e->dcliptok, e->dptok, e->dstok, B, E, s));
@@ -2246,6 +2306,7 @@ int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* 
     }
     // smiles_to_clip / point_to_clip: Linear then (norm_clips) LayerNorm backward; the two heads' Linear backwards share a launch
     const bool old_arch = c.norm_clips && c.old_architecture;
+    if (e->enc_to_coati <= 0) {   // (a SwiGLU smiles_to_coati of COATI2 has run its backward above; the linear one is the norm_clips head)
     if (old_arch) {
       // Linear -> LayerNorm: the LayerNorm's backward first (x = the Linear's output kept in hs_ln / hp_ln), its result in dhs_ln / dhp_ln
       COATI_TRY(launch_layernorm_bwd(e->dhs, 1, E, e->hs_ln, E, 0, e->hs_mean, e->hs_rstd, e->P + e->s2c_lnw, nullptr, e->dhs_ln, nullptr, e->G + e->s2c_lnw, e->G + e->s2c_lnb, e->ln_partial, B, E, s));
@@ -2268,6 +2329,7 @@ int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* 
       COATI_TRY(launch_layernorm_bwd(e->dhs_ln, 1, C, e->hstop, C, 0, e->hs_mean, e->hs_rstd, e->P + e->s2c_lnw, nullptr, e->dhstop, nullptr, e->G + e->s2c_lnw, e->G + e->s2c_lnb, e->ln_partial, B, C, s));
       if (c.use_point_encoder)
         COATI_TRY(launch_layernorm_bwd(e->dhp_ln, 1, H, e->hpoint, H, 0, e->hp_mean, e->hp_rstd, e->P + e->p2c_lnw, nullptr, e->dhpoint, nullptr, e->G + e->p2c_lnw, e->G + e->p2c_lnb, e->ln_partial, B, H, s));
+    }
     }
   }
   // whole backward (stage 0) or the encoder stage of the staged (multi-GPU) backward: the point-encoder backward runs on
@@ -2310,7 +2372,7 @@ int coati_engine_backward(coati_engine* e, const float* dh_smiles, const float* 
 
 int coati_engine_optimizer_step(coati_engine* e, float lr, float beta1, float beta2, float eps, float weight_decay,
                                 float max_norm, int step, float* scal, void* stream) {
-  COATI_CHECK_ARG(e && e->enc_to_coati < 0, "optimizer_step: a COATI2 engine is inference-only (no optimizer step)");
+  COATI_CHECK_ARG(e && !c2_refused(e), "optimizer_step: a COATI2 engine bound without gradient and Adam buffers is inference-only (no optimizer step)");
   COATI_CHECK_ARG(e->P && e->G && e->Mo && e->Vo && scal, "optimizer_step: engine not bound for training");
   COATI_CHECK_ARG(e->have_fwd, "optimizer_step: needs the workspace of a forward call");
   hipStream_t s = (hipStream_t)stream;

@@ -41,7 +41,8 @@ class ModelConfig:
     old_architecture: bool = False   # True (with norm_clips): the two clip heads are Linear -> LayerNorm instead of LayerNorm -> Linear (clip_e2e.py:409-417)
     residual: bool = False   # True: every node MLP also sees the one-hot node features (e3gnn_clip.py:97-100, e_gcl_sparse.py:141, 282-290)
     # COATI2 (simple_coati2/transformer_only.py:43-104): "linear" / "swiglu_mlp" / "swiglu_resnet" selects smiles_to_coati, None = COATI1.
-    # A COATI2 engine is inference-only (encode, token_head, decode); the point-encoder and clip-head fields above do not apply
+    # Engine(cfg, train=True) on a COATI2 layout trains (forward / backward / optimizer_step with atoms = coords = use_point = None: AR loss
+    # only); with train=False it is inference-only (encode, token_head, decode, scoring).  The point-encoder and clip-head fields above do not apply
     enc_to_coati: Optional[str] = None
 
 
@@ -69,6 +70,14 @@ def pack_prompts(prefix: List[List[int]], n_seq: int):
 
 
 ERR_Z_MESSAGE = "torch_emb: an atomic number above 83 has no row in nn.Embedding(84, H) (e3gnn_clip.py:113-115)"
+
+
+def _coati2_step(cfg, do_clip):
+    """True on a COATI2 layout, whose step is the AR loss (+ an external dh_coati): there is no contrastive head, do_clip=True raises"""
+    c2 = getattr(cfg, "enc_to_coati", None) is not None
+    if c2 and do_clip:
+        raise ValueError("a COATI2 engine has no contrastive head: call with do_clip=False (an external head feeds dh_coati)")
+    return c2
 
 
 class Engine:
@@ -234,19 +243,24 @@ class Engine:
         self._ensure_workspace(B, T1, T2, A)
         return True
 
-    def forward(self, raw_tokens, tokens, atoms, coords, use_point, y_next=None, train=True, rows=None, stop_after_heads=False):
+    def forward(self, raw_tokens, tokens, atoms=None, coords=None, use_point=None, y_next=None, train=True, rows=None, stop_after_heads=False):
         """forward_dist (+ AR loss sums when y_next is given).  Returns (h_e3gnn, h_smiles, bad_rows).
+        A COATI2 engine built with train=True takes atoms = coords = use_point = None: h_smiles is h_coati (smiles_to_coati of the
+        encoder pass), coati_to_token of it is injected, h_e3gnn is zeros.
         stop_after_heads: return as soon as the embeddings are final; forward_decoder() then enqueues the decoder pass + lm_head
         (the contrastive head can run on another stream in between, see train_step).
         rows = (rows1, rows2): run both transformer passes on PACKED rows -- the rows' real prefixes only, counts from
         coati_amd.synthetic.packed_rows / the batch assembler (host ints); None = the padded layout (needed by logits())."""
         B, T1 = raw_tokens.shape
         T2 = tokens.shape[1]
-        A = atoms.shape[1]
-        for t in (raw_tokens, tokens, atoms):
+        if self.cfg.enc_to_coati is not None and atoms is None and coords is None and use_point is None:
+            A = 1
+        else:
+            A = atoms.shape[1]
+            coords = coords.to(torch.float32).contiguous()
+            use_point = use_point.to(torch.uint8).contiguous()
+        for t in (raw_tokens, tokens) + ((atoms,) if atoms is not None else ()):
             assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous()
-        coords = coords.to(torch.float32).contiguous()
-        use_point = use_point.to(torch.uint8).contiguous()
         if y_next is not None:
             y_next = y_next.contiguous()
         self._ensure_workspace(B, T1, T2, A)
@@ -477,10 +491,22 @@ class Engine:
     def token_entropy_unit(self):
         return math.log(float(self.cfg.n_tok)) / math.log(2.0)
 
-    def train_step(self, batch, use_point, lr, do_clip=True, clip_weight=None, optimizer=True, head="infonce", **opt_kw):
+    def train_step(self, batch, use_point, lr, do_clip=True, clip_weight=None, optimizer=True, head="infonce", dh_coati=None, **opt_kw):
         """One single-GPU do_minibatch (train_coati.py:216-277).  Losses stay on the device in self.scal.
         head: "infonce" (clip_e2e.py:27-47) or "barlow" (BASELINE configs[3]; parity unpinned, see barlow.py).
-        opt_kw: weight_decay / max_norm / betas / eps forwarded to optimizer_step (train_coati.py:145-151, 276)."""
+        opt_kw: weight_decay / max_norm / betas / eps forwarded to optimizer_step (train_coati.py:145-151, 276).
+        COATI2 engine (train=True): batch = {raw_tokens, tokens, y_next[, rows]}, use_point = None, do_clip=False (True raises
+        ValueError); dh_coati [B, E] (optional) is an external gradient w.r.t. h_coati added in the backward.  Returns (zeros, h_coati, bad)."""
+        if _coati2_step(self.cfg, do_clip):
+            h_e, h_s, bad = self.forward(batch["raw_tokens"], batch["tokens"], y_next=batch["y_next"], train=True, rows=batch.get("rows"))
+            if dh_coati is not None:
+                dh_coati = dh_coati.to(self.device, torch.float32).contiguous()
+                assert dh_coati.shape == h_s.shape, dh_coati.shape
+            self.backward(dh_coati, None, 0)
+            if optimizer:
+                self.optimizer_step(lr, **opt_kw)
+            return h_e, h_s, bad
+        assert dh_coati is None, "dh_coati belongs to a COATI2 engine"
         h_e, h_s, bad = self.forward(batch["raw_tokens"], batch["tokens"], batch["atoms"], batch["coords"], use_point,
                                      y_next=batch["y_next"], train=True, rows=batch.get("rows"), stop_after_heads=True)
         w = self.token_entropy_unit() if clip_weight is None else clip_weight
@@ -502,7 +528,10 @@ class Engine:
         return h_e, h_s, bad
 
     def eval_step(self, batch, use_point, do_clip=True):
-        """Forward + both losses, no backward (the reference's test partition runs under torch.no_grad())."""
+        """Forward + both losses, no backward (the reference's test partition runs under torch.no_grad()).  COATI2 engine
+        (train=True): use_point = None, do_clip=False; the AR loss alone."""
+        if _coati2_step(self.cfg, do_clip):
+            return self.forward(batch["raw_tokens"], batch["tokens"], y_next=batch["y_next"], train=False, rows=batch.get("rows"))
         h_e, h_s, bad = self.forward(batch["raw_tokens"], batch["tokens"], batch["atoms"], batch["coords"], use_point,
                                      y_next=batch["y_next"], train=False, rows=batch.get("rows"))
         if do_clip:

@@ -1,5 +1,6 @@
-"""COATI2's inference model (simple_coati2/transformer_only.py:19-200) with the reference's constructor, state_dict names and
-methods.  The transformer, both heads and generation run in libcoati_hip.so through coati_amd.engine.Engine; this file adapts the
+"""COATI2's model (simple_coati2/transformer_only.py:19-200) with the reference's constructor, state_dict names and methods;
+trainable=True adds the training step the reference does not have (Engine.train_step on a COATI2 layout: AR loss, clip-norm, AdamW).
+The transformer, both heads and generation run in libcoati_hip.so through coati_amd.engine.Engine; this file adapts the
 calling convention.  SwiGLU / SwiGLUResNet are the reference's torch modules, kept for code that builds them directly."""
 import torch
 import torch.nn as nn
@@ -40,13 +41,19 @@ def _is_layernorm(name):
 
 
 class COATI_Smiles_Inference(nn.Module):
-    """Drop-in for coati.models.simple_coati2.transformer_only.COATI_Smiles_Inference.  Inference only: no dropout (mlp_dropout is
-    recorded), and the model's special ids (default: the coati2_12_12 vocabulary's [PAD] / [STOP] / [UNK]) must be the tokenizer's."""
+    """Drop-in for coati.models.simple_coati2.transformer_only.COATI_Smiles_Inference.  No dropout (mlp_dropout is recorded), and the
+    model's special ids (default: the coati2_12_12 vocabulary's [PAD] / [STOP] / [UNK]) must be the tokenizer's.
+    trainable=False (default): a forward-only engine -- no gradient or Adam buffers, every step entry refuses.  trainable=True: the
+    engine is built with train=True, every parameter carries its slice of the gradient buffer as .grad (as e3gnn_smiles_clip_e2e),
+    model.engine.train_step(batch, None, lr, do_clip=False) runs a step and forward() returns (h_coati, logits); mlp_dropout > 0 raises
+    NotImplementedError there (a training step with dropout is not implemented)."""
 
     def __init__(self, n_layer_xformer=16, n_hidden_xformer=256, embed_dim=256, n_head=16, n_seq=80, mlp_dropout=0.0,
                  enc_to_coati="linear", n_direct_clr=64, n_tok=4, biases=True, device=torch.device("cuda:0"), dtype=torch.float, *,
-                 pad_token: int = 31, stop_token: int = 40, unk_token: int = 44):
+                 pad_token: int = 31, stop_token: int = 40, unk_token: int = 44, trainable: bool = False):
         super().__init__()
+        if trainable and mlp_dropout > 0:
+            raise NotImplementedError(f"trainable=True with mlp_dropout={mlp_dropout}: the training step has no dropout")
         if dtype not in (torch.float, torch.float32):
             raise NotImplementedError("parameters are fp32 (bf16 is an internal operand format)")
         device = torch.device(device)
@@ -57,14 +64,19 @@ class COATI_Smiles_Inference(nn.Module):
         self.n_direct_clr = n_direct_clr
         self.mlp_dropout = mlp_dropout
         self.device = device
+        self.trainable = bool(trainable)
+        # the constructor arguments a checkpoint document records (save_coati2)
+        self.model_kwargs = dict(n_layer_xformer=n_layer_xformer, n_hidden_xformer=n_hidden_xformer, embed_dim=embed_dim, n_head=n_head, n_seq=n_seq,
+                                 mlp_dropout=mlp_dropout, enc_to_coati=enc_to_coati, n_direct_clr=n_direct_clr, n_tok=n_tok, biases=biases)
         cfg = ModelConfig(n_layer_xformer=n_layer_xformer, n_layer_e3gnn=0, n_hidden_xformer=n_hidden_xformer, n_hidden_e3nn=n_hidden_xformer,
                           n_embd_common=embed_dim, n_head=n_head, n_seq=n_seq, n_tok=n_tok, pad_token=int(pad_token), stop_token=int(stop_token),
                           unk_token=int(unk_token), use_point_encoder=False, biases=bool(biases), enc_to_coati=enc_to_coati)
-        eng = Engine(cfg, device, train=False)
+        eng = Engine(cfg, device, train=self.trainable)
         object.__setattr__(self, "engine", eng)
         views = eng.named_views("params")
+        grads = eng.named_views("grads") if self.trainable else {}
         for name in coati2_parameter_order(views):
-            _attach(self, name, views[name])
+            _attach(self, name, views[name], grads.get(name))
         for l in range(n_layer_xformer):   # causal-mask buffers of the reference state_dict (basic_transformer.py:117-123)
             _attach(self, f"xformer.transformer.h.{l}.attn.bias",
                     torch.tril(torch.ones(n_seq, n_seq, device=device)).view(1, 1, n_seq, n_seq), buffer=True)
@@ -96,6 +108,17 @@ class COATI_Smiles_Inference(nn.Module):
         if ids != (c.stop_token, c.unk_token, c.pad_token):
             raise NotImplementedError(f"tokenizer special ids (stop/unk/pad) {ids} differ from the model's "
                                       f"{(c.stop_token, c.unk_token, c.pad_token)}; build the model with the tokenizer's ids")
+
+    def forward(self, raw_tokens, augmented_tokens, tokenizer):
+        """(h_coati [B, E], logits [B, T2, n_tok]) of the training step's forward in evaluation mode: smiles_to_coati of the encoder pass
+        over raw_tokens, the decoder pass over augmented_tokens with coati_to_token(h_coati) at [UNK], the lm_head.  trainable=True only."""
+        self._sync_tokens(tokenizer)
+        eng = self.engine
+        _, h, _ = eng.forward(raw_tokens.to(self.device, torch.long).contiguous(), augmented_tokens.to(self.device, torch.long).contiguous(),
+                              y_next=None, train=False)
+        if int(eng.scal[6:7].view(torch.int32).item()) & 1:
+            raise RuntimeError("Some smiles in the batch do not have stop tokens. Did some tokenizations fail?")
+        return h, eng.logits()
 
     def encode_tokens(self, token_indices, tokenizer):
         """transformer_only.py:108-110: smiles_to_coati(xformer.encode(tokens)) -- the [STOP]-row embedding [B, embed_dim]."""

@@ -408,16 +408,30 @@ int coati_engine_encode(coati_engine* e, void* workspace, int64_t workspace_byte
                         const int64_t* raw_tokens, const int64_t* atoms, const float* coords, float* h_smiles,
                         float* h_e3gnn, float* scal, void* stream);
 
-/* COATI2 inference model (simple_coati2/transformer_only.py:43-104, COATI_Smiles_Inference): the same transformer and decode path
+/* COATI2 model (simple_coati2/transformer_only.py:43-104, COATI_Smiles_Inference): the same transformer and decode path
  * without a point encoder, and two heads in place of smiles_to_clip / point_clip_to_special_tokens.  enc_to_coati selects
  * smiles_to_coati: 0 = "linear" (LayerNorm -> Linear, state_dict .0 / .1), 1 = "swiglu_mlp" (LayerNorm -> Linear(C -> 2E) -> SwiGLU ->
  * Linear(E -> E), .0 / .1 / .3), 2 = "swiglu_resnet" (the same + x, .net.0 / .net.2 / .net.4).  coati_to_token is always the
  * residual form (coati_to_token.net.0 / .net.2 / .net.4).  The parameter table holds xformer.* (as coati_engine_create), then
  * smiles_to_coati.* and coati_to_token.net.*.  Needs use_point_encoder = 0, use_fp8 = 0, norm_embed = 0 and
  * n_embd_common == n_hidden_xformer; the point-encoder and clip-head fields of cfg are ignored.  On such an engine
- * coati_engine_encode runs smiles_to_coati behind the encoder pass (raw_tokens only); forward, forward_decoder, backward,
- * optimizer_step, infonce, score, score_grad and logits refuse to run (scoring: coati_engine_score_coati2 / coati_engine_score_grad_coati2);
- * the decode entries work unchanged. */
+ * coati_engine_encode runs smiles_to_coati behind the encoder pass (raw_tokens only); infonce (no contrastive head), score and score_grad
+ * refuse to run (scoring: coati_engine_score_coati2 / coati_engine_score_grad_coati2); the decode entries work unchanged.
+ *
+ * Training: a COATI2 engine trains if and only if coati_engine_bind gave it gradient, Adam-m and Adam-v buffers.  Bound without them it is
+ * inference-only: forward, forward_decoder, backward, optimizer_step and logits refuse ("inference-only") before any other check of the
+ * entry.  Bound with them, the step entries serve it with unchanged signatures:
+ *   coati_engine_forward          atoms, coords and use_point may be null, A is ignored.  Encoder pass over raw_tokens (the [STOP]-row tail
+ *                                 when training) -> smiles_to_coati -> h_coati, returned in h_smiles (h_e3gnn: zeros) -> coati_to_token into
+ *                                 the injection -> decoder pass -> lm_head + AR cross-entropy.  bad_rows, scal, packed rows, train | 2 with
+ *                                 coati_engine_forward_decoder and train = 0 as on a COATI1 engine
+ *   coati_engine_logits           after a padded forward, as on a COATI1 engine
+ *   coati_engine_backward         dh_smiles [B,E] or null: an external gradient w.r.t. h_coati; dh_e3gnn must be null.  lm_head, decoder
+ *                                 pass, coati_to_token and smiles_to_coati (all three variants) with every parameter gradient, encoder
+ *                                 pass; stages 0 .. 5 as on a COATI1 engine (stage 3 has nothing to do)
+ *   coati_engine_optimizer_step   clip-norm + AdamW over every parameter
+ *   coati_engine_workspace_bytes  includes the two heads' saved activations (an engine without training buffers: unchanged)
+ * The step is the AR loss alone: mean over the targets of the cross-entropy of forward_with_replacement(tokens, coati_to_token(h_coati)). */
 int coati_engine_create_coati2(const coati_config* cfg, int enc_to_coati, coati_engine** out);
 /* the token head coati_to_token = SwiGLUResNet(E, E) on h [B,E] f32 -> h_token [B,E] f32 (must not overlap h).  Scratch from the workspace:
  * coati_engine_workspace_bytes(e, B, 1, 1, 1, B) bytes.  Only on a COATI2 engine. */
@@ -459,7 +473,7 @@ int coati_engine_score_coati2(coati_engine* e, void* workspace, int64_t workspac
  * bit for bit what coati_engine_score_coati2(h_coati = ...) returns for the same arguments; dh_coati[b] = weights[b] * d nll[b] /
  * d h_coati[b] ([B,E] f32; weights [B] f32 or null = ones), through the decoder pass and the token head (LayerNorm -> Linear -> SwiGLU ->
  * Linear, + x), summed over every [UNK] position of row b.  rows2 > 0: packed decoder rows.  The model is a constant: no parameter
- * gradient is formed and no parameter is written.  A COATI1 engine is refused.  Workspace as for coati_engine_score_coati2. */
+ * gradient is formed and no parameter, gradient or Adam state is written, on an engine that trains too.  A COATI1 engine is refused.  Workspace as for coati_engine_score_coati2. */
 int coati_engine_score_grad_coati2(coati_engine* e, void* workspace, int64_t workspace_bytes, int B, int T2, const float* h_coati,
                                    const int64_t* tokens, const int64_t* y_next, int64_t rows2, const float* weights, float* nll,
                                    float* dh_coati, float* scal, void* stream);
