@@ -2,6 +2,7 @@
 #include <string.h>
 
 #include "../../include/coati_hip.h"
+#include "../../include/coati_beam.h"
 #include <vector>
 #include "kernels.h"
 
@@ -248,6 +249,23 @@ int coati_topk_sample_prompt(const float* logits, int64_t ldl, int B, int V, int
 int coati_attn_decode_rows(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int head_size, int Tmax, const int32_t* pos,
                            void* stream) {
   return launch_attn_decode_rows(qkv, cache, y, B, n_head, head_size, Tmax, pos, S_(stream));
+}
+// beam search (include/coati_beam.h)
+int coati_attn_decode_anc(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int head_size, int Tmax, int pos,
+                          const int32_t* anc, void* stream) {
+  return launch_attn_decode_anc(qkv, cache, y, B, n_head, head_size, Tmax, pos, anc, S_(stream));
+}
+int coati_beam_row_topk(const float* logits, int64_t ldl, int G, int W, int V, const float* cum, const int32_t* fin, int pad_token,
+                        float* cand_score, int32_t* cand_tok, void* stream) {
+  return launch_beam_row_topk(logits, ldl, G, W, V, cum, fin, pad_token, cand_score, cand_tok, S_(stream));
+}
+int coati_beam_merge(const float* cand_score, const int32_t* cand_tok, int G, int W, const float* cum_in, const int32_t* fin_in,
+                     const int32_t* len_in, const int32_t* anc_in, const int64_t* hist_in, int64_t ldh, int Tmax, int pos, int n,
+                     int stop_token, float* cum_out, int32_t* fin_out, int32_t* len_out, int32_t* anc_out, int64_t* hist_out,
+                     int64_t* tok_next, int32_t* nfin, void* stream) {
+  return launch_beam_merge(cand_score, cand_tok, G, W, cum_in, fin_in, len_in, anc_in, LL(hist_in), ldh, Tmax, pos, n, stop_token, cum_out,
+                           fin_out, len_out, anc_out, reinterpret_cast<long long*>(hist_out), reinterpret_cast<long long*>(tok_next), nfin,
+                           S_(stream));
 }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,

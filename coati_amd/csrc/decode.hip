@@ -5,89 +5,19 @@
 // Cache layout: [B][n_head][Tmax][k | v] bf16 (head size 16 or 32) -> one (b, head) sequence is a contiguous run of
 // 64 / 128-B records, a wave streams it with one record per lane per pass.  HBM-bound: 4 * hs bytes per cached token
 // per head per step.
-#include "kernels.h"
-
-
-template <int N>
-__device__ __forceinline__ void load_bf16(const bf16_t* p, float* x) {
-#pragma unroll
-  for (int i = 0; i < N / 8; ++i) unpack8(*reinterpret_cast<const uint4*>(p + 8 * i), x + 8 * i);
-}
+#include "decode_dev.h"
 
 // qkv: [B, 3C] bf16 of the new token (q, k already rotated by the QKV GEMM epilogue); y: [B, C] bf16.
-// One wave per (b, head).  Appends (k, v) at position pos, attends to positions 0..pos.
-// ROWS (ragged sessions): pos_dev is an array, row b sits at its own position pos_dev[b]; a position outside 0 .. Tmax - 1 marks an
-// idle slot, whose waves return before they read or write anything (their cache records and y rows keep what they held).  The
-// four passes below load only the records t <= pos, so a short row streams its own length, not the batch's.
+// One wave per (b, head).  Appends (k, v) at position pos, attends to positions 0..pos.  ROWS (ragged sessions): row b sits at its own
+// position pos_dev[b].  The body, with its commentary, is attn_decode_body.inc, shared with the ancestry-following kernel of
+// beam.hip.
 template <int DHS, bool ROWS>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ cache,
                                                           bf16_t* __restrict__ y, int B, int n_head, int Tmax, int pos_arg,
                                                           const int* __restrict__ pos_dev) {
-  const int lane = threadIdx.x & 63;
-  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (item >= B * n_head) return;
-  const int b = item / n_head, h = item - b * n_head;
-  const int pos = ROWS ? pos_dev[b] : (pos_dev ? *pos_dev : pos_arg);
-  if (ROWS && (pos < 0 || pos >= Tmax)) return;
-  const int C = n_head * DHS;
-  const bf16_t* row = qkv + (long long)b * 3 * C + h * DHS;
-  float q[DHS], kn[DHS], vn[DHS];
-  constexpr int REC = 2 * DHS, CH = DHS / 8;   // record = [k | v] halfs; 16-B chunks per operand
-  load_bf16<DHS>(row, q);
-  load_bf16<DHS>(row + C, kn);
-  load_bf16<DHS>(row + 2 * C, vn);
-  bf16_t* seq = cache + ((long long)item * Tmax) * REC;
-  if (lane < 2 * CH) {   // append the new record
-    const bf16_t* src = (lane < CH) ? row + C + lane * 8 : row + 2 * C + (lane - CH) * 8;
-    *reinterpret_cast<uint4*>(seq + (long long)pos * REC + lane * 8) = *reinterpret_cast<const uint4*>(src);
-  }
-  // scores of this lane's keys (t = lane, lane + 64, ...); the newest key comes from registers, not from the cache
-  float m = -INFINITY;
-  float sc[4];
-  float kv[4][DHS];   // values of this lane's keys
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int t = lane + 64 * i;
-    sc[i] = -INFINITY;
-    if (t <= pos) {
-      float k[DHS];
-      if (t == pos) {
-#pragma unroll
-        for (int d = 0; d < DHS; ++d) { k[d] = kn[d]; kv[i][d] = vn[d]; }
-      } else {
-        load_bf16<DHS>(seq + (long long)t * REC, k);
-        load_bf16<DHS>(seq + (long long)t * REC + DHS, kv[i]);
-      }
-      float s = 0.f;
-#pragma unroll
-      for (int d = 0; d < DHS; ++d) s += q[d] * k[d];
-      sc[i] = s * (DHS == 16 ? 0.25f : 0.17677669529663687f);   // 1 / sqrt(hs)
-      m = fmaxf(m, sc[i]);
-    } else {
-#pragma unroll
-      for (int d = 0; d < DHS; ++d) kv[i][d] = 0.f;
-    }
-  }
-  m = wave_max(m);
-  float l = 0.f, acc[DHS];
-#pragma unroll
-  for (int d = 0; d < DHS; ++d) acc[d] = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float p = (sc[i] == -INFINITY) ? 0.f : __expf(sc[i] - m);
-    l += p;
-#pragma unroll
-    for (int d = 0; d < DHS; ++d) acc[d] += p * kv[i][d];
-  }
-  l = wave_sum(l);
-  const float inv = 1.0f / l;
-#pragma unroll
-  for (int d = 0; d < DHS; ++d) acc[d] = wave_sum(acc[d]) * inv;
-  if (lane == 0) {
-    bf16_t* dst = y + (long long)b * C + h * DHS;
-#pragma unroll
-    for (int i = 0; i < DHS / 8; ++i) *reinterpret_cast<uint4*>(dst + 8 * i) = pack8(acc + 8 * i);
-  }
+#define ATTN_DECODE_SEQ(t) seq
+#include "attn_decode_body.inc"
+#undef ATTN_DECODE_SEQ
 }
 
 __global__ void add_int_kernel(int* x, int v, int set) { *x = set ? v : *x + v; }
@@ -156,100 +86,13 @@ int launch_decode_rows_prep(const int* pos, const int* inj_len, const long long*
 // threshold in index order), sorted (value descending, index ascending -- the order of a stable descending sort) and
 // sampled by inverse CDF with the caller's uniform u[b] in [0, 1).  stopped rows emit pad_token; a row that draws
 // stop_token is marked stopped (reference :314-324).  Integer/compare work on a 40-KB row: ~10 us per row-block.
-#define TOPK_MAX 128
-__device__ __forceinline__ unsigned f2key(float f) {   // larger float <-> larger unsigned (NaN sorts high, like torch)
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// LDS of one row's selection (the row's keys themselves live in the kernel's dynamic LDS, [V])
-struct TopkLds {
-  int hist[256];
-  unsigned prefix;
-  int need, ngt, neq;
-  unsigned top_k[TOPK_MAX];
-  int top_i[TOPK_MAX];
-};
-
-// The selection and the draw for ONE row (the workgroup's 256 threads, all of them): returns the token in thread 0 (other
-// threads: unspecified).  Shared by topk_sample_kernel and topk_sample_prompt_kernel, so that an unforced row of the second
-// gives the very bits of the first.
+// The selection (topk_select_row, decode_dev.h: shared with beam.hip) and the draw for ONE row (the workgroup's 256 threads, all of
+// them): returns the token in thread 0 (other threads: unspecified).  Shared by topk_sample_kernel and topk_sample_prompt_kernel, so
+// that an unforced row of the second gives the very bits of the first.
 __device__ __forceinline__ int topk_sample_row(const float* __restrict__ lrow, int V, int k, float inv_temp, float uval,
                                                unsigned* keys, TopkLds& sm) {
   const int tid = threadIdx.x;
-  for (int i = tid; i < V; i += 256) keys[i] = f2key(lrow[i]);
-  if (tid == 0) { sm.prefix = 0u; sm.need = k; }
-  __syncthreads();
-  // radix select of the k-th largest key: after pass p the top 8*(p+1) bits of the threshold are known
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    const unsigned mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    sm.hist[tid] = 0;
-    __syncthreads();
-    const unsigned prefix = sm.prefix;
-    for (int i = tid; i < V; i += 256) {
-      const unsigned key = keys[i];
-      if ((key & mask) == prefix) atomicAdd(&sm.hist[(key >> shift) & 255], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int need = sm.need, bin = 255;
-      for (; bin > 0; --bin) {
-        if (sm.hist[bin] >= need) break;
-        need -= sm.hist[bin];
-      }
-      sm.need = need;                              // rank of the threshold inside its bin
-      sm.prefix = prefix | ((unsigned)bin << shift);
-    }
-    __syncthreads();
-  }
-  const unsigned tau = sm.prefix;                  // the k-th largest key; sm.need = how many keys == tau belong to the top k
-  if (tid == 0) { sm.ngt = 0; sm.neq = 0; }
-  __syncthreads();
-  // survivors: every key > tau (any order), then the first sm.need keys == tau in index order
-  for (int i = tid; i < V; i += 256) {
-    if (keys[i] > tau) {
-      const int slot = atomicAdd(&sm.ngt, 1);
-      sm.top_k[slot] = keys[i];
-      sm.top_i[slot] = i;
-    }
-  }
-  __syncthreads();
-  {
-    // the first sm.need keys == tau in INDEX order: threads own contiguous index segments, exclusive scan of their counts
-    const int seg = (V + 255) / 256, i0 = tid * seg, i1 = (i0 + seg < V) ? i0 + seg : V;
-    int cnt = 0;
-    for (int i = i0; i < i1; ++i) cnt += (keys[i] == tau) ? 1 : 0;
-    sm.hist[tid] = cnt;
-    __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += sm.hist[t];
-    const int base = sm.ngt, need = sm.need;
-    if (cnt > 0 && before < need) {
-      int pos = before;
-      for (int i = i0; i < i1 && pos < need; ++i)
-        if (keys[i] == tau) { sm.top_k[base + pos] = tau; sm.top_i[base + pos] = i; ++pos; }
-    }
-  }
-  __syncthreads();
-  // sort the k survivors: key descending, index ascending (rank by counting; k <= 128)
-  unsigned myk = 0;
-  int myi = 0, rank = 0;
-  if (tid < k) {
-    myk = sm.top_k[tid];
-    myi = sm.top_i[tid];
-    for (int j = 0; j < k; ++j) {
-      const unsigned kj = sm.top_k[j];
-      const int ij = sm.top_i[j];
-      rank += (kj > myk || (kj == myk && ij < myi)) ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  if (tid < k) { sm.top_k[rank] = myk; sm.top_i[rank] = myi; }
-  __syncthreads();
+  topk_select_row(lrow, V, k, keys, sm);
   int tok = 0;
   if (tid == 0) {
     const float mx = key2f(sm.top_k[0]) * inv_temp;

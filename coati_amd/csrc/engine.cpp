@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/coati_hip.h"
+#include "../../include/coati_beam.h"
 #include "kernels.h"
 
 // a HIP runtime call inside a function that returns a COATI_* code (beside COATI_TRY / COATI_CHECK_* of common.h)
@@ -2546,8 +2547,10 @@ namespace {
 // instead of the session's d.pos; inj_len (optional, with pos_rows): row b reads the injection only while pos_rows[b] < inj_len[b].
 // Idle slots ride through the row-wise products and LayerNorms (M stays B): their rotary index is clamped to a valid table row
 // (launch_decode_rows_prep), and what they compute is read by nobody -- the attention skips them, every other launch is row-wise.
+// anc (beam step, neither with graph_mode nor with pos_rows): every layer's attention reads position t < d.pos of row b from cache row
+// anc[b * Tmax + t] (int32 [B, Tmax], device) -- the rows of surviving beams follow their parents without a copy.
 int decode_enqueue(coati_engine* e, const long long* tokens, const float* injection, float* logits, int64_t ldl,
-                   bool graph_mode, hipStream_t s, const int* pos_rows = nullptr, const int* inj_len = nullptr) {
+                   bool graph_mode, hipStream_t s, const int* pos_rows = nullptr, const int* inj_len = nullptr, const int* anc = nullptr) {
   auto& d = e->dec;
   const coati_config& c = e->cfg;
   const int C = c.n_hidden_xformer, L = c.n_layer_xformer, B = d.B, hs = C / c.n_head;
@@ -2584,6 +2587,7 @@ int decode_enqueue(coati_engine* e, const long long* tokens, const float* inject
     }
     bf16_t* cache_l = d.cache + (size_t)l * B * C * d.Tmax * 2;
     if (pos_rows) COATI_TRY(launch_attn_decode_rows(d.qkv, cache_l, d.y, B, c.n_head, hs, d.Tmax, pos_rows, s));
+    else if (anc) COATI_TRY(launch_attn_decode_anc(d.qkv, cache_l, d.y, B, c.n_head, hs, d.Tmax, d.pos, anc, s));
     else COATI_TRY(launch_attn_decode(d.qkv, cache_l, d.y, B, c.n_head, hs, d.Tmax, d.pos, graph_mode ? d.pos_dev : nullptr, s));
     COATI_TRY(gemm(e, SITE_NONE, d.y, 0, C, e->S + w.projw, C, B, C, C, xm, C, e->P + w.projb, EPI_RES_F32, x, nullptr, C, s));
     COATI_TRY(launch_layernorm_fwd(xm, C, e->P + w.ln2w, e->P + w.ln2b, d.a, C, nullptr, 0, d.mean, d.rstd, B, C, s));
@@ -2614,6 +2618,22 @@ int coati_engine_decode_step(coati_engine* e, const int64_t* tokens, const float
   COATI_CHECK_SHAPE(d.pos < d.Tmax, "decode_step: the cache is full (pos=%d, Tmax=%d)", d.pos, d.Tmax);
   COATI_CHECK_ARG(!logits || ldl >= e->cfg.n_tok, "decode_step: ldl too small");
   COATI_TRY(decode_enqueue(e, reinterpret_cast<const long long*>(tokens), injection, logits, ldl, false, (hipStream_t)stream));
+  d.pos += 1;
+  return COATI_OK;
+}
+
+// coati_engine_decode_step with every layer's attention in ancestry mode (beam search, include/coati_beam.h): position t < pos of row b
+// is read from cache row anc[b * Tmax + t] (int32 [B, Tmax] of the session's B and Tmax, device), the new record is appended at
+// (b, pos), and the session's position advances.  Eager only (never captured into the decode graphs); refused in a ragged session.
+int coati_engine_decode_step_beams(coati_engine* e, const int64_t* tokens, const int32_t* anc, const float* injection, float* logits,
+                                   int64_t ldl, void* stream) {
+  COATI_CHECK_ARG(e && e->dec.active && tokens, "decode_step_beams: no decode session / null tokens");
+  COATI_CHECK_ARG(anc, "decode_step_beams: null ancestry table");
+  auto& d = e->dec;
+  COATI_CHECK_ARG(!d.ragged, "decode_step_beams: the session is ragged (per-row positions): beam search runs on an aligned session");
+  COATI_CHECK_SHAPE(d.pos < d.Tmax, "decode_step_beams: the cache is full (pos=%d, Tmax=%d)", d.pos, d.Tmax);
+  COATI_CHECK_ARG(!logits || ldl >= e->cfg.n_tok, "decode_step_beams: ldl too small");
+  COATI_TRY(decode_enqueue(e, reinterpret_cast<const long long*>(tokens), injection, logits, ldl, false, (hipStream_t)stream, nullptr, nullptr, anc));
   d.pos += 1;
   return COATI_OK;
 }

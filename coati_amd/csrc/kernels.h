@@ -346,6 +346,17 @@ int launch_kv_cache_fill_rows(const bf16_t* qkv, bf16_t* cache, const int* row_s
 int launch_gather_last_rows(const float* x, const int* off, float* out, int B, int C, int R, hipStream_t s);
 // prompt prefill: the rotated k and the v of a padded [B, m] pass's qkv into one layer's cache [B][nh][Tmax][k|v], positions 0..m-1
 int launch_kv_cache_fill(const bf16_t* qkv, bf16_t* cache, int B, int m, int n_head, int head_size, int Tmax, hipStream_t s);
+// beam search (beam.hip, include/coati_beam.h)
+// launch_attn_decode with the records of t < pos read from cache row anc[b * Tmax + t] (int32 [B, Tmax], device)
+int launch_attn_decode_anc(const bf16_t* qkv, bf16_t* cache, bf16_t* y, int B, int n_head, int head_size, int Tmax, int pos,
+                           const int* anc, hipStream_t s);
+// per row of [G * W, V] logits: its W best continuations (cum[b] + log_softmax, token), best first; 1 <= W <= 16
+int launch_beam_row_topk(const float* logits, long long ldl, int G, int W, int V, const float* cum, const int* fin, int pad_token,
+                         float* cand_score, int* cand_tok, hipStream_t s);
+// per group: the best W of its W * W candidates become its new rows (score, flags, lengths, ancestry and token history rows)
+int launch_beam_merge(const float* cand_score, const int* cand_tok, int G, int W, const float* cum_in, const int* fin_in, const int* len_in,
+                      const int* anc_in, const long long* hist_in, long long ldh, int Tmax, int pos, int n, int stop_token, float* cum_out,
+                      int* fin_out, int* len_out, int* anc_out, long long* hist_out, long long* tok_next, int* nfin, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

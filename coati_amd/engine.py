@@ -708,6 +708,90 @@ class Engine:
             return torch.cat([torch.tensor(prefix, dtype=torch.long, device=dev).unsqueeze(0).repeat(B, 1), gen], dim=1)
         return [prefix + row for row in gen.tolist()]
 
+    # ---- beam search (include/coati_beam.h) ----------------------------------------------------------------------------
+    def decode_step_beams(self, tokens, anc, injection=None, want_logits=True):
+        """decode_step with every layer's attention in ancestry mode (coati_engine_decode_step_beams): position t of row b is read
+        from cache row anc[b, t] (int32 [B, Tmax] on the device), the new record is appended in row b.  Advances the session."""
+        B = self._dec_B
+        tokens = tokens.to(self.device, torch.long).contiguous()
+        assert tokens.shape == (B,)
+        assert anc.dtype == torch.int32 and anc.is_contiguous() and anc.shape == (B, self._dec_Tmax) and anc.device == tokens.device, \
+            "anc: int32 [B, Tmax] on the device"
+        inj = self._injection(injection, B)
+        buf, ld, logits = self._logits_rows(B, want_logits)
+        _lib.call("coati_engine_decode_step_beams", self.h, ptr(tokens), ptr(anc), ptr(inj), ptr(buf), ld, stream())
+        return logits
+
+    def beam_search(self, prefix, stop_token, pad_token=0, beams=4, inj_token=None, inj_payload=None, max_len=None, length_penalty=0.0):
+        """The `beams` most likely continuations of `prefix` for every row of inj_payload [G, C], by beam search on the KV-cached decode
+        path (runs on a private stream, like generate_top_k_with_inj_batch).  Returns (tokens [G, W, T] int64: prefix + generated,
+        pad_token behind [STOP]; scores [G, W] f32: the sum of the generated tokens' log-probabilities, [STOP] included; lengths [G, W]:
+        generated tokens up to and with [STOP]; finished [G, W] bool), per group sorted by score / max(length, 1) ** length_penalty,
+        best first.  The search itself ranks by the raw sum (ties: parent beam, then token id, ascending); the penalty only reorders
+        the result.  It ends when every hypothesis has drawn [STOP] or at min(max_len, n_seq) positions; a hypothesis that has not
+        finished by then is returned as it stands (finished = False, no [STOP] appended: its score is that of its tokens)."""
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            out = self._beam_search(prefix, stop_token, pad_token, beams, inj_token, inj_payload, max_len, length_penalty)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        return out
+
+    def _beam_search(self, prefix, stop_token, pad_token, beams, inj_token, inj_payload, max_len, length_penalty, trace=None):
+        """beam_search on the current stream.  trace (a list, for the tests): receives per step (parent rows [B] int32, tokens [B] int64,
+        scores [B] f32) of the new rows g * W + rank, on the device."""
+        prefix = [int(t) for t in prefix]
+        W, V, dev = int(beams), self.cfg.n_tok, self.device
+        if not 1 <= W <= 16 or W > V:
+            raise ValueError(f"beam_search: beams = {W}; 1 .. min(16, n_tok) fit")
+        if inj_token is not None and int(inj_token) != self.cfg.unk_token:
+            raise NotImplementedError("the injection slot must be the engine's [UNK] id")
+        n_seq = min(int(max_len), self.cfg.n_seq) if max_len else self.cfg.n_seq
+        m = len(prefix)
+        if not 1 <= m < n_seq:
+            raise ValueError(f"beam_search: a prefix of {m} tokens; 1 .. {n_seq - 1} fit")
+        G = int(inj_payload.shape[0])
+        B = G * W
+        payload = self._injection(inj_payload, G).repeat_interleave(W, dim=0)     # row g * W + r reads inj_payload[g]
+        Tmax = self.cfg.n_seq
+        self.decode_begin(B, Tmax)
+        logits = None
+        for i, t in enumerate(prefix):
+            tok = torch.full((B,), t, dtype=torch.long, device=dev)
+            logits = self.decode_step(tok, payload if (inj_token is not None and t == int(inj_token)) else None, want_logits=(i == m - 1))
+        steps = n_seq - m
+        # state, ping-pong: [cum, fin, len, anc, hist]
+        cum = torch.full((G, W), float("-inf"), device=dev)
+        cum[:, 0] = 0.0
+        ident = torch.arange(B, dtype=torch.int32, device=dev).unsqueeze(1).repeat(1, Tmax).contiguous()
+        cur = [cum.view(B), torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev), ident,
+               torch.full((B, steps), int(pad_token), dtype=torch.long, device=dev)]
+        nxt = [torch.empty_like(cur[0]), torch.empty_like(cur[1]), torch.empty_like(cur[2]), ident.clone(), cur[4].clone()]
+        cand_s = torch.empty(B, W, device=dev)
+        cand_t = torch.empty(B, W, dtype=torch.int32, device=dev)
+        tok_next = torch.empty(B, dtype=torch.long, device=dev)
+        nfin = torch.zeros(G, dtype=torch.int32, device=dev)
+        n = 0
+        while True:
+            _lib.call("coati_beam_row_topk", ptr(logits), logits.stride(0), G, W, V, ptr(cur[0]), ptr(cur[1]), int(pad_token), ptr(cand_s),
+                      ptr(cand_t), stream())
+            _lib.call("coati_beam_merge", ptr(cand_s), ptr(cand_t), G, W, ptr(cur[0]), ptr(cur[1]), ptr(cur[2]), ptr(cur[3]), ptr(cur[4]),
+                      steps, Tmax, m - 1 + n, n, int(stop_token), ptr(nxt[0]), ptr(nxt[1]), ptr(nxt[2]), ptr(nxt[3]), ptr(nxt[4]),
+                      ptr(tok_next), ptr(nfin), stream())
+            cur, nxt = nxt, cur
+            if trace is not None:
+                trace.append((cur[3][:, m - 1 + n].clone(), tok_next.clone(), cur[0].clone()))
+            n += 1
+            if n >= steps or int(nfin.sum().item()) >= B:
+                break
+            logits = self.decode_step_beams(tok_next, cur[3])
+        scores, fin, lens, hist = cur[0].view(G, W), cur[1].view(G, W) != 0, cur[2].view(G, W), cur[4][:, :n].reshape(G, W, n)
+        key = scores / lens.clamp(min=1).to(torch.float32) ** float(length_penalty)
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        head = torch.tensor(prefix, dtype=torch.long, device=dev).view(1, 1, m).expand(G, W, m)
+        tokens = torch.cat([head, torch.gather(hist, 1, order.unsqueeze(2).expand(G, W, n))], dim=2)
+        return tokens, torch.gather(scores, 1, order), torch.gather(lens, 1, order), torch.gather(fin, 1, order)
+
     def generate_topk_batch(self, prefix, stop_token, pad_token=0, inv_temp=2, k=10, generator=None, prefill=True, ragged=False):
         """RotarySmilesTransformer.generate_topk_batch (smiles_xformer.py:157-198): continue B prompts of different lengths
         (token lists) on the KV-cached decode path.  Returns B lists of n_seq ints: every prompt verbatim, each row sampled

@@ -103,6 +103,15 @@ def _decode_batch(encoder, H: torch.Tensor, tokenizer, generator=None, slots=Non
     return list(fn(H, tokenizer, **kw))
 
 
+def decode_most_likely(model, vectors: torch.Tensor, tokenizer, beams: int = 4):
+    """The `beams` most likely SMILES of every row of vectors [N, E] with their log-likelihoods, best first: per vector a list of
+    (smiles, log_likelihood) from beam search (hclip_to_2d_beam, hcoati_to_2d_beam on COATI2) -- the deterministic counterpart of
+    drawing samples and keeping the most frequent one."""
+    fn = model.hcoati_to_2d_beam if _is_coati2(model) else model.hclip_to_2d_beam
+    V = vectors if vectors.dim() == 2 else vectors.reshape(1, -1)
+    return fn(V, tokenizer, beams=beams)
+
+
 def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=None, slots=None) -> List[Optional[List[str]]]:
     """n_rep decodes of every row of V [N, E], as few decode calls as DECODE_ROW_CAP allows (whole vectors per call).  Per vector the
     list of its n_rep strings in sample order, or None when its decode call raised.

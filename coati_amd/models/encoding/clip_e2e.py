@@ -222,6 +222,21 @@ def injection_prefix(tokenizer, fill_in_from: str, do_suffix: bool):
     return [int(getattr(tokenizer, n)) for n in names]
 
 
+def beam_decodings(engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty):
+    """Engine.beam_search from `prefix` with h_token [G, C] in the [UNK] slot, as per-embedding lists of (smiles, log_likelihood), best
+    first (the token lists themselves for a tokenizer that cannot decode); return_tokens: (those, the hypotheses' token lists: the
+    prompt and the generated tokens up to and with [STOP])."""
+    tokens, scores, lengths, _ = engine.beam_search(prefix=prefix, stop_token=tokenizer.stop_token, pad_token=tokenizer.pad_token,
+                                                    beams=beams, inj_token=tokenizer.unk_token, inj_payload=h_token,
+                                                    length_penalty=length_penalty)
+    tokens, scores, lengths = tokens.tolist(), scores.tolist(), lengths.tolist()
+    m = len(prefix)
+    rows = [[hyp[:m + n] for hyp, n in zip(tg, ng)] for tg, ng in zip(tokens, lengths)]
+    text = (lambda t: tokenizer.decode(t, special=keep_special)) if hasattr(tokenizer, "decode") else (lambda t: t)
+    out = [[(text(t), float(sc)) for t, sc in zip(rg, sg)] for rg, sg in zip(rows, scores)]
+    return (out, rows) if return_tokens else out
+
+
 def attach_xformer_logits(xformer: nn.Module, engine: Engine):
     """RotarySmilesTransformer.forward(idx) and .forward_with_replacement(idx, injection, tokenizer, inject_token) (smiles_xformer.py:375-382,
     426-454; simple_coati2/smiles_xformer.py:388, 439) on `xformer`, so that xformer(idx) works as well: the decoder pass over the padded
@@ -420,6 +435,27 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         h_clip = self.encode_points(atom_batch, coords_batch)
         return self.hclip_to_2d_batch(h_clip, tokenizer, fill_in_from=fill_in_from, noise_scale=noise_scale, inv_temp=inv_temp, k=k,
                                       do_suffix=do_suffix, keep_special=keep_special, generator=generator, slots=slots)
+
+    @torch.no_grad()
+    def hclip_to_2d_beam(self, h_clip, tokenizer, beams: int = 4, fill_in_from: str = "[SMILES]", do_suffix: bool = False,
+                         keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0):
+        """The `beams` most likely decodings of every clip embedding of h_clip [G, E], by beam search (Engine.beam_search) from the
+        prompt of hclip_to_2d_batch: per embedding a list of (smiles, log_likelihood), best first -- the log-likelihood is the sum of
+        the generated tokens' log-probabilities, [STOP] included.  return_tokens=True: also the hypotheses' token lists, per embedding
+        (the prompt, the generated tokens up to and with [STOP]).  No reference counterpart (the reference only samples)."""
+        self._sync_tokens(tokenizer)
+        assert fill_in_from in ("[SMILES]", "[GRAPH]")
+        h_token = self.special_tokens_from_clip(h_clip)
+        prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
+        return beam_decodings(self.engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty)
+
+    @torch.no_grad()
+    def points_to_2d_beam(self, atoms, coords, tokenizer, beams: int = 4, fill_in_from: str = "[SMILES]", do_suffix: bool = False,
+                          keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0):
+        """encode_points, then hclip_to_2d_beam."""
+        return self.hclip_to_2d_beam(self.encode_points(atoms, coords), tokenizer, beams=beams, fill_in_from=fill_in_from,
+                                     do_suffix=do_suffix, keep_special=keep_special, return_tokens=return_tokens,
+                                     length_penalty=length_penalty)
 
     def _to_2d_one(self, h_clip, tokenizer, fill_in_from, noise_scale, suffix, inv_temp, k, generator):
         """hclip_to_2d / points_to_2d: the special token of h_clip injected as the reference does it, h_token[0] -- the first row of a

@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from ...engine import Engine, ModelConfig
-from ..encoding.clip_e2e import (_attach, attach_xformer_logits, hcoati_likelihood_tokens, injection_prefix, reference_parameter_order,
+from ..encoding.clip_e2e import (_attach, attach_xformer_logits, beam_decodings, hcoati_likelihood_tokens, injection_prefix, reference_parameter_order,
                                  s2s_hcoati_likelihood_tokens, score_host_rows, torch_default_init)
 
 
@@ -173,6 +173,18 @@ class COATI_Smiles_Inference(nn.Module):
         if return_tokens:
             return smiles_list, generation
         return smiles_list
+
+    @torch.no_grad()
+    def hcoati_to_2d_beam(self, h_coati, tokenizer, beams: int = 4, fill_in_from: str = "[SMILES]", do_suffix: bool = False,
+                          keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0):
+        """The `beams` most likely decodings of every embedding of h_coati [G, E], by beam search (Engine.beam_search) through
+        coati_to_token at the [UNK] slot of hcoati_to_2d_batch's prompt: per embedding a list of (smiles, log_likelihood), best first;
+        return_tokens=True: also the hypotheses' token lists.  No reference counterpart (the reference only samples)."""
+        self._sync_tokens(tokenizer)
+        assert fill_in_from == "[SMILES]" or fill_in_from == "[GRAPH]"
+        h_token = self.engine.token_head(h_coati.to(self.device, torch.float32))
+        prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
+        return beam_decodings(self.engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty)
 
     def hcoati_and_tokens_to_likelihood(self, h_coati: torch.Tensor, smiles, tokenizer, do_suffix=False) -> torch.Tensor:
         """The likelihood of a SMILES string under an embedding (COATI1's hclip_and_tokens_to_likelihood, clip_e2e.py:634-665, on
