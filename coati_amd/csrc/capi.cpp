@@ -3,6 +3,7 @@
 
 #include "../../include/coati_hip.h"
 #include "../../include/coati_beam.h"
+#include "../../include/coati_search.h"
 #include <vector>
 #include "kernels.h"
 
@@ -267,6 +268,13 @@ int coati_beam_merge(const float* cand_score, const int32_t* cand_tok, int G, in
                            fin_out, len_out, anc_out, reinterpret_cast<long long*>(hist_out), reinterpret_cast<long long*>(tok_next), nfin,
                            S_(stream));
 }
+// embedding-library search (include/coati_search.h)
+int coati_search_topk(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, int k, float alpha, int S,
+                      float* part_score, int32_t* part_row, float* out_score, int64_t* out_row, void* stream) {
+  return launch_search_topk(lib, N, E, bias, q, Q, k, alpha, S, part_score, part_row, out_score, reinterpret_cast<long long*>(out_row),
+                            S_(stream));
+}
+int coati_search_slices(int64_t N, int Q, int k) { return search_slices(N, Q, k); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

@@ -357,6 +357,11 @@ int launch_beam_row_topk(const float* logits, long long ldl, int G, int W, int V
 int launch_beam_merge(const float* cand_score, const int* cand_tok, int G, int W, const float* cum_in, const int* fin_in, const int* len_in,
                       const int* anc_in, const long long* hist_in, long long ldh, int Tmax, int pos, int n, int stop_token, float* cum_out,
                       int* fin_out, int* len_out, int* anc_out, long long* hist_out, long long* tok_next, int* nfin, hipStream_t s);
+// embedding-library search (search.hip, include/coati_search.h): per query the k best rows of lib [N, E] bf16 by alpha * dot + bias,
+// score descending, row ascending; part_* are [Q, S, k] scratch
+int launch_search_topk(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, int k, float alpha, int S,
+                       float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s);
+int search_slices(long long N, int Q, int k);   // host only: the default S
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

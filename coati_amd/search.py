@@ -1,0 +1,236 @@
+"""Nearest-neighbour search over a library of embeddings held in device memory as bf16 rows (include/coati_search.h, csrc/search.hip).
+
+    index = EmbeddingIndex(256, metric="cosine")
+    index.add(library_vectors)                       # [N, 256] float, any device
+    scores, rows = index.search(queries, k=10)       # [Q, 10] f32 / int64: score descending, row ascending among equal scores
+
+One streaming kernel computes alpha * dot(q, row) + bias[row] on the matrix cores and keeps every query's k best in LDS -- no [Q, N]
+score matrix exists -- and a second one merges the library slices' lists.  The three metrics are host-side preparation (torch) on
+top of that one kernel: "dot" (alpha 1, no bias), "cosine" (rows and queries normalised in f32, then rounded to bf16) and "l2" (alpha 2,
+bias = -|x|^2 of the STORED bf16 values; the score returned is the negated squared distance).  Removing a row sets its bias to -inf.
+There is no CPU fallback: search() on an index that is not on a GPU raises.  The reference has no counterpart."""
+import ctypes
+
+import torch
+
+from . import _lib
+
+METRICS = ("dot", "cosine", "l2")
+DIM_MAX = 512
+K_MAX = 128                      # TOPK_MAX of the radix select (csrc/decode_dev.h)
+MERGE_MAX = 30720                # S * k: one query's partial lists are one row of the merge's select
+SCRATCH_BYTES = 64 << 20         # the [Q, S, k] partial lists of one chunk of queries (f32 score + int32 row)
+MIN_CAPACITY = 1024
+
+
+def padded_dim(dim):
+    """the stored width of a `dim`-wide embedding: the next multiple of 32 (the zero columns change no metric)"""
+    if dim < 1 or dim > DIM_MAX:
+        raise ValueError(f"EmbeddingIndex: dim={dim} outside 1 .. {DIM_MAX}")
+    return (dim + 31) // 32 * 32
+
+
+def _check_metric(metric):
+    if metric not in METRICS:
+        raise ValueError(f"EmbeddingIndex: metric {metric!r} is not one of {METRICS}")
+
+
+def metric_alpha(metric):
+    _check_metric(metric)
+    return 2.0 if metric == "l2" else 1.0
+
+
+def _as_f32(x, dim, device, what):
+    x = torch.as_tensor(x)
+    if x.dim() == 1:
+        x = x[None]
+    if x.dim() != 2 or x.shape[1] != dim:
+        raise ValueError(f"EmbeddingIndex: {what} must be [n, {dim}], got {tuple(x.shape)}")
+    x = x.detach().to(device=device, dtype=torch.float32)
+    ep = padded_dim(dim)
+    return x if ep == dim else torch.nn.functional.pad(x, (0, ep - dim))
+
+
+def _normalised(x):
+    return x / x.norm(dim=1, keepdim=True).clamp_min(1e-30)
+
+
+def prepare_rows(x, metric, dim, device=None):
+    """library rows as stored: (f32 [n, dim_padded] after the metric's preparation, its bf16 rounding, bias [n] f32)"""
+    _check_metric(metric)
+    x = _as_f32(x, dim, device, "vectors")
+    if metric == "cosine":
+        x = _normalised(x)
+    x16 = x.to(torch.bfloat16)
+    if metric == "l2":
+        bias = -(x16.double() ** 2).sum(dim=1).float()      # one rounding: the squares' sum in float64, stored as f32
+    else:
+        bias = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+    return x, x16, bias
+
+
+def prepare_queries(q, metric, dim, device=None):
+    """queries as searched: (f32 [Q, dim_padded] after the metric's preparation, its bf16 rounding)"""
+    _check_metric(metric)
+    q = _as_f32(q, dim, device, "queries")
+    if metric == "cosine":
+        q = _normalised(q)
+    return q, q.to(torch.bfloat16).contiguous()
+
+
+def finish_scores(scores, metric, q16):
+    """the kernel's alpha * dot + bias as the metric's score: l2 = 2 q.x - |x|^2 - |q|^2 = -|q - x|^2 (at most 0); -inf padding stays"""
+    if metric != "l2":
+        return scores
+    return (scores - (q16.float() ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+class EmbeddingIndex:
+    def __init__(self, dim, metric="cosine", device="cuda:0", keep_f32=False):
+        _check_metric(metric)
+        self.dim, self.dim_padded = int(dim), padded_dim(int(dim))
+        self.metric, self.device, self.keep_f32 = metric, torch.device(device), bool(keep_f32)
+        self._n = 0
+        self._vec = self._bias = self._f32 = None      # [capacity, dim_padded] bf16, [capacity] f32, [capacity, dim_padded] f32 (keep_f32)
+        self._scratch = None                           # the partial lists, kept between searches
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def vectors(self):
+        """the stored bf16 rows [N, dim_padded] (a view)"""
+        return self._empty(torch.bfloat16) if self._vec is None else self._vec[:self._n]
+
+    @property
+    def bias(self):
+        """the rows' f32 bias [N] (a view): 0, -|x|^2 for l2, -inf once removed"""
+        return torch.empty(0, dtype=torch.float32, device=self.device) if self._bias is None else self._bias[:self._n]
+
+    def _empty(self, dtype):
+        return torch.empty(0, self.dim_padded, dtype=dtype, device=self.device)
+
+    def _reserve(self, n):
+        cap = 0 if self._vec is None else self._vec.shape[0]
+        if n <= cap:
+            return
+        new = max(MIN_CAPACITY, cap)
+        while new < n:
+            new *= 2
+
+        def grown(old, shape, dtype):
+            t = torch.empty(shape, dtype=dtype, device=self.device)
+            if old is not None:
+                t[:self._n] = old[:self._n]
+            return t
+
+        self._vec = grown(self._vec, (new, self.dim_padded), torch.bfloat16)
+        self._bias = grown(self._bias, (new,), torch.float32)
+        if self.keep_f32:
+            self._f32 = grown(self._f32, (new, self.dim_padded), torch.float32)
+
+    def add(self, vectors):
+        """appends the rows of vectors [n, dim] (any float dtype, any device); returns their row indices"""
+        x, x16, bias = prepare_rows(vectors, self.metric, self.dim, self.device)
+        if self._n + x.shape[0] >= 2 ** 31:
+            raise ValueError("EmbeddingIndex: more than 2^31 - 1 rows")
+        lo, hi = self._n, self._n + x.shape[0]
+        self._reserve(hi)
+        self._vec[lo:hi], self._bias[lo:hi] = x16, bias
+        if self.keep_f32:
+            self._f32[lo:hi] = x
+        self._n = hi
+        return range(lo, hi)
+
+    def remove(self, rows):
+        """the rows are never returned again; len() and the other rows' indices do not change"""
+        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+        if rows.numel() == 0:
+            return
+        if int(rows.min()) < 0 or int(rows.max()) >= self._n:
+            raise IndexError(f"EmbeddingIndex.remove: rows outside 0 .. {self._n - 1}")
+        self._bias[rows.to(self.device)] = float("-inf")
+
+    def _plan(self, Q, k, slices):
+        """(queries per call, slices): the [Q, S, k] partial lists of a call stay within SCRATCH_BYTES"""
+        lib = _lib.lib()
+        qc = Q
+        while True:
+            S = int(slices) if slices is not None else lib.coati_search_slices(self._n, qc, k)
+            if S < 1:
+                raise RuntimeError(f"coati_search_slices({self._n}, {qc}, {k}) = {S}: {lib.coati_last_error().decode('utf-8', 'replace')}")
+            if qc * S * k * 8 <= SCRATCH_BYTES or qc == 1:
+                return qc, S
+            qc = max(1, min(qc // 2, SCRATCH_BYTES // (S * k * 8)))
+
+    def search(self, queries, k, rescore=1, slices=None):
+        """(scores [Q, k] f32, rows [Q, k] int64) of the k nearest rows per query, score descending, row ascending among equal scores;
+        fewer than k rows left: the tail is (-inf, -1).  rescore = m > 1 (needs keep_f32): the best min(m * k, 128) rows of the bf16
+        search are scored again from the f32 copies and the best k of those returned.  slices: the library slices of the kernel's
+        grid (default: coati_search_slices); the result does not depend on it."""
+        k, rescore = int(k), int(rescore)
+        if k < 1 or k > K_MAX:
+            raise ValueError(f"EmbeddingIndex.search: k={k} outside 1 .. {K_MAX}")
+        if rescore < 1:
+            raise ValueError(f"EmbeddingIndex.search: rescore={rescore} < 1")
+        if rescore > 1 and not self.keep_f32:
+            raise ValueError("EmbeddingIndex.search: rescore > 1 needs the f32 copies (keep_f32=True)")
+        kk = min(rescore * k, K_MAX) if rescore > 1 else k
+        if slices is not None and (int(slices) < 1 or int(slices) * kk > MERGE_MAX):
+            raise ValueError(f"EmbeddingIndex.search: slices={slices} outside 1 .. {MERGE_MAX // kk} at k={kk}")
+        q32, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
+        Q = q16.shape[0]
+        scores = torch.full((Q, kk), float("-inf"), dtype=torch.float32, device=self.device)
+        rows = torch.full((Q, kk), -1, dtype=torch.int64, device=self.device)
+        if Q > 0 and self._n > 0:
+            if self.device.type != "cuda":
+                raise RuntimeError("EmbeddingIndex.search: the index is not on a GPU; there is no CPU fallback")
+            qc, S = self._plan(Q, kk, slices)
+            need = qc * S * kk
+            if self._scratch is None or self._scratch[0].numel() < need:
+                self._scratch = (torch.empty(need, dtype=torch.float32, device=self.device),
+                                 torch.empty(need, dtype=torch.int32, device=self.device))
+            with torch.cuda.device(self.device):
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                for lo in range(0, Q, qc):
+                    n = min(qc, Q - lo)
+                    _lib.call("coati_search_topk", _ptr(self._vec), self._n, self.dim_padded, _ptr(self._bias), _ptr(q16[lo:lo + n]), n, kk,
+                              metric_alpha(self.metric), S, _ptr(self._scratch[0]), _ptr(self._scratch[1]), _ptr(scores[lo:lo + n]),
+                              _ptr(rows[lo:lo + n]), stream)
+        if rescore > 1:
+            return self._rescore(q32, scores, rows, k)
+        return finish_scores(scores, self.metric, q16), rows
+
+    def _rescore(self, q32, scores, rows, k):
+        """the candidates' scores from the f32 copies (a gather and a bmm over [Q, m k, E]), re-sorted: score descending, row ascending"""
+        pad = rows < 0
+        order = torch.where(pad, torch.full_like(rows, 2 ** 62), rows).argsort(dim=1, stable=True)
+        rows, pad = rows.gather(1, order), pad.gather(1, order)
+        cand = self._f32[rows.clamp_min(0)]                                   # [Q, kk, E]
+        s = torch.bmm(cand, q32.unsqueeze(2)).squeeze(2)
+        if self.metric == "l2":
+            s = -(cand - q32.unsqueeze(1)).pow(2).sum(dim=2)
+        s = torch.where(pad, torch.full_like(s, float("-inf")), s)
+        s, order = s.sort(dim=1, descending=True, stable=True)
+        return s[:, :k].contiguous(), rows.gather(1, order)[:, :k].contiguous()
+
+    def save(self, path):
+        torch.save({"dim": self.dim, "metric": self.metric, "vectors": self.vectors.cpu(), "bias": self.bias.cpu(),
+                    "f32": self._f32[:self._n].cpu() if self.keep_f32 and self._f32 is not None else None}, path)
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        d = torch.load(path, map_location="cpu")
+        index = cls(d["dim"], metric=d["metric"], device=device, keep_f32=d["f32"] is not None)
+        n = d["vectors"].shape[0]
+        index._reserve(n)
+        if n:
+            index._vec[:n], index._bias[:n] = d["vectors"].to(index.device), d["bias"].to(index.device)
+            if index.keep_f32:
+                index._f32[:n] = d["f32"].to(index.device)
+        index._n = n
+        return index

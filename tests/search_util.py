@@ -1,0 +1,49 @@
+"""A pure-torch restatement of the embedding-library search of include/coati_search.h, in float64, for the tests: scores from the
+STORED bf16 rows and the bf16-rounded queries, a stable descending sort (row index ascending among equal scores), rows whose score is
+-inf never returned, padding with (-inf, -1)."""
+import torch
+
+NEG_INF = float("-inf")
+
+
+def score_matrix(rows16, bias, q16, alpha=1.0):
+    """[Q, N] float64: alpha * q . x + bias of bf16 (or any exactly representable) operands; a zero is +0"""
+    s = alpha * (q16.to(torch.float64) @ rows16.to(torch.float64).T)
+    if bias is not None:
+        s = s + bias.to(torch.float64)[None, :]
+    return s + 0.0
+
+
+def topk(s, k):
+    """(scores [Q, k] float64, rows [Q, k] int64) of a score matrix [Q, N]: score descending, row ascending among equal scores; what is
+    -inf is not a result, and what is missing is (-inf, -1)"""
+    Q, N = s.shape
+    val, idx = torch.sort(s, dim=1, descending=True, stable=True)
+    val, idx = val[:, :k], idx[:, :k]
+    idx = torch.where(val == NEG_INF, torch.full_like(idx, -1), idx)
+    if k > N:
+        val = torch.cat([val, torch.full((Q, k - N), NEG_INF, dtype=val.dtype, device=val.device)], dim=1)
+        idx = torch.cat([idx, torch.full((Q, k - N), -1, dtype=idx.dtype, device=idx.device)], dim=1)
+    return val, idx
+
+
+def search(rows16, bias, q16, k, alpha=1.0):
+    return topk(score_matrix(rows16, bias, q16, alpha), k)
+
+
+def index_scores(index, queries):
+    """The metric's scores [Q, N] float64 of an EmbeddingIndex's stored rows for `queries` as the index prepares them (normalised for
+    cosine, rounded to bf16): dot / cosine = q . x, l2 = min(2 q . x - |x|^2 - |q|^2, 0) with a removed row at -inf."""
+    from coati_amd import search as S
+    _, q16 = S.prepare_queries(queries, index.metric, index.dim, index.vectors.device)
+    s = score_matrix(index.vectors, index.bias, q16, S.metric_alpha(index.metric))
+    if index.metric == "l2":
+        s = (s - (q16.to(torch.float64) ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
+    return s
+
+
+def index_search(index, queries, k):
+    """the oracle of EmbeddingIndex.search(queries, k): (scores [Q, k] float64, rows [Q, k] int64, the score matrix)"""
+    s = index_scores(index, queries)
+    val, idx = topk(s, k)
+    return val, idx, s
