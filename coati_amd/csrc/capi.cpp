@@ -4,6 +4,7 @@
 #include "../../include/coati_hip.h"
 #include "../../include/coati_beam.h"
 #include "../../include/coati_search.h"
+#include "../../include/coati_grammar.h"
 #include <vector>
 #include "kernels.h"
 
@@ -275,6 +276,12 @@ int coati_search_topk(const uint16_t* lib, int64_t N, int E, const float* bias, 
                             S_(stream));
 }
 int coati_search_slices(int64_t N, int Q, int k) { return search_slices(N, Q, k); }
+// syntax-constrained decoding (include/coati_grammar.h)
+int coati_grammar_step(float* logits, int64_t ldl, int B, int V, const uint64_t* table, const int32_t* state_in, int32_t* state_out,
+                       const int64_t* tok_prev, const int32_t* parent, int remaining, int stop_token, void* stream) {
+  return launch_grammar_step(logits, ldl, B, V, reinterpret_cast<const unsigned long long*>(table), state_in, state_out, LL(tok_prev), parent,
+                             remaining, stop_token, S_(stream));
+}
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

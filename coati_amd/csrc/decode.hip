@@ -97,10 +97,15 @@ __device__ __forceinline__ int topk_sample_row(const float* __restrict__ lrow, i
   if (tid == 0) {
     const float mx = key2f(sm.top_k[0]) * inv_temp;
     float z = 0.f;
-    for (int r = 0; r < k; ++r) z += __expf(key2f(sm.top_k[r]) * inv_temp - mx);
+    int last = 0;   // the last candidate of non-zero weight: k - 1 on finite logits, fewer when a mask left fewer than k entries above -inf
+    for (int r = 0; r < k; ++r) {
+      const float w = __expf(key2f(sm.top_k[r]) * inv_temp - mx);
+      z += w;
+      last = w > 0.f ? r : last;
+    }
     const float target = uval * z;
     float c = 0.f;
-    int pick = k - 1;
+    int pick = last;   // (where rounding lets uval * z reach the running sum)
     for (int r = 0; r < k; ++r) {
       c += __expf(key2f(sm.top_k[r]) * inv_temp - mx);
       if (target < c) { pick = r; break; }

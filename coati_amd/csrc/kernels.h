@@ -362,6 +362,10 @@ int launch_beam_merge(const float* cand_score, const int* cand_tok, int G, int W
 int launch_search_topk(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, int k, float alpha, int S,
                        float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s);
 int search_slices(long long N, int Q, int k);   // host only: the default S
+// syntax-constrained decoding (grammar.hip, include/coati_grammar.h): state_out[b] = state_in[parent ? parent[b] : b] advanced by
+// tok_prev[b], then -inf over the entries of logits row b that may not follow; table [2][V] of 8-byte entries, states int32 [B, 4]
+int launch_grammar_step(float* logits, long long ldl, int B, int V, const unsigned long long* table, const int* state_in, int* state_out,
+                        const long long* tok_prev, const int* parent, int remaining, int stop_token, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

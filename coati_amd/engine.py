@@ -136,6 +136,8 @@ class Engine:
         self.scal = torch.zeros(16, device=dev, dtype=torch.float32)
         self._shape = None
         self.step_count = 0
+        self.last_grammar_violations = None   # bool [B] ([G, W] for beams) of the last call with grammar=: the rows that went dead
+        self.last_unstopped = None            # bool [B] of the last generate_top_k_with_inj_batch: rows whose last position was overwritten with [STOP]
 
     def __del__(self):
         try:
@@ -658,18 +660,39 @@ class Engine:
         _lib.check(self.l.coati_engine_decode_graph_build(self.h, stream()), "decode_graph_build")
 
     def generate_top_k_with_inj_batch(self, prefix, stop_token, pad_token=0, inv_temp=1.0, k=50, inj_token=None,
-                                      inj_payload=None, as_tensor=False, generator=None, use_graph=False):
+                                      inj_payload=None, as_tensor=False, generator=None, use_graph=False, grammar=None):
         """See _generate; runs on a private stream so that the decode step can be replayed from a captured HIP graph
         (use_graph=True).  Measured: replay == eager (the step is bound by the ~6 us device-side cost of each of its ~115
-        dependent kernels, not by host launch overhead), so eager is the default."""
+        dependent kernels, not by host launch overhead), so eager is the default.
+        grammar (a coati_amd.grammar.SmilesGrammar): only tokens that keep parentheses, ring digits and bracket atoms closable
+        within n_seq are drawn, so every row draws its own [STOP]; rows whose prefix already broke the syntax are unconstrained and
+        marked in last_grammar_violations (bool [B]).  Not with use_graph."""
+        if grammar is not None and use_graph:
+            raise NotImplementedError("grammar= with use_graph=True: the mask launch is not part of the captured decode graphs")
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            out = self._generate(prefix, stop_token, pad_token, inv_temp, k, inj_token, inj_payload, as_tensor, generator, use_graph)
+            out = self._generate(prefix, stop_token, pad_token, inv_temp, k, inj_token, inj_payload, as_tensor, generator, use_graph,
+                                 grammar)
         torch.cuda.current_stream(self.device).wait_stream(side)
         return out
 
-    def _generate(self, prefix, stop_token, pad_token, inv_temp, k, inj_token, inj_payload, as_tensor, generator, use_graph):
+    def _grammar_begin(self, grammar, stop_token, rows, remaining):
+        """The device states [B, 4] behind the forced token lists `rows` (one list: every row of the batch alike), `remaining` positions
+        to fill from their first token on."""
+        if int(stop_token) != grammar.stop_token or grammar.n_token != self.cfg.n_tok:
+            raise ValueError(f"grammar: built for {grammar.n_token} tokens with [STOP] = {grammar.stop_token}; the call has "
+                             f"{self.cfg.n_tok} and {int(stop_token)}")
+        return grammar.states([grammar.walk(r, remaining) for r in rows], self.device)
+
+    def _grammar_end(self, grammar, logits, state, tok_last):
+        """Advances the states by the last tokens (what is still open behind the last position is a violation) and returns the dead
+        rows, bool [B].  The consumed logits serve as the launch's operand."""
+        grammar.step(logits, state, state, tok_prev=tok_last, remaining=1)
+        return (state[:, 2] & 2) != 0
+
+    def _generate(self, prefix, stop_token, pad_token, inv_temp, k, inj_token, inj_payload, as_tensor, generator, use_graph,
+                  grammar=None):
         """RotarySmilesTransformer.generate_top_k_with_inj_batch (smiles_xformer.py:272-351) on the KV-cached decode
         path: same arguments, same stopping rules (stopped rows emit pad_token, rows that never stop get a final
         stop_token), sampling = softmax(top-k logits * inv_temp) drawn with uniforms from `generator`."""
@@ -690,7 +713,10 @@ class Engine:
         stopped = torch.zeros(B, dtype=torch.int32, device=dev)
         generated = []
         idx = 0
+        gstate = self._grammar_begin(grammar, stop_token, [prefix], n_seq).repeat(B, 1) if grammar is not None else None
         while idx < n_seq - len(prefix):
+            if grammar is not None:   # the state follows the token drawn last; n_seq - len(prefix) - idx positions are still to be drawn
+                grammar.step(logits, gstate, gstate, tok_prev=generated[-1] if generated else None, remaining=n_seq - len(prefix) - idx)
             u = torch.rand(B, device=dev, generator=generator) if k > 1 else torch.zeros(B, device=dev)
             nxt = torch.empty(B, dtype=torch.long, device=dev)
             _lib.call("coati_topk_sample", ptr(logits), logits.stride(0), B, self.cfg.n_tok, int(k), float(inv_temp), ptr(u),
@@ -702,6 +728,8 @@ class Engine:
             logits = self.decode_step(nxt, graph=use_graph)
         gen = torch.stack(generated, dim=1)
         not_stopped = stopped == 0
+        self.last_unstopped = not_stopped            # bool [B]: the rows whose last position is overwritten with [STOP] below
+        self.last_grammar_violations = self._grammar_end(grammar, logits, gstate, generated[-1]) if grammar is not None else None
         if bool(not_stopped.any()):
             gen[not_stopped, -1] = int(stop_token)
         if as_tensor:
@@ -722,22 +750,28 @@ class Engine:
         _lib.call("coati_engine_decode_step_beams", self.h, ptr(tokens), ptr(anc), ptr(inj), ptr(buf), ld, stream())
         return logits
 
-    def beam_search(self, prefix, stop_token, pad_token=0, beams=4, inj_token=None, inj_payload=None, max_len=None, length_penalty=0.0):
+    def beam_search(self, prefix, stop_token, pad_token=0, beams=4, inj_token=None, inj_payload=None, max_len=None, length_penalty=0.0,
+                    grammar=None):
         """The `beams` most likely continuations of `prefix` for every row of inj_payload [G, C], by beam search on the KV-cached decode
         path (runs on a private stream, like generate_top_k_with_inj_batch).  Returns (tokens [G, W, T] int64: prefix + generated,
         pad_token behind [STOP]; scores [G, W] f32: the sum of the generated tokens' log-probabilities, [STOP] included; lengths [G, W]:
         generated tokens up to and with [STOP]; finished [G, W] bool), per group sorted by score / max(length, 1) ** length_penalty,
         best first.  The search itself ranks by the raw sum (ties: parent beam, then token id, ascending); the penalty only reorders
         the result.  It ends when every hypothesis has drawn [STOP] or at min(max_len, n_seq) positions; a hypothesis that has not
-        finished by then is returned as it stands (finished = False, no [STOP] appended: its score is that of its tokens)."""
+        finished by then is returned as it stands (finished = False, no [STOP] appended: its score is that of its tokens).
+        grammar (a coati_amd.grammar.SmilesGrammar): only continuations that stay closable within the positions left are ranked, and
+        a beam's score is the sum of log-probabilities RENORMALISED OVER THE ADMITTED TOKENS of each step (the log-softmax of the
+        masked logits), not the model's own; every hypothesis of finite score then ends in [STOP] with everything closed.  Fewer than
+        `beams` admitted continuations leave hypotheses of score -inf.  last_grammar_violations: bool [G, W] in the result's order."""
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            out = self._beam_search(prefix, stop_token, pad_token, beams, inj_token, inj_payload, max_len, length_penalty)
+            out = self._beam_search(prefix, stop_token, pad_token, beams, inj_token, inj_payload, max_len, length_penalty, grammar=grammar)
         torch.cuda.current_stream(self.device).wait_stream(side)
         return out
 
-    def _beam_search(self, prefix, stop_token, pad_token, beams, inj_token, inj_payload, max_len, length_penalty, trace=None):
+    def _beam_search(self, prefix, stop_token, pad_token, beams, inj_token, inj_payload, max_len, length_penalty, trace=None,
+                     grammar=None):
         """beam_search on the current stream.  trace (a list, for the tests): receives per step (parent rows [B] int32, tokens [B] int64,
         scores [B] f32) of the new rows g * W + rank, on the device."""
         prefix = [int(t) for t in prefix]
@@ -772,13 +806,22 @@ class Engine:
         tok_next = torch.empty(B, dtype=torch.long, device=dev)
         nfin = torch.zeros(G, dtype=torch.int32, device=dev)
         n = 0
+        if grammar is not None:   # the automaton states ping-pong through the merge's parent rows, next to anc
+            gcur = self._grammar_begin(grammar, stop_token, [prefix], n_seq).repeat(B, 1)
+            gnxt = torch.empty_like(gcur)
+            parent = None
         while True:
+            if grammar is not None:
+                grammar.step(logits, gcur, gnxt, tok_prev=tok_next if n else None, parent=parent, remaining=steps - n)
+                gcur, gnxt = gnxt, gcur
             _lib.call("coati_beam_row_topk", ptr(logits), logits.stride(0), G, W, V, ptr(cur[0]), ptr(cur[1]), int(pad_token), ptr(cand_s),
                       ptr(cand_t), stream())
             _lib.call("coati_beam_merge", ptr(cand_s), ptr(cand_t), G, W, ptr(cur[0]), ptr(cur[1]), ptr(cur[2]), ptr(cur[3]), ptr(cur[4]),
                       steps, Tmax, m - 1 + n, n, int(stop_token), ptr(nxt[0]), ptr(nxt[1]), ptr(nxt[2]), ptr(nxt[3]), ptr(nxt[4]),
                       ptr(tok_next), ptr(nfin), stream())
             cur, nxt = nxt, cur
+            if grammar is not None:
+                parent = cur[3][:, m - 1 + n].contiguous()
             if trace is not None:
                 trace.append((cur[3][:, m - 1 + n].clone(), tok_next.clone(), cur[0].clone()))
             n += 1
@@ -788,11 +831,16 @@ class Engine:
         scores, fin, lens, hist = cur[0].view(G, W), cur[1].view(G, W) != 0, cur[2].view(G, W), cur[4][:, :n].reshape(G, W, n)
         key = scores / lens.clamp(min=1).to(torch.float32) ** float(length_penalty)
         order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        self.last_grammar_violations = None
+        if grammar is not None:
+            grammar.step(logits, gcur, gnxt, tok_prev=tok_next, parent=parent, remaining=1)
+            self.last_grammar_violations = torch.gather(((gnxt[:, 2] & 2) != 0).view(G, W), 1, order)
         head = torch.tensor(prefix, dtype=torch.long, device=dev).view(1, 1, m).expand(G, W, m)
         tokens = torch.cat([head, torch.gather(hist, 1, order.unsqueeze(2).expand(G, W, n))], dim=2)
         return tokens, torch.gather(scores, 1, order), torch.gather(lens, 1, order), torch.gather(fin, 1, order)
 
-    def generate_topk_batch(self, prefix, stop_token, pad_token=0, inv_temp=2, k=10, generator=None, prefill=True, ragged=False):
+    def generate_topk_batch(self, prefix, stop_token, pad_token=0, inv_temp=2, k=10, generator=None, prefill=True, ragged=False,
+                            grammar=None):
         """RotarySmilesTransformer.generate_topk_batch (smiles_xformer.py:157-198): continue B prompts of different lengths
         (token lists) on the KV-cached decode path.  Returns B lists of n_seq ints: every prompt verbatim, each row sampled
         from its own prompt end (softmax(top-k logits * inv_temp), uniforms from `generator`), [STOP] and then pad_token,
@@ -802,16 +850,20 @@ class Engine:
         ragged=True: every prompt is prefilled in FULL (decode_prefill_rows) and the rows then step at their own positions, each
         sampling from its own prompt end at once; a row is done when it draws [STOP], and the call when every row is.  Same output
         format.  Off by default: with k > 1 the uniforms reach the rows in another order, so a seed's samples differ from the
-        aligned path's.  (fp8 engines: the prompts go through forced ragged steps.)"""
-        out, _ = self._complete(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, None, ragged)
+        aligned path's.  (fp8 engines: the prompts go through forced ragged steps.)
+        grammar (a coati_amd.grammar.SmilesGrammar; aligned path only): the prompt's tokens advance each row's automaton state, and only
+        tokens that keep the row closable within n_seq are drawn -- the completion of `c1ccc(` closes it.  A prompt that breaks the
+        syntax itself (`)`) leaves its row unconstrained and marked in last_grammar_violations (bool [B])."""
+        out, _ = self._complete(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, None, ragged, grammar)
         return out.tolist()
 
     def generate_topk_with_inj(self, prefix, stop_token, inv_temp=1, k=50, inj_token=None, inj_payload=None, generator=None,
-                               prefill=True):
+                               prefill=True, grammar=None):
         """RotarySmilesTransformer.generate_topk_with_inj (smiles_xformer.py:215-270): one prompt (token list) whose
         inj_token slot carries inj_payload ([C], or a scalar that fills all C channels, as the reference's assignment
         broadcasts it); sampling stops on stop_token or after n_seq - 1 generated tokens.  Returns prefix + generated.
-        A sequence that has not stopped within n_seq positions is returned at n_seq positions (the reference raises)."""
+        A sequence that has not stopped within n_seq positions is returned at n_seq positions (the reference raises).
+        grammar: as in generate_topk_batch."""
         prefix = [int(t) for t in prefix]
         C = self.cfg.n_hidden_xformer
         inj = None
@@ -825,21 +877,25 @@ class Engine:
                 p = p.expand(C)
             assert p.numel() == C, f"inj_payload: {p.numel()} values for {C} channels"
             inj = p.reshape(1, C).contiguous()
-        out, n = self._complete([prefix], stop_token, 0, inv_temp, k, generator, prefill, inj)
+        out, n = self._complete([prefix], stop_token, 0, inv_temp, k, generator, prefill, inj, grammar=grammar)
         return out[0, :n].tolist()
 
-    def _complete(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection, ragged=False):
+    def _complete(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection, ragged=False, grammar=None):
         """The decode loop of generate_topk_batch / generate_topk_with_inj on a private stream.  Returns (tokens [B, n_seq] on
         the host, number of columns written)."""
+        if grammar is not None and ragged:
+            raise NotImplementedError("grammar= with ragged=True: the ragged sampler draws and advances in one launch")
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            fn = self._complete_rows_on_stream if ragged else self._complete_on_stream
-            out = fn(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection)
+            if ragged:
+                out = self._complete_rows_on_stream(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection)
+            else:
+                out = self._complete_on_stream(prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection, grammar)
         torch.cuda.current_stream(self.device).wait_stream(side)
         return out
 
-    def _complete_on_stream(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection):
+    def _complete_on_stream(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection, grammar=None):
         n_seq = int(self.cfg.n_seq)
         prompt, plen = pack_prompts(prefix, n_seq)
         B = prompt.shape[0]
@@ -856,7 +912,13 @@ class Engine:
         else:   # (fp8 engines: the prompt goes through forced steps)
             logits = self.decode_step(out[:, 0], injection)
             pos = 1
+        nxt = None
+        self.last_grammar_violations = None
+        if grammar is not None:   # the state behind the columns fed so far; forced prompt tokens behind them advance it like drawn ones
+            gstate = self._grammar_begin(grammar, stop_token, [r[:pos] for r in prompt.tolist()], n_seq)
         while pos < n_seq:
+            if grammar is not None:
+                grammar.step(logits, gstate, gstate, tok_prev=nxt, remaining=n_seq - pos)
             u = torch.rand(B, device=dev, generator=generator) if k > 1 else torch.zeros(B, device=dev)
             nxt = torch.empty(B, dtype=torch.long, device=dev)
             _lib.call("coati_topk_sample_prompt", ptr(logits), logits.stride(0), B, self.cfg.n_tok, int(k), float(inv_temp), ptr(u),
@@ -866,6 +928,8 @@ class Engine:
             if pos >= n_seq or (pos >= longest and int(stopped.sum().item()) >= B):
                 break
             logits = self.decode_step(nxt, injection)
+        if grammar is not None:
+            self.last_grammar_violations = self._grammar_end(grammar, logits, gstate, nxt)
         return out.cpu(), pos
 
     def _complete_rows_on_stream(self, prefix, stop_token, pad_token, inv_temp, k, generator, prefill, injection):
@@ -914,7 +978,7 @@ class Engine:
         return out, width
 
     def generate_stream(self, prefix, stop_token, pad_token=0, inv_temp=1.0, k=50, inj_token=None, inj_payload=None, slots=None,
-                        generator=None, as_tensor=False, poll=1, forced=None):
+                        generator=None, as_tensor=False, poll=1, forced=None, grammar=None):
         """generate_top_k_with_inj_batch for N = inj_payload.shape[0] requests on `slots` cache slots (default min(N,
         slots.STREAM_SLOT_CAP)): a slot whose row has drawn [STOP] is handed the next request at position 0 while the other rows
         carry on, so no step is spent on finished rows as long as requests wait.  A request enters with the first prefix token and
@@ -925,7 +989,9 @@ class Engine:
         poll: the host looks for ended rows every `poll` steps (1: every step, as the aligned loops synchronise every step).
         forced (tokens [N, W], lengths [N]): request n emits tokens[n, :lengths[n]] through the sampler's prompt rule instead of
         the prefix (benchmarks with random weights, which never draw [STOP], force their row lengths with it).
-        self.stream_steps holds the number of decode steps the call took."""
+        self.stream_steps holds the number of decode steps the call took.  grammar= is not supported here."""
+        if grammar is not None:
+            raise NotImplementedError("grammar= with generate_stream / slots=: the ragged sampler draws and advances in one launch")
         from .slots import STREAM_SLOT_CAP, SlotScheduler
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))

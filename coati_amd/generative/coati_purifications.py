@@ -95,24 +95,27 @@ def _embed_padded(encoder, tokenizer, tok: torch.Tensor, pad: int) -> torch.Tens
     return h
 
 
-def _decode_batch(encoder, H: torch.Tensor, tokenizer, generator=None, slots=None) -> List[str]:
+def _decode_batch(encoder, H: torch.Tensor, tokenizer, generator=None, slots=None, grammar=None) -> List[str]:
     fn = encoder.hcoati_to_2d_batch if _is_coati2(encoder) else encoder.hclip_to_2d_batch
     kw = {} if generator is None else {"generator": generator}
+    if grammar is not None:    # (coati_amd.grammar.SmilesGrammar: syntax-constrained decoding)
+        kw["grammar"] = grammar
     if slots is not None:
         kw["slots"] = slots
     return list(fn(H, tokenizer, **kw))
 
 
-def decode_most_likely(model, vectors: torch.Tensor, tokenizer, beams: int = 4):
+def decode_most_likely(model, vectors: torch.Tensor, tokenizer, beams: int = 4, grammar=None):
     """The `beams` most likely SMILES of every row of vectors [N, E] with their log-likelihoods, best first: per vector a list of
     (smiles, log_likelihood) from beam search (hclip_to_2d_beam, hcoati_to_2d_beam on COATI2) -- the deterministic counterpart of
-    drawing samples and keeping the most frequent one."""
+    drawing samples and keeping the most frequent one.  grammar (coati_amd.grammar.SmilesGrammar): only syntactically closable
+    continuations are ranked; the log-likelihoods are then renormalised over the admitted tokens (Engine.beam_search)."""
     fn = model.hcoati_to_2d_beam if _is_coati2(model) else model.hclip_to_2d_beam
     V = vectors if vectors.dim() == 2 else vectors.reshape(1, -1)
-    return fn(V, tokenizer, beams=beams)
+    return fn(V, tokenizer, beams=beams, **({} if grammar is None else {"grammar": grammar}))
 
 
-def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=None, slots=None) -> List[Optional[List[str]]]:
+def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=None, slots=None, grammar=None) -> List[Optional[List[str]]]:
     """n_rep decodes of every row of V [N, E], as few decode calls as DECODE_ROW_CAP allows (whole vectors per call).  Per vector the
     list of its n_rep strings in sample order, or None when its decode call raised.
     slots (a number; default None = the chunked calls): ONE streamed call of all N * n_rep rows on that many cache slots
@@ -120,7 +123,7 @@ def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=
     N = V.shape[0]
     if slots is not None:
         try:
-            got = _decode_batch(encoder, V.repeat_interleave(n_rep, dim=0), tokenizer, generator, slots=int(slots))
+            got = _decode_batch(encoder, V.repeat_interleave(n_rep, dim=0), tokenizer, generator, slots=int(slots), grammar=grammar)
             assert len(got) == N * n_rep
             return [got[i * n_rep:(i + 1) * n_rep] for i in range(N)]
         except Exception:
@@ -131,7 +134,7 @@ def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=
         hi = min(N, lo + per_call)
         H = V[lo:hi].repeat_interleave(n_rep, dim=0)
         try:
-            got = _decode_batch(encoder, H, tokenizer, generator)
+            got = _decode_batch(encoder, H, tokenizer, generator, grammar=grammar)
             assert len(got) == H.shape[0]
             out += [got[i * n_rep:(i + 1) * n_rep] for i in range(hi - lo)]
         except Exception:
@@ -139,16 +142,18 @@ def _decode_repeated(encoder, V: torch.Tensor, tokenizer, n_rep: int, generator=
     return out
 
 
-def _decode_like_one(encoder, V: torch.Tensor, tokenizer, k: int, generator=None) -> List[str]:
+def _decode_like_one(encoder, V: torch.Tensor, tokenizer, k: int, generator=None, grammar=None) -> List[str]:
     """k independent draws from the distribution of hclip_to_2d(V) (hcoati_to_2d on COATI2) in one decode call.  hclip_to_2d injects
     h_token[0] -- for a 1-D V its first channel, a scalar spread over the [UNK] row --, and so does this."""
     if getattr(encoder, "engine", None) is None:
         one = encoder.hcoati_to_2d if _is_coati2(encoder) else encoder.hclip_to_2d
         kw = {} if generator is None else {"generator": generator}
+        if grammar is not None:
+            kw["grammar"] = grammar
         return [one(V, tokenizer, **kw) for _ in range(k)]
     h = V.to(encoder.device, torch.float32)
     if h.dim() == 2:
-        return _decode_batch(encoder, h[:1].expand(k, -1).contiguous(), tokenizer, generator)
+        return _decode_batch(encoder, h[:1].expand(k, -1).contiguous(), tokenizer, generator, grammar=grammar)
     from ..models.encoding.clip_e2e import injection_prefix
     encoder._sync_tokens(tokenizer)
     h2 = h.reshape(1, -1)
@@ -156,7 +161,7 @@ def _decode_like_one(encoder, V: torch.Tensor, tokenizer, k: int, generator=None
     payload = h_token[0, 0].expand(k, h_token.shape[1]).contiguous()
     gen = encoder.xformer.generate_top_k_with_inj_batch(prefix=injection_prefix(tokenizer, "[SMILES]", False), stop_token=tokenizer.stop_token,
                                                         inv_temp=2, k=100, pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
-                                                        inj_payload=payload, generator=generator)
+                                                        inj_payload=payload, generator=generator, **({} if grammar is None else {"grammar": grammar}))
     return [tokenizer.decode(t, special=False) for t in gen]
 
 
@@ -283,28 +288,31 @@ def _purify(V: torch.Tensor, plan: PurificationPlan, encoder, tokenizer) -> torc
     return ops.group_mean_rows(x, off, w=w.to(emb.device), fallback=Vd)
 
 
-def purify_vector(V: torch.Tensor, encoder, tokenizer, n_rep=128, canon_smiles=None, generator=None) -> torch.Tensor:
+def purify_vector(V: torch.Tensor, encoder, tokenizer, n_rep=128, canon_smiles=None, generator=None, grammar=None) -> torch.Tensor:
     """coati_purifications.py:51-97: decode n_rep copies of V [E]; keep the strings that canonicalise and tokenize; return the mean of
-    their embeddings [E].  V itself (the same object) when the decoder raises or nothing is kept."""
+    their embeddings [E].  V itself (the same object) when the decoder raises or nothing is kept.  grammar (here and in the functions
+    below; coati_amd.grammar.SmilesGrammar): the decodes are syntax-constrained, so no draw is spent on an unclosed string."""
     with torch.no_grad():
-        decoded = _decode_repeated(encoder, V.reshape(1, -1).to(encoder.device, torch.float32), tokenizer, n_rep, generator)
+        decoded = _decode_repeated(encoder, V.reshape(1, -1).to(encoder.device, torch.float32), tokenizer, n_rep, generator,
+                                   grammar=grammar)
         plan = purification_plan(decoded, tokenizer, canon_smiles)
         if plan.failed[0] or not plan.members[0]:
             return V
         return _purify(V.reshape(1, -1), plan, encoder, tokenizer)[0]
 
 
-def purify_vectors(V: torch.Tensor, encoder, tokenizer, n_rep=128, canon_smiles=None, generator=None) -> torch.Tensor:
+def purify_vectors(V: torch.Tensor, encoder, tokenizer, n_rep=128, canon_smiles=None, generator=None, grammar=None) -> torch.Tensor:
     """purify_vector of every row of V [N, E] -> [N, E]: one decode of the N * n_rep rows (calls of at most DECODE_ROW_CAP rows), the
     distinct molecules encoded once on packed rows, and per vector the multiplicity-weighted mean of its molecules' embeddings
     (coati_group_mean_rows).  Given the same decoded strings, row g equals purify_vector(V[g]) to rounding."""
     assert V.dim() == 2, "purify_vectors: V [N, E]"
     with torch.no_grad():
-        decoded = _decode_repeated(encoder, V.to(encoder.device, torch.float32), tokenizer, n_rep, generator)
+        decoded = _decode_repeated(encoder, V.to(encoder.device, torch.float32), tokenizer, n_rep, generator, grammar=grammar)
         return _purify(V, purification_plan(decoded, tokenizer, canon_smiles), encoder, tokenizer)
 
 
-def force_decode_valid(V: torch.Tensor, encoder, tokenizer, max_attempts: int = 2000, canon_smiles=None, generator=None) -> str:
+def force_decode_valid(V: torch.Tensor, encoder, tokenizer, max_attempts: int = 2000, canon_smiles=None, generator=None,
+                       grammar=None) -> str:
     """coati_purifications.py:100-119: the first valid decode of V (as decoded, not canonicalised), or "C" after max_attempts attempts.
     Attempts are drawn FORCE_DECODE_CHUNK per decode call and taken in sample order: the distribution of the reference's loop, not its
     random stream.  A decode call that raises spends its attempts."""
@@ -314,7 +322,7 @@ def force_decode_valid(V: torch.Tensor, encoder, tokenizer, max_attempts: int = 
         k = min(FORCE_DECODE_CHUNK, max_attempts - done)
         try:
             with torch.no_grad():
-                cands = _decode_like_one(encoder, V, tokenizer, k, generator)
+                cands = _decode_like_one(encoder, V, tokenizer, k, generator, grammar)
         except Exception:
             cands = []
         for S in cands[:k]:
@@ -325,15 +333,15 @@ def force_decode_valid(V: torch.Tensor, encoder, tokenizer, max_attempts: int = 
 
 
 def force_decode_valid_batch(V: torch.Tensor, encoder, tokenizer, batch_size: int = 128, max_attempts: int = 4, canon_smiles=None,
-                             generator=None) -> str:
+                             generator=None, grammar=None) -> str:
     """coati_purifications.py:122-154: up to max_attempts decodes of batch_size copies of V [E]; the most frequent valid canonical string
     of the first attempt that has one (ties: first in decode order), "C" when none does."""
     return force_decode_valid_batches(V.reshape(1, -1), encoder, tokenizer, batch_size=batch_size, max_attempts=max_attempts,
-                                      canon_smiles=canon_smiles, generator=generator)[0]
+                                      canon_smiles=canon_smiles, generator=generator, grammar=grammar)[0]
 
 
 def force_decode_valid_batches(V: torch.Tensor, encoder, tokenizer, batch_size: int = 128, max_attempts: int = 4, canon_smiles=None,
-                               generator=None) -> List[str]:
+                               generator=None, grammar=None) -> List[str]:
     """force_decode_valid_batch of every row of V [N, E] -> N strings.  Each attempt decodes the vectors still unresolved together
     (calls of at most DECODE_ROW_CAP rows); each vector follows the reference's rule."""
     assert V.dim() == 2, "force_decode_valid_batches: V [N, E]"
@@ -346,7 +354,7 @@ def force_decode_valid_batches(V: torch.Tensor, encoder, tokenizer, batch_size: 
         if not todo:
             break
         with torch.no_grad():
-            decoded = _decode_repeated(encoder, Vd[todo], tokenizer, batch_size, generator)
+            decoded = _decode_repeated(encoder, Vd[todo], tokenizer, batch_size, generator, grammar=grammar)
         still = []
         for g, strings in zip(todo, decoded):
             pick = most_frequent_valid(strings, canon)

@@ -222,13 +222,14 @@ def injection_prefix(tokenizer, fill_in_from: str, do_suffix: bool):
     return [int(getattr(tokenizer, n)) for n in names]
 
 
-def beam_decodings(engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty):
+def beam_decodings(engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty, grammar=None):
     """Engine.beam_search from `prefix` with h_token [G, C] in the [UNK] slot, as per-embedding lists of (smiles, log_likelihood), best
     first (the token lists themselves for a tokenizer that cannot decode); return_tokens: (those, the hypotheses' token lists: the
-    prompt and the generated tokens up to and with [STOP])."""
+    prompt and the generated tokens up to and with [STOP]).  grammar: Engine.beam_search's (the scores are then renormalised over the
+    admitted tokens)."""
     tokens, scores, lengths, _ = engine.beam_search(prefix=prefix, stop_token=tokenizer.stop_token, pad_token=tokenizer.pad_token,
                                                     beams=beams, inj_token=tokenizer.unk_token, inj_payload=h_token,
-                                                    length_penalty=length_penalty)
+                                                    length_penalty=length_penalty, grammar=grammar)
     tokens, scores, lengths = tokens.tolist(), scores.tolist(), lengths.tolist()
     m = len(prefix)
     rows = [[hyp[:m + n] for hyp, n in zip(tg, ng)] for tg, ng in zip(tokens, lengths)]
@@ -402,12 +403,14 @@ class e3gnn_smiles_clip_e2e(nn.Module):
     @torch.no_grad()
     def hclip_to_2d_batch(self, h_clip, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
                           inv_temp: float = 2, k: int = 100, do_suffix=False, keep_special: bool = False,
-                          return_tokens: bool = False, generator=None, slots=None):
+                          return_tokens: bool = False, generator=None, slots=None, grammar=None):
         """clip_e2e.py:544-588: decode a batch of clip embeddings into token sequences (and SMILES when the tokenizer
         can decode).  Prefix "[CLIP][UNK]" + fill_in_from (+ "[SUFFIX][MIDDLE]"), the [UNK] slot carries the
         special-token embedding of h_clip; generation = top-k sampling on the KV-cached decode path.
         slots: None = one aligned batch of all rows; a number = Engine.generate_stream on that many cache slots (rows that have
-        stopped hand their slot to the next embedding; the draws of a seed differ from the aligned path's)."""
+        stopped hand their slot to the next embedding; the draws of a seed differ from the aligned path's).
+        grammar (coati_amd.grammar.SmilesGrammar.from_tokenizer(tokenizer)): syntax-constrained decoding -- every string has its
+        parentheses, ring digits and bracket atoms closed and ends in a drawn [STOP]; aligned path only (not with slots)."""
         self._sync_tokens(tokenizer)
         assert fill_in_from in ("[SMILES]", "[GRAPH]")
         if noise_scale > 0:
@@ -417,11 +420,11 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         if slots is None:
             generation = self.engine.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp,
                                                                    k=k, pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
-                                                                   inj_payload=h_token, generator=generator)
+                                                                   inj_payload=h_token, generator=generator, grammar=grammar)
         else:
             generation = self.engine.generate_stream(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
                                                      pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token, inj_payload=h_token,
-                                                     slots=int(slots), generator=generator)
+                                                     slots=int(slots), generator=generator, grammar=grammar)
         if hasattr(tokenizer, "decode"):
             smiles_list = [tokenizer.decode(t, special=keep_special) for t in generation]
         else:
@@ -430,34 +433,36 @@ class e3gnn_smiles_clip_e2e(nn.Module):
 
     @torch.no_grad()
     def points_to_2d_batch(self, atom_batch, coords_batch, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
-                           do_suffix: bool = False, inv_temp: float = 2, k=100, keep_special=False, generator=None, slots=None):
-        """clip_e2e.py:590-632: encode_points, then the hclip_to_2d_batch flow (noise added out of place; slots as there)."""
+                           do_suffix: bool = False, inv_temp: float = 2, k=100, keep_special=False, generator=None, slots=None,
+                           grammar=None):
+        """clip_e2e.py:590-632: encode_points, then the hclip_to_2d_batch flow (noise added out of place; slots, grammar as there)."""
         h_clip = self.encode_points(atom_batch, coords_batch)
         return self.hclip_to_2d_batch(h_clip, tokenizer, fill_in_from=fill_in_from, noise_scale=noise_scale, inv_temp=inv_temp, k=k,
-                                      do_suffix=do_suffix, keep_special=keep_special, generator=generator, slots=slots)
+                                      do_suffix=do_suffix, keep_special=keep_special, generator=generator, slots=slots, grammar=grammar)
 
     @torch.no_grad()
     def hclip_to_2d_beam(self, h_clip, tokenizer, beams: int = 4, fill_in_from: str = "[SMILES]", do_suffix: bool = False,
-                         keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0):
+                         keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0, grammar=None):
         """The `beams` most likely decodings of every clip embedding of h_clip [G, E], by beam search (Engine.beam_search) from the
         prompt of hclip_to_2d_batch: per embedding a list of (smiles, log_likelihood), best first -- the log-likelihood is the sum of
         the generated tokens' log-probabilities, [STOP] included.  return_tokens=True: also the hypotheses' token lists, per embedding
-        (the prompt, the generated tokens up to and with [STOP]).  No reference counterpart (the reference only samples)."""
+        (the prompt, the generated tokens up to and with [STOP]).  No reference counterpart (the reference only samples).
+        grammar: see Engine.beam_search."""
         self._sync_tokens(tokenizer)
         assert fill_in_from in ("[SMILES]", "[GRAPH]")
         h_token = self.special_tokens_from_clip(h_clip)
         prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
-        return beam_decodings(self.engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty)
+        return beam_decodings(self.engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty, grammar)
 
     @torch.no_grad()
     def points_to_2d_beam(self, atoms, coords, tokenizer, beams: int = 4, fill_in_from: str = "[SMILES]", do_suffix: bool = False,
-                          keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0):
+                          keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0, grammar=None):
         """encode_points, then hclip_to_2d_beam."""
         return self.hclip_to_2d_beam(self.encode_points(atoms, coords), tokenizer, beams=beams, fill_in_from=fill_in_from,
                                      do_suffix=do_suffix, keep_special=keep_special, return_tokens=return_tokens,
-                                     length_penalty=length_penalty)
+                                     length_penalty=length_penalty, grammar=grammar)
 
-    def _to_2d_one(self, h_clip, tokenizer, fill_in_from, noise_scale, suffix, inv_temp, k, generator):
+    def _to_2d_one(self, h_clip, tokenizer, fill_in_from, noise_scale, suffix, inv_temp, k, generator, grammar=None):
         """hclip_to_2d / points_to_2d: the special token of h_clip injected as the reference does it, h_token[0] -- the first row of a
         [B, E] input, and for a 1-D [E] input its first CHANNEL, a scalar that the reference's assignment spreads over all C."""
         self._sync_tokens(tokenizer)
@@ -469,32 +474,36 @@ class e3gnn_smiles_clip_e2e(nn.Module):
         payload = h_token[0] if h.dim() == 2 else h_token[0, 0]
         prefix = tokenizer.tokenize_text("[CLIP][UNK]" + fill_in_from + suffix, pad=False)
         generation = self.engine.generate_topk_with_inj(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
-                                                        inj_token=tokenizer.unk_token, inj_payload=payload, generator=generator)
+                                                        inj_token=tokenizer.unk_token, inj_payload=payload, generator=generator,
+                                                        grammar=grammar)
         return tokenizer.decode(generation, special=False) if fill_in_from == "[SMILES]" else tokenizer.decode(generation)
 
     @torch.no_grad()
     def points_to_2d(self, atoms, coords, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0, inv_temp: float = 2,
-                     k: int = 100, generator=None):
-        """clip_e2e.py:465-501: one molecule's atoms / coords -> SMILES (prefix [CLIP][UNK]<fill_in_from>[SUFFIX][MIDDLE])."""
+                     k: int = 100, generator=None, grammar=None):
+        """clip_e2e.py:465-501: one molecule's atoms / coords -> SMILES (prefix [CLIP][UNK]<fill_in_from>[SUFFIX][MIDDLE]).
+        grammar: as in hclip_to_2d_batch."""
         h_clip = self.encode_points(atoms, coords)
-        return self._to_2d_one(h_clip, tokenizer, fill_in_from, noise_scale, "[SUFFIX][MIDDLE]", inv_temp, k, generator)
+        return self._to_2d_one(h_clip, tokenizer, fill_in_from, noise_scale, "[SUFFIX][MIDDLE]", inv_temp, k, generator, grammar)
 
     @torch.no_grad()
     def hclip_to_2d(self, h_clip, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0, do_suffix: bool = False,
-                    inv_temp: float = 2, k: int = 100, generator=None):
-        """clip_e2e.py:503-542: one embedding ([1, E] or [E]) -> SMILES (prefix [CLIP][UNK]<fill_in_from>, + [SUFFIX][MIDDLE])."""
+                    inv_temp: float = 2, k: int = 100, generator=None, grammar=None):
+        """clip_e2e.py:503-542: one embedding ([1, E] or [E]) -> SMILES (prefix [CLIP][UNK]<fill_in_from>, + [SUFFIX][MIDDLE]).
+        grammar: as in hclip_to_2d_batch."""
         return self._to_2d_one(h_clip, tokenizer, fill_in_from, noise_scale, "[SUFFIX][MIDDLE]" if do_suffix else "", inv_temp, k,
-                               generator)
+                               generator, grammar)
 
     @torch.no_grad()
     def complete_batch(self, prefixes: List[str], tokenizer, inv_temp: float = 2, k: int = 100, keep_special: bool = False,
-                       de_fim: bool = True, generator=None):
+                       de_fim: bool = True, generator=None, grammar=None):
         """clip_e2e.py:744-770: continue text prompts of different lengths (e.g. fill-in-middle [SMILES]..[SUFFIX]..[MIDDLE]);
-        no injection.  Returns the decoded strings."""
+        no injection.  Returns the decoded strings.  grammar: the prompts' tokens advance the automaton, the completion closes what
+        they opened (Engine.generate_topk_batch)."""
         self._sync_tokens(tokenizer)
         tokens = [tokenizer.tokenize_text(p, pad=False) for p in prefixes]
         generation = self.engine.generate_topk_batch(prefix=tokens, stop_token=tokenizer.stop_token, pad_token=tokenizer.pad_token,
-                                                     inv_temp=inv_temp, k=k, generator=generator)
+                                                     inv_temp=inv_temp, k=k, generator=generator, grammar=grammar)
         return [tokenizer.decode(t, special=keep_special, de_fim=de_fim) for t in generation]
 
     def _score(self, tokens, y_next, h_clip=None, raw_tokens=None, differentiable=False):

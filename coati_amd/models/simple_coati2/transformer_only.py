@@ -130,8 +130,9 @@ class COATI_Smiles_Inference(nn.Module):
         return h
 
     @torch.no_grad()
-    def hcoati_to_2d(self, h_coati, tokenizer, fill_in_from="[SMILES]", noise_scale=0.0, do_suffix=False, inv_temp=2, k=100, generator=None):
-        """transformer_only.py:112-152: one embedding -> SMILES.  The payload is h_token[0]: the first row of a [B, E] input, and for a
+    def hcoati_to_2d(self, h_coati, tokenizer, fill_in_from="[SMILES]", noise_scale=0.0, do_suffix=False, inv_temp=2, k=100, generator=None,
+                     grammar=None):
+        """transformer_only.py:112-152: one embedding -> SMILES (grammar: syntax-constrained decoding, see hcoati_to_2d_batch).  The payload is h_token[0]: the first row of a [B, E] input, and for a
         1-D [E] input its first channel, a scalar the reference's assignment spreads over all C.  Noise is added out of place."""
         self._sync_tokens(tokenizer)
         assert fill_in_from == "[SMILES]" or fill_in_from == "[GRAPH]"
@@ -142,16 +143,19 @@ class COATI_Smiles_Inference(nn.Module):
         payload = h_token[0] if h.dim() == 2 else h_token[0, 0]
         prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
         generation = self.xformer.generate_topk_with_inj(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
-                                                         inj_token=tokenizer.unk_token, inj_payload=payload, generator=generator)
+                                                         inj_token=tokenizer.unk_token, inj_payload=payload, generator=generator,
+                                                         grammar=grammar)
         return tokenizer.decode(generation, special=False) if fill_in_from == "[SMILES]" else tokenizer.decode(generation)
 
     @torch.no_grad()
     def hcoati_to_2d_batch(self, h_coati: torch.Tensor, tokenizer, fill_in_from: str = "[SMILES]", noise_scale: float = 0.0,
                            inv_temp: float = 2, k: int = 100, do_suffix=False, keep_special: bool = False, return_tokens: bool = False,
-                           generator=None, slots=None):
+                           generator=None, slots=None, grammar=None):
         """transformer_only.py:154-200: decode [B, E] embeddings through coati_to_token at the [UNK] slot of
         [CLIP][UNK]<fill_in_from> (+ [SUFFIX][MIDDLE]); top-k sampling on the KV-cached decode path.  Noise is added out of place.
-        slots: None = one aligned batch of all rows; a number = Engine.generate_stream on that many cache slots."""
+        slots: None = one aligned batch of all rows; a number = Engine.generate_stream on that many cache slots.
+        grammar (coati_amd.grammar.SmilesGrammar.from_tokenizer(tokenizer)): every string has its parentheses, ring digits and bracket
+        atoms closed and ends in a drawn [STOP]; aligned path only (not with slots)."""
         assert k > 1
         self._sync_tokens(tokenizer)
         h = h_coati.to(self.device, torch.float32)
@@ -164,11 +168,11 @@ class COATI_Smiles_Inference(nn.Module):
         if slots is None:
             generation = self.xformer.generate_top_k_with_inj_batch(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
                                                                     pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token,
-                                                                    inj_payload=h_token, generator=generator)
+                                                                    inj_payload=h_token, generator=generator, grammar=grammar)
         else:
             generation = self.engine.generate_stream(prefix=prefix, stop_token=tokenizer.stop_token, inv_temp=inv_temp, k=k,
                                                      pad_token=tokenizer.pad_token, inj_token=tokenizer.unk_token, inj_payload=h_token,
-                                                     slots=int(slots), generator=generator)
+                                                     slots=int(slots), generator=generator, grammar=grammar)
         smiles_list = [tokenizer.decode(t, special=keep_special) for t in generation]
         if return_tokens:
             return smiles_list, generation
@@ -176,15 +180,16 @@ class COATI_Smiles_Inference(nn.Module):
 
     @torch.no_grad()
     def hcoati_to_2d_beam(self, h_coati, tokenizer, beams: int = 4, fill_in_from: str = "[SMILES]", do_suffix: bool = False,
-                          keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0):
+                          keep_special: bool = False, return_tokens: bool = False, length_penalty: float = 0.0, grammar=None):
         """The `beams` most likely decodings of every embedding of h_coati [G, E], by beam search (Engine.beam_search) through
         coati_to_token at the [UNK] slot of hcoati_to_2d_batch's prompt: per embedding a list of (smiles, log_likelihood), best first;
-        return_tokens=True: also the hypotheses' token lists.  No reference counterpart (the reference only samples)."""
+        return_tokens=True: also the hypotheses' token lists.  No reference counterpart (the reference only samples).
+        grammar: see Engine.beam_search."""
         self._sync_tokens(tokenizer)
         assert fill_in_from == "[SMILES]" or fill_in_from == "[GRAPH]"
         h_token = self.engine.token_head(h_coati.to(self.device, torch.float32))
         prefix = injection_prefix(tokenizer, fill_in_from, do_suffix)
-        return beam_decodings(self.engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty)
+        return beam_decodings(self.engine, tokenizer, prefix, h_token, beams, keep_special, return_tokens, length_penalty, grammar)
 
     def hcoati_and_tokens_to_likelihood(self, h_coati: torch.Tensor, smiles, tokenizer, do_suffix=False) -> torch.Tensor:
         """The likelihood of a SMILES string under an embedding (COATI1's hclip_and_tokens_to_likelihood, clip_e2e.py:634-665, on
