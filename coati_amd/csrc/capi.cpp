@@ -5,6 +5,7 @@
 #include "../../include/coati_beam.h"
 #include "../../include/coati_search.h"
 #include "../../include/coati_grammar.h"
+#include "../../include/coati_screen.h"
 #include <vector>
 #include "kernels.h"
 
@@ -281,6 +282,11 @@ int coati_grammar_step(float* logits, int64_t ldl, int B, int V, const uint64_t*
                        const int64_t* tok_prev, const int32_t* parent, int remaining, int stop_token, void* stream) {
   return launch_grammar_step(logits, ldl, B, V, reinterpret_cast<const unsigned long long*>(table), state_in, state_out, LL(tok_prev), parent,
                              remaining, stop_token, S_(stream));
+}
+// property heads (include/coati_screen.h)
+int coati_head_eval(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
+                    int D, const float* wl, const float* bl, int P, int F, float* out, int64_t ldo, void* stream) {
+  return launch_head_eval(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, F, out, ldo, S_(stream));
 }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,

@@ -366,6 +366,9 @@ int search_slices(long long N, int Q, int k);   // host only: the default S
 // tok_prev[b], then -inf over the entries of logits row b that may not follow; table [2][V] of 8-byte entries, states int32 [B, 4]
 int launch_grammar_step(float* logits, long long ldl, int B, int V, const unsigned long long* table, const int* state_in, int* state_out,
                         const long long* tok_prev, const int* parent, int remaining, int stop_token, hipStream_t s);
+// property heads (screen.hip, include/coati_screen.h): out [N, P] = the FC-ResNet head (w0, b0 | wr, br x D | wl, bl) on the bf16 rows x [N, E]
+int launch_head_eval(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
+                     int D, const float* wl, const float* bl, int P, int F, float* out, long long ldo, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

@@ -167,11 +167,13 @@ class EmbeddingIndex:
                 return qc, S
             qc = max(1, min(qc // 2, SCRATCH_BYTES // (S * k * 8)))
 
-    def search(self, queries, k, rescore=1, slices=None):
+    def search(self, queries, k, rescore=1, slices=None, bias=None):
         """(scores [Q, k] f32, rows [Q, k] int64) of the k nearest rows per query, score descending, row ascending among equal scores;
         fewer than k rows left: the tail is (-inf, -1).  rescore = m > 1 (needs keep_f32): the best min(m * k, 128) rows of the bf16
         search are scored again from the f32 copies and the best k of those returned.  slices: the library slices of the kernel's
-        grid (default: coati_search_slices); the result does not depend on it."""
+        grid (default: coati_search_slices); the result does not depend on it.  bias: f32 [N], added to every row's score under the
+        metric (for l2: to the negated squared distance), e.g. a multiple of property_scores(head)[:, 0] for "near q and high property";
+        -inf entries exclude rows.  Not with rescore > 1."""
         k, rescore = int(k), int(rescore)
         if k < 1 or k > K_MAX:
             raise ValueError(f"EmbeddingIndex.search: k={k} outside 1 .. {K_MAX}")
@@ -182,7 +184,19 @@ class EmbeddingIndex:
         kk = min(rescore * k, K_MAX) if rescore > 1 else k
         if slices is not None and (int(slices) < 1 or int(slices) * kk > MERGE_MAX):
             raise ValueError(f"EmbeddingIndex.search: slices={slices} outside 1 .. {MERGE_MAX // kk} at k={kk}")
+        if bias is not None:
+            if rescore > 1:
+                raise ValueError("EmbeddingIndex.search: bias is not compatible with rescore > 1")
+            if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,):
+                raise ValueError(f"EmbeddingIndex.search: bias must be an f32 tensor [{self._n}]")
         q32, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
+        scores, rows = self._topk(q16, kk, slices, self._bias if bias is None else self.bias + bias.to(self.device))
+        if rescore > 1:
+            return self._rescore(q32, scores, rows, k)
+        return finish_scores(scores, self.metric, q16), rows
+
+    def _topk(self, q16, kk, slices, bias):
+        """the kernel on prepared queries: (alpha * dot + bias[row] [Q, kk], rows [Q, kk]); bias f32, at least N entries on the device"""
         Q = q16.shape[0]
         scores = torch.full((Q, kk), float("-inf"), dtype=torch.float32, device=self.device)
         rows = torch.full((Q, kk), -1, dtype=torch.int64, device=self.device)
@@ -198,12 +212,43 @@ class EmbeddingIndex:
                 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
                 for lo in range(0, Q, qc):
                     n = min(qc, Q - lo)
-                    _lib.call("coati_search_topk", _ptr(self._vec), self._n, self.dim_padded, _ptr(self._bias), _ptr(q16[lo:lo + n]), n, kk,
+                    _lib.call("coati_search_topk", _ptr(self._vec), self._n, self.dim_padded, _ptr(bias), _ptr(q16[lo:lo + n]), n, kk,
                               metric_alpha(self.metric), S, _ptr(self._scratch[0]), _ptr(self._scratch[1]), _ptr(scores[lo:lo + n]),
                               _ptr(rows[lo:lo + n]), stream)
-        if rescore > 1:
-            return self._rescore(q32, scores, rows, k)
-        return finish_scores(scores, self.metric, q16), rows
+        return scores, rows
+
+    def property_scores(self, head):
+        """[N, P] f32: head (coati_amd.models.regression.PropertyHead, on the index's device) on every stored row -- one fused kernel
+        over the bf16 rows, removed rows included.  A cosine index stores unit rows, so the head must be one of unit inputs
+        (unit_input=True), and only then."""
+        if head.input_dim != self.dim:
+            raise ValueError(f"EmbeddingIndex.property_scores: the head's input_dim={head.input_dim}, the index's dim={self.dim}")
+        if bool(head.unit_input) != (self.metric == "cosine"):
+            raise ValueError(f"EmbeddingIndex.property_scores: a head with unit_input={bool(head.unit_input)} on a {self.metric!r} index "
+                             "(cosine indices store unit rows, the others rows as given)")
+        return head.predict_rows(self.vectors)
+
+    def screen(self, head, k, output=0, largest=True):
+        """(scores [k] f32, rows [k] int64): the k best live rows by the head's output `output` -- the largest values first (the smallest
+        first for largest=False; the scores returned are the head's own values either way), row index ascending among equal values.
+        Removed rows are never returned; fewer than k live rows: the tail is (-inf, -1).  The selection is one call of the search
+        kernel, so 1 <= k <= 128: for larger selections sort property_scores(head) yourself."""
+        k, output = int(k), int(output)
+        if k < 1 or k > K_MAX:
+            raise ValueError(f"EmbeddingIndex.screen: k={k} outside 1 .. {K_MAX} (for more, sort property_scores)")
+        if output < 0 or output >= head.num_outputs:
+            raise ValueError(f"EmbeddingIndex.screen: output={output} outside 0 .. {head.num_outputs - 1}")
+        values = self.property_scores(head)[:, output]
+        if self._n == 0:
+            return (torch.full((k,), float("-inf"), dtype=torch.float32, device=self.device),
+                    torch.full((k,), -1, dtype=torch.int64, device=self.device))
+        live = self.bias > float("-inf")                     # (not `+ self.bias`: an l2 index keeps -|x|^2 there)
+        key = torch.where(live, values if largest else -values, torch.full_like(values, float("-inf"))).contiguous()
+        q16 = torch.zeros(1, self.dim_padded, dtype=torch.bfloat16, device=self.device)      # alpha * dot(0, row) + key[row]
+        _, rows = self._topk(q16, k, None, key)
+        rows = rows[0]
+        scores = torch.where(rows >= 0, values[rows.clamp_min(0)], torch.full((k,), float("-inf"), dtype=torch.float32, device=self.device))
+        return scores, rows
 
     def _rescore(self, q32, scores, rows, k):
         """the candidates' scores from the f32 copies (a gather and a bmm over [Q, m k, E]), re-sorted: score descending, row ascending"""
