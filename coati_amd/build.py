@@ -15,7 +15,8 @@ BEAM_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_beam.h")   #
 SEARCH_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_search.h")   # embedding-library search: a third one
 GRAMMAR_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_grammar.h")   # syntax-constrained decoding: a fourth
 SCREEN_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_screen.h")   # property heads on library rows: a fifth
-HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip"]
+GUIDE_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_guide.h")   # the head's input gradient: a sixth
+HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip", "guide.hip"]
 CPP_UNITS = ["engine.cpp", "capi.cpp", "tokenizer.cpp", "comm.cpp"]
 # -amdgpu-mfma-vgpr-form: MFMA results in VGPRs (gfx950 has one unified register file).  Where the compiler picked the AGPR form
 # (the attention forward kernels) 13 % of the instructions were v_accvgpr_read / write moves in a VALU-bound kernel
@@ -46,7 +47,7 @@ def _sources():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if not os.path.isdir(os.path.join(CSRC, f))]
     if EXPERIMENTAL:
         deps += [os.path.join(CSRC, "experimental", f) for f in os.listdir(os.path.join(CSRC, "experimental"))]
-    deps += [HEADER, BEAM_HEADER, SEARCH_HEADER, GRAMMAR_HEADER, SCREEN_HEADER]
+    deps += [HEADER, BEAM_HEADER, SEARCH_HEADER, GRAMMAR_HEADER, SCREEN_HEADER, GUIDE_HEADER]
     return deps
 
 

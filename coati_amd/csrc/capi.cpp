@@ -6,6 +6,7 @@
 #include "../../include/coati_search.h"
 #include "../../include/coati_grammar.h"
 #include "../../include/coati_screen.h"
+#include "../../include/coati_guide.h"
 #include <vector>
 #include "kernels.h"
 
@@ -287,6 +288,13 @@ int coati_grammar_step(float* logits, int64_t ldl, int B, int V, const uint64_t*
 int coati_head_eval(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
                     int D, const float* wl, const float* bl, int P, int F, float* out, int64_t ldo, void* stream) {
   return launch_head_eval(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, F, out, ldo, S_(stream));
+}
+
+// the head's input gradient (include/coati_guide.h)
+int coati_head_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
+                    int D, const float* wl, const float* bl, int P, int F, const uint16_t* w0t, const uint16_t* wrt, const float* cot,
+                    int64_t ldc, float* out, int64_t ldo, float* g, int64_t ldg, void* stream) {
+  return launch_head_grad(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, F, w0t, wrt, cot, ldc, out, ldo, g, ldg, S_(stream));
 }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,

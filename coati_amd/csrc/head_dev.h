@@ -1,0 +1,412 @@
+// The property head's device body, shared by head_eval_kernel (screen.hip) and head_grad_kernel (guide.hip): one text, two kernels.
+//
+// head_body<F, WAVES, NP, GRAD>, one workgroup per tile of WAVES * NP * 32 rows; a wave owns NP panels of 32 rows for the whole kernel:
+//  * every product is computed TRANSPOSED on v_mfma_f32_32x32x16_bf16: the weights are the M side (32 output features x 16 inputs, read
+//    from LDS), the rows of the library the N side.  The result map (column = lane & 31 = the lane's ROW of the library, register r =
+//    feature 8 (r >> 2) + 4 (lane >> 5) + (r & 3) of the 32-feature tile) then is, register for register, the B operand of the next
+//    product: registers 8 t .. 8 t + 7 of tile mt, rounded to bf16, are the lane's eight k values of k-step 2 mt + t -- in the order
+//    k = 8 (j >> 2) + 4 (lane >> 5) + (j & 3) instead of 8 (lane >> 5) + j.  A product does not care in which order k is summed as long
+//    as both operands agree, so the residual weights are staged with the two middle 4-element groups of every 16 swapped and are then
+//    read like any A operand (one ds_read_b128).  Nothing passes through LDS or the lanes between two layers;
+//  * the f32 residual stream h [F, rows] lives in registers (F / 32 * NP * 16 per lane), the bf16 operand of the layer in F / 16 * NP * 4
+//    more, a 32-feature tile's accumulators in NP * 16;
+//  * weights come through LDS in chunks of at most 32 KiB, two buffers, one barrier per chunk: the first layer by K (all F features x 64
+//    inputs: the x fragments of a chunk are loaded from memory just in time, the accumulators are the stream itself), a residual layer
+//    by M (16384 / F output features x all F inputs).  The next chunk travels global -> registers under the current chunk's MFMAs and
+//    registers -> LDS behind them.  Row strides of K + 8 elements keep every ds_read_b128 group on 16 different 16-byte slots;
+//  * the chunk count is the same for every thread, so no barrier is under a lane- or wave-dependent condition;
+//  * the last layer (P <= 8 outputs) is VALU work: a lane's dot over the features it holds, plus the other half-wave's;
+//  * rows >= N (ragged last tile) are read at row N - 1 and never written.
+//
+// GRAD = true goes on where the forward ends (include/coati_guide.h).  The forward leaves, next to `h += max(acc, 0)`, the tile's 16 sign
+// decisions as one 16-bit word per (layer, 32-feature tile, panel, thread) in LDS: the thread that writes a word is the one that reads it,
+// so the words need no barrier of their own.  After `out`, h is dead and d = cot . wl (VALU, like the last layer) takes its registers.  A
+// backward layer is the residual-layer loop once more: chunks of wrt[l] (wr[l] transposed, the same middle-group swap), the operand rb(m (.)
+// d) built from d and the layer's mask words, accumulators starting at zero, d += acc.  g = rb(d) . w0 runs as one more such layer over w0t
+// with E output features: its 32-feature tiles go straight to memory (a lane's registers 4 q .. 4 q + 3 are 4 consecutive floats of its row:
+// one 16-byte store).  The chunk sequence is C0 + 2 D MCH + ceil(E / MC), again the same for every thread.
+// No atomics, no workspace.
+#pragma once
+#include "kernels.h"
+
+#define HEAD_E_MAX 512
+#define HEAD_D_MAX 16
+#define HEAD_P_MAX 8
+#define HEAD_KC 64         // inputs per chunk of the first layer (the last chunk has 32 when E % 64 == 32)
+#define HEAD_CHUNK 16384   // elements per chunk of a residual layer
+#ifndef HEAD_WAVES_256
+#define HEAD_WAVES_256 4   // F = 256: 4 waves (one per SIMD) of one 32-row panel each; wider tiles spill
+#define HEAD_NP_256 1
+#endif
+
+// elements of one of the two weight buffers
+template <int F>
+constexpr int head_buf_elems() {
+  constexpr int MC = HEAD_CHUNK / F < F ? HEAD_CHUNK / F : F;
+  return F * (HEAD_KC + 8) > MC * (F + 8) ? F * (HEAD_KC + 8) : MC * (F + 8);
+}
+// bytes of dynamic LDS of the GRAD body: the two weight buffers, then D layers of mask words
+template <int F, int WAVES, int NP>
+constexpr size_t head_grad_lds_bytes(int D) {
+  return (size_t)4 * head_buf_elems<F>() + (size_t)D * (F / 32) * NP * (64 * WAVES) * 2;
+}
+
+template <int F, int WAVES, int NP, bool GRAD>
+__device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long long ldx, long long N, int E, const bf16_t* __restrict__ w0,
+                                          const float* __restrict__ b0, const bf16_t* __restrict__ wr, const float* __restrict__ br, int D,
+                                          const float* __restrict__ wl, const float* __restrict__ bl, int P, float* __restrict__ out,
+                                          long long ldo, const bf16_t* __restrict__ w0t, const bf16_t* __restrict__ wrt,
+                                          const float* __restrict__ cot, long long ldc, float* __restrict__ g, long long ldg) {
+  constexpr int NT = 64 * WAVES, MT = F / 32, KS = F / 16;
+  constexpr int MC = HEAD_CHUNK / F < F ? HEAD_CHUNK / F : F;   // output features per residual chunk: 64 (F = 256), 128, 64
+  constexpr int MCH = F / MC, TPC = MC / 32;                    // chunks per residual layer, 32-feature tiles per chunk
+  constexpr int LD0 = HEAD_KC + 8, LDR = F + 8;                 // LDS row strides (elements)
+  constexpr int BUF = head_buf_elems<F>();
+  constexpr int U0 = F * HEAD_KC / 16, UR = MC * F / 16;        // 32-byte units of a chunk
+  constexpr int UPT = ((U0 > UR ? U0 : UR) + NT - 1) / NT;
+  bf16_t* lds;                                                  // [2][BUF]
+  unsigned short* masks = nullptr;                              // GRAD: [D][MT][NP][NT]
+  if constexpr (GRAD) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char head_smem[];
+    lds = reinterpret_cast<bf16_t*>(head_smem);
+    masks = reinterpret_cast<unsigned short*>(head_smem + 4 * BUF);
+  } else {
+    __shared__ __attribute__((aligned(16))) bf16_t head_lds[2 * BUF];
+    lds = head_lds;
+  }
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hh = lane >> 5;
+  const int C0 = (E + HEAD_KC - 1) / HEAD_KC;
+  const int CT = GRAD ? C0 + 2 * D * MCH + (E + MC - 1) / MC : C0 + D * MCH;
+  const long long row0 = (long long)blockIdx.x * (WAVES * NP * 32) + wave * (NP * 32);
+
+  // chunk gc of the sequence: global -> st (stage_load), st -> lds[gc & 1] (stage_store)
+  uint4 st[UPT][2];
+  auto stage_load = [&](int gc, bool first) {
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+      const int u = tid + NT * i;
+      const bf16_t* src;
+      bool on;
+      if (first) {   // (a 16-column unit past E, in the last chunk of E % 64 == 32, is neither loaded nor read)
+        on = u < U0 && HEAD_KC * gc + 16 * (u & 3) < E;
+        src = w0 + (long long)(u >> 2) * E + HEAD_KC * gc + 16 * (u & 3);
+      } else if (!GRAD || gc - C0 < D * MCH) {
+        const int cc = gc - C0;
+        on = u < UR;
+        src = wr + ((long long)(cc / MCH) * F + (cc % MCH) * MC + u / KS) * F + 16 * (u % KS);
+      } else if (gc - C0 < 2 * D * MCH) {   // backward layer D - 1 - cc / MCH: the same chunks of the transposed weights
+        const int cc = gc - C0 - D * MCH;
+        on = u < UR;
+        src = wrt + ((long long)(D - 1 - cc / MCH) * F + (cc % MCH) * MC + u / KS) * F + 16 * (u % KS);
+      } else {                              // w0t [E, F]: MC of its rows, none past E
+        const int cc = gc - C0 - 2 * D * MCH;
+        on = u < UR && cc * MC + u / KS < E;
+        src = w0t + ((long long)cc * MC + u / KS) * F + 16 * (u % KS);
+      }
+      if (on) {
+        st[i][0] = reinterpret_cast<const uint4*>(src)[0];
+        st[i][1] = reinterpret_cast<const uint4*>(src)[1];
+      }
+    }
+  };
+  auto stage_store = [&](int gc, bool first) {
+    bf16_t* buf = lds + (gc & 1) * BUF;
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+      const int u = tid + NT * i;
+      const uint4 a = st[i][0], b = st[i][1];
+      if (first) {
+        if (u < U0 && HEAD_KC * gc + 16 * (u & 3) < E) {
+          uint4* d = reinterpret_cast<uint4*>(buf + (u >> 2) * LD0 + 16 * (u & 3));
+          d[0] = a;
+          d[1] = b;
+        }
+      } else if (u < UR) {   // groups of 4 elements (g0 g1 | g2 g3) -> (g0 g2 | g1 g3): the k order of the chained operand
+        uint4* d = reinterpret_cast<uint4*>(buf + (u / KS) * LDR + 16 * (u % KS));   // (rows of w0t past E: stale registers, never read)
+        d[0] = make_uint4(a.x, a.y, b.x, b.y);
+        d[1] = make_uint4(a.z, a.w, b.z, b.w);
+      }
+    }
+  };
+
+  // the lane's library rows: B[k = 16 s + 8 hh + j][column = n] of panel p
+  const bf16_t* xrow[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const long long row = min(row0 + 32 * p + n, N - 1);
+    xrow[p] = x + row * ldx + 8 * hh;
+  }
+  uint4 xn[NP][4];
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) xn[p][t] = make_uint4(0u, 0u, 0u, 0u);
+  auto x_load = [&](int c) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (HEAD_KC * c + 16 * t < E) xn[p][t] = *reinterpret_cast<const uint4*>(xrow[p] + HEAD_KC * c + 16 * t);
+  };
+
+  stage_load(0, true);
+  x_load(0);
+  stage_store(0, true);
+
+  // the stream: h[mt][p][r] = feature 32 mt + 8 (r >> 2) + 4 hh + (r & 3) of row 32 p + n
+  f32x16 h[MT][NP];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 bv = *reinterpret_cast<const float4*>(b0 + 32 * mt + 8 * q + 4 * hh);
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        h[mt][p][4 * q] = bv.x;
+        h[mt][p][4 * q + 1] = bv.y;
+        h[mt][p][4 * q + 2] = bv.z;
+        h[mt][p][4 * q + 3] = bv.w;
+      }
+    }
+  __syncthreads();
+
+  int gc = 0;
+  // first layer, by K
+  for (int c = 0; c < C0; ++c, ++gc) {
+    uint4 xc[NP][4];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) xc[p][t] = xn[p][t];
+    const bool whole = HEAD_KC * c + 32 < E;   // 64 inputs in this chunk, not 32
+    if (c + 1 < C0) {
+      stage_load(gc + 1, true);
+      x_load(c + 1);
+    } else if (gc + 1 < CT) {
+      stage_load(gc + 1, false);
+    }
+    const bf16_t* a = lds + (gc & 1) * BUF + n * LD0 + 8 * hh;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (t < 2 || whole) {
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(a + 32 * mt * LD0 + 16 * t);
+#pragma unroll
+          for (int p = 0; p < NP; ++p)
+            h[mt][p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(bf16x8, xc[p][t]), h[mt][p], 0, 0, 0);
+        }
+      }
+    if (c + 1 < C0)
+      stage_store(gc + 1, true);
+    else if (gc + 1 < CT)
+      stage_store(gc + 1, false);
+    __syncthreads();
+  }
+
+  // residual layers, by M
+  for (int l = 0; l < D; ++l) {
+    bf16x8 bfr[NP][KS];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          uint4 v;
+          v.x = pack2bf(h[mt][p][8 * t], h[mt][p][8 * t + 1]);
+          v.y = pack2bf(h[mt][p][8 * t + 2], h[mt][p][8 * t + 3]);
+          v.z = pack2bf(h[mt][p][8 * t + 4], h[mt][p][8 * t + 5]);
+          v.w = pack2bf(h[mt][p][8 * t + 6], h[mt][p][8 * t + 7]);
+          bfr[p][2 * mt + t] = __builtin_bit_cast(bf16x8, v);
+        }
+    const float* bb = br + (long long)l * F + 4 * hh;
+#pragma unroll
+    for (int i = 0; i < MCH; ++i, ++gc) {
+      if (gc + 1 < CT) stage_load(gc + 1, false);
+      const bf16_t* a = lds + (gc & 1) * BUF + n * LDR + 8 * hh;
+#pragma unroll
+      for (int tt = 0; tt < TPC; ++tt) {
+        const int mt = i * TPC + tt;
+        f32x16 acc[NP];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 bv = *reinterpret_cast<const float4*>(bb + 32 * mt + 8 * q);
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            acc[p][4 * q] = bv.x;
+            acc[p][4 * q + 1] = bv.y;
+            acc[p][4 * q + 2] = bv.z;
+            acc[p][4 * q + 3] = bv.w;
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(a + 32 * tt * LDR + 16 * s);
+#pragma unroll
+          for (int p = 0; p < NP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[p][s], acc[p], 0, 0, 0);
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) h[mt][p][r] += fmaxf(acc[p][r], 0.f);
+          if constexpr (GRAD) {   // the tile's ReLU decisions, bit r = register r
+            unsigned m = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) m |= (acc[p][r] > 0.f ? 1u : 0u) << r;
+            masks[(((long long)l * MT + mt) * NP + p) * NT + tid] = (unsigned short)m;
+          }
+        }
+      }
+      if (gc + 1 < CT) stage_store(gc + 1, false);
+      __syncthreads();
+    }
+  }
+
+  // last layer: the lane's features of its rows against wl, then the other half-wave's
+  for (int o = 0; o < P; ++o) {
+    float sum[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) sum[p] = 0.f;
+    const float* wo = wl + (long long)o * F + 4 * hh;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 wv = *reinterpret_cast<const float4*>(wo + 32 * mt + 8 * q);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          sum[p] = fmaf(wv.x, h[mt][p][4 * q], sum[p]);
+          sum[p] = fmaf(wv.y, h[mt][p][4 * q + 1], sum[p]);
+          sum[p] = fmaf(wv.z, h[mt][p][4 * q + 2], sum[p]);
+          sum[p] = fmaf(wv.w, h[mt][p][4 * q + 3], sum[p]);
+        }
+      }
+    const float bo = bl[o];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const float tot = half_xchg_sum(sum[p]) + bo;
+      const long long row = row0 + 32 * p + n;
+      if (hh == 0 && row < N) out[row * ldo + o] = tot;
+    }
+  }
+
+  if constexpr (GRAD) {
+    // d = cot . wl in the registers of h, the same map
+    const float* crow[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) crow[p] = cot + min(row0 + 32 * p + n, N - 1) * ldc;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h[mt][p][r] = 0.f;
+    for (int o = 0; o < P; ++o) {
+      float c[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) c[p] = crow[p][o];
+      const float* wo = wl + (long long)o * F + 4 * hh;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 wv = *reinterpret_cast<const float4*>(wo + 32 * mt + 8 * q);
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            h[mt][p][4 * q] = fmaf(c[p], wv.x, h[mt][p][4 * q]);
+            h[mt][p][4 * q + 1] = fmaf(c[p], wv.y, h[mt][p][4 * q + 1]);
+            h[mt][p][4 * q + 2] = fmaf(c[p], wv.z, h[mt][p][4 * q + 2]);
+            h[mt][p][4 * q + 3] = fmaf(c[p], wv.w, h[mt][p][4 * q + 3]);
+          }
+        }
+    }
+
+    // backward layers D - 1 .. 0 (masked operand, d += acc), then rb(d) . w0 as one more layer whose tiles go to memory
+    for (int b = 0; b <= D; ++b) {
+      const bool lastp = b == D;
+      const int l = D - 1 - b;
+      bf16x8 bfr[NP][KS];
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          const unsigned m = lastp ? 0xffffu : (unsigned)masks[(((long long)l * MT + mt) * NP + p) * NT + tid];
+          float dm[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dm[r] = (m >> r) & 1u ? h[mt][p][r] : 0.f;
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            uint4 v;
+            v.x = pack2bf(dm[8 * t], dm[8 * t + 1]);
+            v.y = pack2bf(dm[8 * t + 2], dm[8 * t + 3]);
+            v.z = pack2bf(dm[8 * t + 4], dm[8 * t + 5]);
+            v.w = pack2bf(dm[8 * t + 6], dm[8 * t + 7]);
+            bfr[p][2 * mt + t] = __builtin_bit_cast(bf16x8, v);
+          }
+        }
+      if (!lastp) {
+#pragma unroll
+        for (int i = 0; i < MCH; ++i, ++gc) {
+          if (gc + 1 < CT) stage_load(gc + 1, false);
+          const bf16_t* a = lds + (gc & 1) * BUF + n * LDR + 8 * hh;
+#pragma unroll
+          for (int tt = 0; tt < TPC; ++tt) {
+            const int mt = i * TPC + tt;
+            f32x16 acc[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+              const bf16x8 af = *reinterpret_cast<const bf16x8*>(a + 32 * tt * LDR + 16 * s);
+#pragma unroll
+              for (int p = 0; p < NP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[p][s], acc[p], 0, 0, 0);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) h[mt][p][r] += acc[p][r];
+          }
+          if (gc + 1 < CT) stage_store(gc + 1, false);
+          __syncthreads();
+        }
+      } else {
+        for (int e0 = 0; e0 < E; e0 += MC, ++gc) {
+          if (gc + 1 < CT) stage_load(gc + 1, false);
+          const bf16_t* a = lds + (gc & 1) * BUF + n * LDR + 8 * hh;
+#pragma unroll
+          for (int tt = 0; tt < TPC; ++tt) {
+            if (e0 + 32 * tt < E) {   // (the same for every thread)
+              f32x16 acc[NP];
+#pragma unroll
+              for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+#pragma unroll
+              for (int s = 0; s < KS; ++s) {
+                const bf16x8 af = *reinterpret_cast<const bf16x8*>(a + 32 * tt * LDR + 16 * s);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[p][s], acc[p], 0, 0, 0);
+              }
+#pragma unroll
+              for (int p = 0; p < NP; ++p) {
+                const long long row = row0 + 32 * p + n;
+                if (row < N) {
+                  float* gr = g + row * ldg + e0 + 32 * tt + 4 * hh;
+#pragma unroll
+                  for (int q = 0; q < 4; ++q)
+                    *reinterpret_cast<float4*>(gr + 8 * q) = make_float4(acc[p][4 * q], acc[p][4 * q + 1], acc[p][4 * q + 2], acc[p][4 * q + 3]);
+                }
+              }
+            }
+          }
+          if (gc + 1 < CT) stage_store(gc + 1, false);
+          __syncthreads();
+        }
+      }
+    }
+  }
+}

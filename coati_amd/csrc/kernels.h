@@ -369,6 +369,11 @@ int launch_grammar_step(float* logits, long long ldl, int B, int V, const unsign
 // property heads (screen.hip, include/coati_screen.h): out [N, P] = the FC-ResNet head (w0, b0 | wr, br x D | wl, bl) on the bf16 rows x [N, E]
 int launch_head_eval(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
                      int D, const float* wl, const float* bl, int P, int F, float* out, long long ldo, hipStream_t s);
+// the head's input gradient (guide.hip, include/coati_guide.h): out as launch_head_eval writes it, g [N, E] = d (cot . out) / dx; w0t [E, F] and
+// wrt [D, F, F] are w0 and wr[l] transposed
+int launch_head_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
+                     int D, const float* wl, const float* bl, int P, int F, const bf16_t* w0t, const bf16_t* wrt, const float* cot,
+                     long long ldc, float* out, long long ldo, float* g, long long ldg, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,
