@@ -38,6 +38,11 @@ try:
         _GUIDE_ABI = _abi.parse(_f.read(), guard="COATI_GUIDE_H", name="coati_guide.h", base=_ABI)
 except OSError as e:
     raise RuntimeError(f"coati_amd: cannot read {_build.GUIDE_HEADER}, which the head-gradient binding is derived from: {e}") from e
+try:
+    with open(_build.LN_XHAT_HEADER) as _f:
+        _LN_XHAT_ABI = _abi.parse(_f.read(), guard="COATI_LN_XHAT_H", name="coati_ln_xhat.h", base=_ABI)
+except OSError as e:
+    raise RuntimeError(f"coati_amd: cannot read {_build.LN_XHAT_HEADER}, which the saved-xhat binding is derived from: {e}") from e
 
 PROTOTYPES = _ABI.prototypes        # name -> (restype, argtypes), the operators of csrc/experimental/ included
 CoatiConfig = _ABI.CoatiConfig
@@ -47,6 +52,7 @@ SEARCH_PROTOTYPES = _SEARCH_ABI.prototypes   # the entries of include/coati_sear
 GRAMMAR_PROTOTYPES = _GRAMMAR_ABI.prototypes   # the entry of include/coati_grammar.h, likewise
 SCREEN_PROTOTYPES = _SCREEN_ABI.prototypes   # the entry of include/coati_screen.h, likewise
 GUIDE_PROTOTYPES = _GUIDE_ABI.prototypes   # the entry of include/coati_guide.h, likewise
+LN_XHAT_PROTOTYPES = _LN_XHAT_ABI.prototypes   # the entries of include/coati_ln_xhat.h, likewise
 
 _lib = None
 
@@ -75,14 +81,14 @@ def lib():
     import torch  # noqa: F401
     l = ctypes.CDLL(path)
     # operators of csrc/experimental/ are only in libcoati_hip_x.so (COATI_AMD_EXPERIMENTAL=1, build.py): bound when the loaded library has them
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BEAM_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items()) + list(GRAMMAR_PROTOTYPES.items()) + list(SCREEN_PROTOTYPES.items()) + list(GUIDE_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BEAM_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items()) + list(GRAMMAR_PROTOTYPES.items()) + list(SCREEN_PROTOTYPES.items()) + list(GUIDE_PROTOTYPES.items()) + list(LN_XHAT_PROTOTYPES.items()):
         if hasattr(l, name):
             getattr(l, name).restype = restype
             getattr(l, name).argtypes = argtypes
     if l.coati_abi_version() != ABI_VERSION:
         raise RuntimeError(f"coati_amd: {path} has ABI version {l.coati_abi_version()}, this package expects {ABI_VERSION}; "
                            "rebuild with `python -m coati_amd.build --force`")
-    missing = [n for n in exported_symbols() + sorted(BEAM_PROTOTYPES) + sorted(SEARCH_PROTOTYPES) + sorted(GRAMMAR_PROTOTYPES) + sorted(SCREEN_PROTOTYPES) + sorted(GUIDE_PROTOTYPES) if not hasattr(l, n)]
+    missing = [n for n in exported_symbols() + sorted(BEAM_PROTOTYPES) + sorted(SEARCH_PROTOTYPES) + sorted(GRAMMAR_PROTOTYPES) + sorted(SCREEN_PROTOTYPES) + sorted(GUIDE_PROTOTYPES) + sorted(LN_XHAT_PROTOTYPES) if not hasattr(l, n)]
     if missing:
         raise RuntimeError(f"coati_amd: {path} lacks symbols {missing[:6]}; rebuild with `python -m coati_amd.build --force`")
     _lib = l

@@ -7,6 +7,7 @@
 #include "../../include/coati_grammar.h"
 #include "../../include/coati_screen.h"
 #include "../../include/coati_guide.h"
+#include "../../include/coati_ln_xhat.h"
 #include <vector>
 #include "kernels.h"
 
@@ -51,6 +52,35 @@ int coati_gemm_lnbwd(const uint16_t* dY, int64_t lda, const uint16_t* WT, int64_
   COATI_CHECK_SHAPE(gemm_ring_lnbwd_supported(a, &nwg), "gemm_lnbwd: unsupported shape M=%d K=%d (256 columns, 40 961 .. 57 344 rows, K %% 64 == 0)", M, K);
   *n_partial_rows = nwg;
   return launch_gemm_nt(a, 0, EPI_LNBWD, S_(stream));
+}
+
+int coati_gemm_lnbwd_xhat(const uint16_t* dY, int64_t lda, const uint16_t* WT, int64_t ldw, int M, int K, const uint16_t* xhat, const float* rstd,
+                          const float* gamma, const float* dres, float* dx, uint16_t* dx16, float* partial, int32_t* n_partial_rows,
+                          const uint16_t* chain_W, uint16_t* chain_C, void* stream) {
+  COATI_CHECK_ARG(dY && WT && xhat && rstd && gamma && dres && dx && partial && n_partial_rows, "gemm_lnbwd_xhat: null argument");
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = dY; a.lda = lda; a.B = WT; a.ldb = ldw; a.M = M; a.N = 256; a.K = K; a.C = dx; a.ldc = 256; a.aux_in = dres; a.ld_aux = 256;
+  a.aux_out = dx16; a.lnb_xhat = xhat; a.lnb_rstd = rstd; a.lnb_gamma = gamma; a.lnb_partial = partial;
+  COATI_CHECK_ARG((chain_W == nullptr) == (chain_C == nullptr) && (chain_W == nullptr || dx16 != nullptr), "gemm_lnbwd_xhat: the chained product needs chain_W, chain_C and dx16");
+  a.chain_W = chain_W; a.chain_ldw = 256; a.chain_C = chain_C; a.chain_ldc = 256;
+  int nwg = 0;
+  COATI_CHECK_SHAPE(gemm_ring_lnbwd_supported(a, &nwg), "gemm_lnbwd_xhat: unsupported shape M=%d K=%d (256 columns, 40 961 .. 57 344 rows, K %% 64 == 0)", M, K);
+  *n_partial_rows = nwg;
+  return launch_gemm_nt(a, 0, EPI_LNBWD, S_(stream));
+}
+
+int coati_gemm_ln_gelu_grad(const float* x, int64_t ldx, const float* gamma, const float* beta, const uint16_t* W, int64_t ldw, const float* bias,
+                            int M, int N, uint16_t* saved, float* mean, float* rstd, uint16_t* g, uint8_t* codes, int save_xhat, void* stream) {
+  COATI_CHECK_ARG(x && gamma && beta && W && saved && mean && rstd && g && codes, "gemm_ln_gelu_grad: null argument");
+  COATI_CHECK_SHAPE(M > 0 && N > 0 && N % 16 == 0 && ldx >= 256 && ldx % 4 == 0 && ldw >= 256 && ldw % 8 == 0, "gemm_ln_gelu_grad: shape / alignment (M=%d N=%d ldx=%lld ldw=%lld)", M, N, (long long)ldx, (long long)ldw);
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = saved; a.lda = 256; a.B = W; a.ldb = ldw; a.M = M; a.N = N; a.K = 256; a.C = g; a.ldc = N; a.bias = bias; a.aux_out = codes; a.ld_aux = N;
+  a.ln_x = x; a.ln_ldx = ldx; a.ln_gamma = gamma; a.ln_beta = beta; a.ln_mean = mean; a.ln_rstd = rstd; a.ln_save_xhat = save_xhat ? 1 : 0;
+  // (both save forms on the same kernel: the 16-row-slab one, the only one that has both)
+  COATI_CHECK_SHAPE(gemm_rb16_supported(a, 0, EPI_GELU_GRAD), "gemm_ln_gelu_grad: the LayerNorm-fused 16-row-slab kernel takes 36 865 .. 65 536 rows (M=%d N=%d)", M, N);
+  return launch_gemm_rb16(a, EPI_GELU_GRAD, S_(stream));
 }
 
 int coati_quant_mx8(const void* x, int x_f32, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* scales, int M, int K, void* stream) {
@@ -106,11 +136,20 @@ int64_t coati_wgrad_grouped_workspace_bytes(int n_problems, const int* N, const 
 int coati_wgrad_grouped(int n_problems, const uint16_t* const* A, const int64_t* lda, const uint16_t* const* B, const int64_t* ldb,
                         int M, const int* N, const int* K, float* const* dW, const int64_t* ldw, float* const* dbias, int tile_size,
                         void* workspace, int64_t workspace_bytes, void* stream) {
+  return coati_wgrad_grouped_affine(n_problems, A, lda, B, ldb, M, N, K, dW, ldw, dbias, nullptr, nullptr, tile_size, workspace, workspace_bytes, stream);
+}
+
+int coati_wgrad_grouped_affine(int n_problems, const uint16_t* const* A, const int64_t* lda, const uint16_t* const* B, const int64_t* ldb,
+                               int M, const int* N, const int* K, float* const* dW, const int64_t* ldw, float* const* dbias,
+                               const float* const* b_gamma, const float* const* b_beta, int tile_size, void* workspace, int64_t workspace_bytes,
+                               void* stream) {
   COATI_CHECK_ARG(n_problems > 0 && A && lda && B && ldb && N && K && dW && ldw && dbias && workspace, "wgrad_grouped: null argument");
+  COATI_CHECK_ARG((b_gamma == nullptr) == (b_beta == nullptr), "wgrad_grouped: b_gamma and b_beta come together");
   std::vector<WgradTile> tab;
   for (int i = 0; i < n_problems; ++i) {
     WgradArgs a;
     a.A = A[i]; a.lda = lda[i]; a.B = B[i]; a.ldb = ldb[i]; a.M = M; a.N = N[i]; a.K = K[i]; a.dW = dW[i]; a.ldw = ldw[i]; a.dbias = dbias[i]; a.n_out = 0;
+    if (b_gamma != nullptr) { a.b_gamma = b_gamma[i]; a.b_beta = b_beta[i]; }
     COATI_TRY(wgrad_table_append(tab, a, tile_size));
   }
   COATI_CHECK_ARG((int64_t)(tab.size() * sizeof(WgradTile)) <= workspace_bytes, "wgrad_grouped: workspace too small (%zu tiles)", tab.size());

@@ -20,6 +20,7 @@
 
 #include "../../include/coati_hip.h"
 #include "../../include/coati_beam.h"
+#include "../../include/coati_ln_xhat.h"
 #include "kernels.h"
 
 // a HIP runtime call inside a function that returns a COATI_* code (beside COATI_TRY / COATI_CHECK_* of common.h)
@@ -89,6 +90,9 @@ struct XPass {  // saved activations of one transformer pass
   std::vector<float*> xmid;   // L
   std::vector<float*> mean1, rstd1, mean2, rstd2, lse;
   std::vector<bf16_t*> a1, qkv, y, a2, g;
+  // what the LayerNorm-fused launches of the LAST forward left in a1 / a2: false = the Linear's input a = xhat gamma + beta, true = xhat itself
+  // (xformer_fwd decides per pass and step, xhat_saved_by_fwd; every reader of a1 / a2 honours it or returns an error)
+  bool ln_xhat = false;
   std::vector<unsigned char*> hpre;   // NewGELU'(pre-activation) as 8-bit fixed point (common.h packq8)
   float *meanf, *rstdf, *xf32;
   float *x_emb = nullptr, *mean0 = nullptr, *rstd0 = nullptr;   // norm_embed: the raw embedding rows and their LayerNorm statistics
@@ -600,7 +604,10 @@ static void advance_rows(GemmArgs& a, long long r0, int epi, int lnb_partial_row
   if (a.partial) a.partial += r0 * cdiv(a.N, a.partial_tile > 0 ? a.partial_tile : 128);
   if (a.rope_row_t) a.rope_row_t += r0;
   if (a.ln_x) { a.ln_x += r0 * a.ln_ldx; a.ln_mean += r0; a.ln_rstd += r0; }
-  if (a.lnb_x) { a.lnb_x += r0 * a.lnb_ldx; a.lnb_mean += r0; a.lnb_rstd += r0; }
+  if (a.lnb_x) a.lnb_x += r0 * a.lnb_ldx;
+  if (a.lnb_xhat) a.lnb_xhat += r0 * a.ldc;
+  if (a.lnb_mean) a.lnb_mean += r0;
+  if (a.lnb_rstd) a.lnb_rstd += r0;
   if (a.lnb_partial) a.lnb_partial += (long long)lnb_partial_rows_done * 2 * a.N;
   if (a.chain_C) a.chain_C += r0 * a.chain_ldc;
 }
@@ -640,6 +647,44 @@ static bool lnbwd_rows_supported(const GemmArgs& a, int* nwg) {
     total += k;
   }
   if (nwg) *nwg = total;
+  return true;
+}
+
+// Whether the LayerNorm-fused Linears (c_attn behind ln_1, c_fc behind ln_2) of a pass of M rows save xhat in a1 / a2 instead of the Linear's
+// input a = xhat gamma + beta (GemmArgs::ln_save_xhat): the LayerNorm backward then reads 2 bytes per element instead of 4 of f32 x, the grouped
+// weight gradient applies gamma / beta to its finished tiles.  THE one place that decides; xformer_fwd records the answer in XPass::ln_xhat.
+// All of: the bf16 path; both products on the LayerNorm-fused 16-row-slab kernel, every launch of a row-split plan included (launch_gemm_nt
+// refuses ln_save_xhat anywhere else); the weight gradients grouped on 256-wide tiles with K = 256; both LayerNorm backwards in the write-out
+// of their input-gradient products (dgrad_lnbwd's own conditions: COATI_NO_LNBWD_FUSE=1 therefore restores a).
+static bool xhat_saved_by_fwd(const coati_engine* e, int M, int T, bool packed, bool attn_block) {
+  const coati_config& c = e->cfg;
+  const int C = c.n_hidden_xformer, L = c.n_layer_xformer;
+  if (c.use_fp8 || attn_block || C != 256) return false;
+  if (!(e->wg_group && M >= 4096 && e->wg_tile == 256)) return false;   // (xformer_bwd's grp)
+  if (2 * L + 1 > COATI_LN_MAX_SLOTS) return false;                      // (xformer_bwd's defer)
+  const float* const some = e->P;   // shapes decide, not addresses: any non-null pointer stands for an operand that is there
+  for (int which = 0; which < 2; ++which) {
+    const int epi = which == 0 ? EPI_QKV_ROPE : EPI_GELU_GRAD, N = which == 0 ? 3 * C : 4 * C;
+    GemmArgs f;
+    memset(&f, 0, sizeof(f));
+    f.M = M; f.N = N; f.K = C; f.lda = C; f.ldb = C; f.ldc = N; f.ld_aux = N; f.bias = some; f.ln_x = some;
+    if (which == 0) { f.rope_T = T; f.rope_C = C; f.rope_hs = C / c.n_head; f.rope_row_t = packed ? reinterpret_cast<const int*>(some) : nullptr; }
+    if (!gemm_rb256_ln_fusable(f, epi)) return false;
+    const int rows = row_split_plan(f, 0, epi), step = rows > 0 ? rows : M;
+    for (long long r0 = 0; r0 < M; r0 += step) {
+      GemmArgs b = f;
+      b.M = (int)std::min<long long>(step, M - r0);
+#ifdef COATI_EXPERIMENTAL
+      if (gemm_t32_supported(b, 0, epi)) return false;
+#endif
+      if (!gemm_rb16_supported(b, 0, epi)) return false;
+    }
+    GemmArgs d;
+    memset(&d, 0, sizeof(d));
+    d.M = M; d.N = C; d.K = N; d.lda = N; d.ldb = N; d.ldc = C;
+    int nwg = 0;
+    if (!lnbwd_rows_supported(d, &nwg) || nwg > COATI_LN_PARTIAL_ROWS) return false;
+  }
   return true;
 }
 
@@ -884,6 +929,7 @@ int xformer_fwd(coati_engine* e, XPass& p, const float* injection, hipStream_t s
 #else
   constexpr bool ab = false;
 #endif
+  p.ln_xhat = xhat_saved_by_fwd(e, M, p.T, p.packed, ab);
   for (int l = 0; l < L; ++l) {
     const XLayerP& w = e->xl[l];
 #ifdef COATI_EXPERIMENTAL
@@ -941,7 +987,9 @@ int xformer_fwd(coati_engine* e, XPass& p, const float* injection, hipStream_t s
       const bool fuse = gemm_rb256_ln_fusable(a, EPI_QKV_ROPE);
       if (fuse) {
         a.ln_x = p.x[l]; a.ln_ldx = C; a.ln_gamma = e->P + w.ln1w; a.ln_beta = e->P + w.ln1b; a.ln_mean = p.mean1[l]; a.ln_rstd = p.rstd1[l];
+        a.ln_save_xhat = p.ln_xhat;
       } else {
+        COATI_CHECK_ARG(!p.ln_xhat, "xformer_fwd: the pass saves xhat, ln_1 of layer %d does not run fused", l);
         ProfScope ps(e, SITE_LN_FWD, 0, s, (double)M * C * 6 + (double)M * 8);
         COATI_TRY(launch_layernorm_fwd(p.x[l], C, e->P + w.ln1w, e->P + w.ln1b, p.a1[l], C, nullptr, 0, p.mean1[l], p.rstd1[l], M, C, s));
       }
@@ -979,7 +1027,9 @@ int xformer_fwd(coati_engine* e, XPass& p, const float* injection, hipStream_t s
       const bool fuse = gemm_rb256_ln_fusable(a, EPI_GELU_GRAD);
       if (fuse) {
         a.ln_x = p.xmid[l]; a.ln_ldx = C; a.ln_gamma = e->P + w.ln2w; a.ln_beta = e->P + w.ln2b; a.ln_mean = p.mean2[l]; a.ln_rstd = p.rstd2[l];
+        a.ln_save_xhat = p.ln_xhat;
       } else {
+        COATI_CHECK_ARG(!p.ln_xhat, "xformer_fwd: the pass saves xhat, ln_2 of layer %d does not run fused", l);
         ProfScope ps(e, SITE_LN_FWD, 0, s, (double)M * C * 6 + (double)M * 8);
         COATI_TRY(launch_layernorm_fwd(p.xmid[l], C, e->P + w.ln2w, e->P + w.ln2b, p.a2[l], C, nullptr, 0, p.mean2[l], p.rstd2[l], M, C, s));
       }
@@ -1031,6 +1081,8 @@ int xformer_wgrad_group(coati_engine* e, XPass& p, int l_lo, int l_hi, hipStream
   // launch really streams (fewer with packed rows, different every batch) are a kernel argument
   const int C = e->cfg.n_hidden_xformer, M = p.M, Mtab = p.Mcap;
   const long long sig = e->carve_sig * 2 + (p.tail ? 1 : 0);      // the capacity layout: a batch with another T / row count reuses the table
+  const bool affine_ok = e->wg_tile == 256 && C == 256;   // (wgrad_table_append: 256-wide tiles, K = 256)
+  COATI_CHECK_ARG(!p.ln_xhat || affine_ok, "wgrad group: a1 / a2 hold xhat and the %d-wide tiles cannot apply gamma / beta (C=%d)", e->wg_tile, C);
   int slot = -1;
   for (int i = 0; i < 4; ++i)
     if (e->wtab_key[i].pass == &p && e->wtab_key[i].lo == l_lo && e->wtab_key[i].hi == l_hi && e->wtab_key[i].M == Mtab && e->wtab_key[i].sig == sig) slot = i;
@@ -1041,17 +1093,21 @@ int xformer_wgrad_group(coati_engine* e, XPass& p, int l_lo, int l_hi, hipStream
   }
   if (slot < 0) {
     std::vector<WgradTile> tab;
-    auto add = [&](const bf16_t* A, int lda, const bf16_t* B, int ldb, int N, int K, int64_t w_off, int64_t b_off) -> int {
+    // ln_g / ln_b >= 0: B is a1 / a2, the rows a LayerNorm-fused forward saved -- as the Linear's input or as xhat, which differs from batch
+    // to batch (XPass::ln_xhat) while this table is cached: the entry carries gamma / beta wherever the kernel can apply them and the LAUNCH says
+    // whether it does
+    auto add = [&](const bf16_t* A, int lda, const bf16_t* B, int ldb, int N, int K, int64_t w_off, int64_t b_off, int64_t ln_g = -1, int64_t ln_b = -1) -> int {
       WgradArgs a;
       a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.M = Mtab; a.N = N; a.K = K; a.dW = e->G + w_off; a.ldw = K; a.dbias = e->G + b_off; a.n_out = 0;
+      if (ln_g >= 0 && affine_ok) { a.b_gamma = e->P + ln_g; a.b_beta = e->P + ln_b; }
       return wgrad_table_append(tab, a, e->wg_tile);
     };
     for (int l = l_hi - 1; l >= l_lo; --l) {
       const XLayerP& w = e->xl[l];
-      COATI_TRY(add(e->w_dqkv[l], 3 * C, p.a1[l], C, 3 * C, C, w.attnw, w.attnb));
+      COATI_TRY(add(e->w_dqkv[l], 3 * C, p.a1[l], C, 3 * C, C, w.attnw, w.attnb, w.ln1w, w.ln1b));
       COATI_TRY(add(e->w_dxb[l], C, p.y[l], C, C, C, w.projw, w.projb));
       if (p.tail && l == e->cfg.n_layer_xformer - 1) continue;   // the tail layer's MLP ran on the [STOP] rows only: its two gradients are small launches in xformer_bwd
-      COATI_TRY(add(e->w_dh4[l], 4 * C, p.a2[l], C, 4 * C, C, w.fc1w, w.fc1b));
+      COATI_TRY(add(e->w_dh4[l], 4 * C, p.a2[l], C, 4 * C, C, w.fc1w, w.fc1b, w.ln2w, w.ln2b));
       COATI_TRY(add(e->w_dxa[l], C, p.g[l], 4 * C, C, 4 * C, w.fc2w, w.fc2b));
     }
     COATI_CHECK_ARG((int)tab.size() <= e->wtab_cap, "wgrad group: table overflow (%zu > %d)", tab.size(), e->wtab_cap);
@@ -1062,7 +1118,7 @@ int xformer_wgrad_group(coati_engine* e, XPass& p, int l_lo, int l_hi, hipStream
     e->wtab_key[slot] = k;
   }
   ProfScope ps(e, SITE_XF_WGRAD, flops, s, bytes);
-  return launch_wgrad_table(e->d_wtab + (size_t)slot * e->wtab_cap, e->wtab_key[slot].n, s, e->wg_tile, M);
+  return launch_wgrad_table(e->d_wtab + (size_t)slot * e->wtab_cap, e->wtab_key[slot].n, s, e->wg_tile, M, p.ln_xhat ? 1 : 0);
 }
 
 // dyf: gradient w.r.t. ln_f output, bf16 (decoder pass) or f32 (encoder pass)
@@ -1097,14 +1153,17 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
   // Returns 1 when the fused launch ran, 0 when the shape does not take it (the caller then runs the two launches), < 0 on error.
   // chainW / chainC: the product that consumes the LayerNorm backward's bf16 output (c_proj's input gradient behind ln_2) in the
   // same launch
-  auto dgrad_lnbwd = [&](int site, const bf16_t* dY, int K, const bf16_t* WT, const float* x, const float* mean, const float* rstd,
+  // xhat: the bf16 normalised rows where the forward saved them (XPass::ln_xhat), read instead of x and mean; null: x, mean, rstd
+  auto dgrad_lnbwd = [&](int site, const bf16_t* dY, int K, const bf16_t* WT, const float* x, const bf16_t* xhat, const float* mean, const float* rstd,
                          const float* gamma, size_t goff, size_t boff, bf16_t* dx16, const bf16_t* chainW = nullptr,
                          bf16_t* chainC = nullptr, bool has_dres = true) -> int {
     if (!defer || c.use_fp8) return 0;
     GemmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = dY; a.lda = K; a.B = WT; a.ldb = K; a.M = M; a.N = C; a.K = K; a.C = DX; a.ldc = C; a.aux_in = has_dres ? DX : nullptr; a.ld_aux = C; a.aux_out = dx16;
-    a.lnb_x = x; a.lnb_ldx = C; a.lnb_mean = mean; a.lnb_rstd = rstd; a.lnb_gamma = gamma;
+    a.lnb_rstd = rstd; a.lnb_gamma = gamma;
+    if (xhat != nullptr) a.lnb_xhat = xhat;
+    else { a.lnb_x = x; a.lnb_ldx = C; a.lnb_mean = mean; }
     if (chainW != nullptr && dx16 != nullptr) { a.chain_W = chainW; a.chain_ldw = C; a.chain_C = chainC; a.chain_ldc = C; }
     int nwg = 0;
     if (!lnbwd_rows_supported(a, &nwg) || nwg > COATI_LN_PARTIAL_ROWS) return 0;
@@ -1113,9 +1172,9 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
     fin.db_off[fin.n] = (long long)boff;
     fin.nblk[fin.n] = nwg;
     ++fin.n;
-    // algorithmic bytes: dY + weight in; x, dres in; dx (f32) + its bf16 copy out
+    // algorithmic bytes: dY + weight in; x (f32) or xhat (bf16), dres in; dx (f32) + its bf16 copy out
     ProfScope ps(e, site, 2.0 * M * C * K + (a.chain_W ? 2.0 * M * C * C : 0.0), s,
-                 (double)M * K * 2 + (double)C * K * 2 + (double)M * C * (4 + (has_dres ? 4 : 0) + 4 + (dx16 ? 2 : 0)) + (a.chain_W ? (double)M * C * 2 + (double)C * C * 2 : 0.0));
+                 (double)M * K * 2 + (double)C * K * 2 + (double)M * C * ((xhat ? 2 : 4) + (has_dres ? 4 : 0) + 4 + (dx16 ? 2 : 0)) + (a.chain_W ? (double)M * C * 2 + (double)C * C * 2 : 0.0));
     const int rc = gemm_rows(a, 0, EPI_LNBWD, s);
     return rc == COATI_OK ? 1 : rc;
   };
@@ -1123,6 +1182,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
   // this call (grouped = every activation gradient of the layer range stays alive in its own buffer).
   const bool grp = e->wg_group && M >= 4096 && !inputs_only;
   const bool wg_each = !grp && !inputs_only;   // one weight-gradient launch per Linear
+  COATI_CHECK_ARG(!(wg_each && p.ln_xhat), "xformer_bwd: a1 / a2 hold xhat; the per-Linear weight gradients take the Linear's input");
   COATI_CHECK_ARG(!inputs_only || (!p.tail && !c.use_fp8 && dinjection != nullptr), "xformer_bwd: the inputs-only backward serves a full bf16 pass with an injection");
   if (l_hi == L && p.tail) {
     // ln_f backward on the B tail rows (dyf = [B, C]); not deferred: its partial sums have their own row count
@@ -1133,7 +1193,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
     // backward in its write-out where the shape takes it
     int lnf_fused = 0;
     if (lmh_dlogits != nullptr) {
-      lnf_fused = dgrad_lnbwd(SITE_LMHEAD_DGRAD, lmh_dlogits, e->Vpad, e->S + e->lmheadT, p.x[L], p.meanf, p.rstdf, e->P + e->lnfw, e->lnfw, e->lnfb,
+      lnf_fused = dgrad_lnbwd(SITE_LMHEAD_DGRAD, lmh_dlogits, e->Vpad, e->S + e->lmheadT, p.x[L], nullptr, p.meanf, p.rstdf, e->P + e->lnfw, e->lnfw, e->lnfb,
                               grp ? e->w_dxa[L - 1] : e->DX16, nullptr, nullptr, false);
       if (lnf_fused < 0) return lnf_fused;
       if (!lnf_fused) COATI_TRY(gemm(e, SITE_LMHEAD_DGRAD, lmh_dlogits, 0, e->Vpad, e->S + e->lmheadT, e->Vpad, M, C, e->Vpad, e->da, C, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
@@ -1184,7 +1244,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
       COATI_TRY(gemm(e, SITE_FC2_DGRAD, dxa, 0, C, e->S + w.fc2T, C, M, 4 * C, C, dh4, 4 * C, nullptr, EPI_MUL_AUX, p.hpre[l], nullptr, 4 * C, s));
       // hpre = a2 W1^T + b1 ; at packed-batch sizes with ln_2's backward in the write-out
       // ... and, chained behind it in the same launch, the c_proj input gradient dyb = dxb Wp (the attention backward's dO)
-      ln2_fused = dgrad_lnbwd(SITE_FC1_DGRAD, dh4, 4 * C, e->S + w.fc1T, p.xmid[l], p.mean2[l], p.rstd2[l], e->P + w.ln2w, w.ln2w, w.ln2b, dxb,
+      ln2_fused = dgrad_lnbwd(SITE_FC1_DGRAD, dh4, 4 * C, e->S + w.fc1T, p.xmid[l], p.ln_xhat ? p.a2[l] : nullptr, p.mean2[l], p.rstd2[l], e->P + w.ln2w, w.ln2w, w.ln2b, dxb,
                               e->S + w.projT, e->dyb);
       if (ln2_fused < 0) return ln2_fused;
       if (!ln2_fused) COATI_TRY(gemm(e, SITE_FC1_DGRAD, dh4, 0, 4 * C, e->S + w.fc1T, 4 * C, M, C, 4 * C, e->da, C, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
@@ -1219,7 +1279,7 @@ int xformer_bwd(coati_engine* e, XPass& p, const void* dyf, int dyf_f32, float* 
       a.C = e->da; a.ldc = C;
       COATI_TRY(gemm8(e, SITE_QKV_DGRAD, w, 4, dqkv, 3 * C, M, C, 3 * C, a, EPI_BF16, s));
     } else {
-    ln1_fused = dgrad_lnbwd(SITE_QKV_DGRAD, dqkv, 3 * C, e->S + w.attnT, p.x[l], p.mean1[l], p.rstd1[l], e->P + w.ln1w, w.ln1w, w.ln1b, dx_out);
+    ln1_fused = dgrad_lnbwd(SITE_QKV_DGRAD, dqkv, 3 * C, e->S + w.attnT, p.x[l], p.ln_xhat ? p.a1[l] : nullptr, p.mean1[l], p.rstd1[l], e->P + w.ln1w, w.ln1w, w.ln1b, dx_out);
     if (ln1_fused < 0) return ln1_fused;
     if (!ln1_fused) COATI_TRY(gemm(e, SITE_QKV_DGRAD, dqkv, 0, 3 * C, e->S + w.attnT, 3 * C, M, C, 3 * C, e->da, C, nullptr, EPI_BF16, nullptr, nullptr, 0, s));
     }
@@ -2537,6 +2597,11 @@ int coati_engine_decode_begin(coati_engine* e, void* workspace, int64_t ws_bytes
 }
 
 int coati_engine_decode_pos(coati_engine* e) { return (e && e->dec.active) ? e->dec.pos : -1; }
+
+int coati_engine_ln_saves_xhat(const coati_engine* e, int pass) {
+  COATI_CHECK_ARG(e != nullptr && (pass == 0 || pass == 1), "engine_ln_saves_xhat: null engine or pass %d (0 = encoder, 1 = decoder)", pass);
+  return (pass == 0 ? e->p1 : e->p2).ln_xhat ? 1 : 0;
+}
 
 }  // extern "C"
 

@@ -288,6 +288,11 @@ int launch_gemm_nt(const GemmArgs& a, int a_f32, int epi, hipStream_t s) {
   if (epi == EPI_CE_BWD_ROW) COATI_CHECK_ARG(a.lse && a.target && a.row_scale, "gemm_nt: per-row CE operands missing");
   if (epi == EPI_QKV_ROPE) COATI_CHECK_ARG(a.rope_cos && a.rope_sin && a.rope_T > 0 && a.rope_C > 0 && a.N % 16 == 0 && a.rope_C % 16 == 0 && (a.rope_hs == 0 || a.rope_hs == 16 || a.rope_hs == 32) && (a.rope_hs != 32 || a.rope_C % 32 == 0), "gemm_nt: rope operands missing / unsupported head size");
   if (epi == EPI_EDGE_DPRE) COATI_CHECK_ARG(a.P && a.d2 && a.w1c && a.b1 && a.natom > 0 && a.ldp % 8 == 0, "gemm_nt: edge operands missing");
+  if (a.ln_save_xhat) {   // xhat as the saved copy of a fused LayerNorm: the 16-row-slab kernel only; nobody else may take the launch and save a
+    COATI_CHECK_ARG(a.ln_x != nullptr && (epi == EPI_QKV_ROPE || epi == EPI_GELU_GRAD) && gemm_rb16_supported(a, a_f32, epi),
+                    "gemm_nt: ln_save_xhat needs the LayerNorm-fused 16-row-slab kernel (36 865 .. 65 536 rows, K = 256; M=%d K=%d epi=%d)", a.M, a.K, epi);
+    return launch_gemm_rb16(a, epi, s);
+  }
   {
     // N = 256 with a bf16 / residual epilogue: the ring kernel, also at K = 256 (proj forward 57 -> 44 us against the
     // row-block kernel); every other K = 256 product: the row-block kernel
@@ -875,7 +880,7 @@ struct W2Frags { bf16x8 a[4], b[2]; };
 // slices of a tile meet in fp32 atomics; no bias; N need not be a multiple of 256 -- the A columns past N come from the zero page and
 // the rows past n_out are not committed.
 template <int NS, bool SPLIT>
-__device__ __forceinline__ void wgrad256_body(const WgradArgs& p, int tiles_k, int tile, int c_begin, int c_end, unsigned char* smem) {
+__device__ __forceinline__ void wgrad256_body(const WgradArgs& p, int tiles_k, int tile, int c_begin, int c_end, unsigned char* smem, bool affine = false) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const int tile_n = tile / tiles_k, tile_k = tile - tile_n * tiles_k;
@@ -1063,6 +1068,28 @@ __device__ __forceinline__ void wgrad256_body(const WgradArgs& p, int tiles_k, i
     const float t = bsum[tid] + bsum[256 + tid] + bsum[512 + tid] + bsum[768 + tid];
     if (tiles_k == 1) p.dbias[n0 + tid] += t;
     else atomicAdd(p.dbias + n0 + tid, t);
+    if (affine) bsum[1024 + tid] = t;
+  }
+  if (affine) {
+    // B held xhat of a LayerNorm, the Linear's input is xhat gamma + beta (tiles_k == 1: acc is the whole sum over M, bsum the whole
+    // column sum): dW[n, k] += gamma[k] sum_m dY[m, n] xhat[m, k] + beta[k] sum_m dY[m, n]
+    __syncthreads();
+    float gk[2], bk[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { gk[j] = p.b_gamma[k0 + wn * 64 + j * 32 + (lane & 31)]; bk[j] = p.b_beta[k0 + wn * 64 + j * 32 + (lane & 31)]; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int nl = wm * 128 + i * 32 + frag_row(r, lane);
+        const float cs = bsum[1024 + nl];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int k = k0 + wn * 64 + j * 32 + (lane & 31);
+          p.dW[(long long)(n0 + nl) * p.ldw + k] += fmaf(gk[j], acc[i][j][r], bk[j] * cs);
+        }
+      }
+    return;
   }
   // this workgroup is the only one that touches the tile now: plain read-add-store
 #pragma unroll
@@ -1078,12 +1105,13 @@ __device__ __forceinline__ void wgrad256_body(const WgradArgs& p, int tiles_k, i
 }
 
 template <int NS>
-__global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile* __restrict__ table, int M_rt) {
+__global__ __launch_bounds__(512, 1) void wgrad256_table_kernel(const WgradTile* __restrict__ table, int M_rt, int b_affine) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const WgradTile& d = table[xcd_swizzle(blockIdx.x, gridDim.x)];
   WgradArgs p = d.p;
   if (M_rt > 0) p.M = M_rt;   // the rows of THIS launch (see wgrad_dma_table_kernel)
-  wgrad256_body<NS, false>(p, d.tiles_k, d.tile, 0, (p.M + W2_CH - 1) / W2_CH, smem);
+  // (b_affine is the LAUNCH's word on whether the B rows are xhat: a table cached across batches carries gamma / beta for either kind)
+  wgrad256_body<NS, false>(p, d.tiles_k, d.tile, 0, (p.M + W2_CH - 1) / W2_CH, smem, b_affine != 0 && p.b_gamma != nullptr);
 }
 
 // One problem, 256 x 256 tiles, M split over the workgroups of a tile so that one round fills the machine (the lm_head's weight gradient:
@@ -1109,6 +1137,9 @@ int wgrad_table_append(std::vector<WgradTile>& tab, const WgradArgs& a, int tile
   COATI_CHECK_ARG(a.A && a.B && a.dW && a.dbias, "wgrad_table: null operand (the grouped kernel is the bias variant)");
   COATI_CHECK_SHAPE(a.M > 0 && a.N % 8 == 0 && a.K % 8 == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0, "wgrad_table: shape / alignment");
   COATI_CHECK_ARG(tile_size == 128 || tile_size == 256, "wgrad_table: tile size %d", tile_size);
+  COATI_CHECK_ARG((a.b_gamma == nullptr) == (a.b_beta == nullptr), "wgrad_table: b_gamma and b_beta come together");
+  // gamma / beta on the finished tile need the workgroup that owns the tile to hold the whole column sum of A
+  COATI_CHECK_ARG(a.b_gamma == nullptr || (tile_size == 256 && a.K == 256), "wgrad_table: b_gamma / b_beta need 256-wide tiles and K = 256 (tile %d, K=%d)", tile_size, a.K);
   if (tile_size == 256) {
     COATI_CHECK_SHAPE(wgrad_table_tile256_ok(a), "wgrad_table: 256-wide tiles need N and K to be multiples of 256 (N=%d K=%d)", a.N, a.K);
     const int tk = a.K / 256, nt = (a.N / 256) * tk;
@@ -1123,6 +1154,7 @@ int wgrad_table_append(std::vector<WgradTile>& tab, const WgradArgs& a, int tile
 
 int wgrad_table_append_split(std::vector<WgradTile>& tab, const WgradArgs& a, int n_splits) {
   COATI_CHECK_ARG(a.A && a.B && a.dW, "wgrad_table(split): null operand");
+  COATI_CHECK_ARG(a.b_gamma == nullptr && a.b_beta == nullptr, "wgrad_table(split): b_gamma / b_beta belong to the grouped 256-wide tiles");
   COATI_CHECK_SHAPE(a.M > 0 && a.N % 8 == 0 && a.K % 8 == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0 && a.m_dev == nullptr, "wgrad_table(split): shape / alignment");
   const int tiles_n = cdiv(a.N, BM), tiles_k = cdiv(a.K, BN), nchunks = cdiv(a.M, WD_CH);
   if (n_splits > cdiv(nchunks, 4)) n_splits = cdiv(nchunks, 4);
@@ -1175,7 +1207,7 @@ static int launch_wgrad_table_t(const WgradTile* dev_table, int n_tiles, hipStre
 }
 
 template <int NS>
-static int launch_wgrad256_t(const WgradTile* dev_table, int n_tiles, hipStream_t s, int M_rt) {
+static int launch_wgrad256_t(const WgradTile* dev_table, int n_tiles, hipStream_t s, int M_rt, int b_affine) {
   static bool attr_set = false;
   auto kern = wgrad256_table_kernel<NS>;
   constexpr int lds = NS * W2_STAGE_BYTES;
@@ -1187,7 +1219,7 @@ static int launch_wgrad256_t(const WgradTile* dev_table, int n_tiles, hipStream_
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(512), lds, s, dev_table, M_rt);
+  hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(512), lds, s, dev_table, M_rt, b_affine);
   COATI_LAUNCH_CHECK("wgrad_table256");
   return COATI_OK;
 }
@@ -1224,11 +1256,11 @@ static int launch_wgrad256_split(const WgradArgs& a, hipStream_t s) {
   return COATI_OK;
 }
 
-int launch_wgrad_table(const WgradTile* dev_table, int n_tiles, hipStream_t s, int tile_size, int M_rt) {
+int launch_wgrad_table(const WgradTile* dev_table, int n_tiles, hipStream_t s, int tile_size, int M_rt, int b_affine) {
   COATI_CHECK_ARG(dev_table && n_tiles > 0, "wgrad_table: empty table");
   if (tile_size == 256) {
     // ring of 4 stages of 32 KiB (96 KiB in flight per CU); a 5-deep ring (all 160 KiB of LDS) measured the same (round 2)
-    return launch_wgrad256_t<4>(dev_table, n_tiles, s, M_rt);
+    return launch_wgrad256_t<4>(dev_table, n_tiles, s, M_rt, b_affine);
   }
   return launch_wgrad_table_t<4>(dev_table, n_tiles, s, M_rt);   // ring of 4 stages of 32 KiB, 3 in flight
 }
@@ -1294,6 +1326,7 @@ static int launch_wgrad_t(const WgradArgs& a, hipStream_t s) {
 
 int launch_wgrad(const WgradArgs& a, int a_f32, hipStream_t s) {
   COATI_CHECK_ARG(a.A && a.B && a.dW, "wgrad: null operand");
+  COATI_CHECK_ARG(a.b_gamma == nullptr && a.b_beta == nullptr, "wgrad: b_gamma / b_beta belong to the grouped 256-wide tiles (wgrad_table)");
   COATI_CHECK_SHAPE(a.M > 0 && a.N > 0 && a.K > 0, "wgrad: empty problem");
   COATI_CHECK_SHAPE(a.N % 8 == 0 && a.K % 8 == 0, "wgrad: N=%d and K=%d must be multiples of 8", a.N, a.K);
   COATI_CHECK_SHAPE(a.lda % 8 == 0 && a.ldb % 8 == 0, "wgrad: lda/ldb alignment");

@@ -138,11 +138,14 @@ __global__ __launch_bounds__(64 * R16_MAXW, 1) void gemm_rb16_kernel(GemmArgs p,
       const float4 g0 = *reinterpret_cast<const float4*>(GB + ks * 32 + kq * 8), g1 = *reinterpret_cast<const float4*>(GB + ks * 32 + kq * 8 + 4);
       const float4 b0 = *reinterpret_cast<const float4*>(GB + 256 + ks * 32 + kq * 8), b1 = *reinterpret_cast<const float4*>(GB + 256 + ks * 32 + kq * 8 + 4);
       const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, bt[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-      float o[8];
+      float o[8], xh[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = (xf[ks][i] - mean) * rstd * g[i] + bt[i];
-      const uint4 u = pack8(o);
+      for (int i = 0; i < 8; ++i) { xh[i] = (xf[ks][i] - mean) * rstd; o[i] = xh[i] * g[i] + bt[i]; }
+      uint4 u = pack8(o);
       af[ks] = __builtin_bit_cast(bf16x8, u);
+      // ln_save_xhat: the saved copy is xhat itself (the LayerNorm backward reads it in place of f32 x, the weight gradient applies
+      // gamma / beta to its finished tile); the operand above is the same either way
+      if (p.ln_save_xhat) u = pack8(xh);
       // (non-temporal: only the backward's weight gradient reads this copy, a whole forward pass later -- it should not push the rows
       //  the next launch reads out of the caches.  With the NewGELU' codes below: 21.05 vs 21.10 ms per step, A/B x 3 on one box)
       if (row_l < p.M) __builtin_nontemporal_store(r16_v4u{u.x, u.y, u.z, u.w}, reinterpret_cast<r16_v4u*>(op + ks * 32));

@@ -363,8 +363,15 @@ __device__ __forceinline__ void r1_wait_vm(int n) {   // s_waitcnt vmcnt(n), n =
   else __builtin_amdgcn_s_waitcnt(0x0f70);
 }
 
-template <int EPI>
+// EPI_LNBWD's write-out exists in two forms that differ in where xhat comes from: gemm_ring1_kernel<EPI_LNBWD> reads the bf16 xhat the
+// forward saved (lnb_xhat: half the bytes of x, no mean) and widens it; gemm_ring1_kernel<EPI_LNBWD_X32> rebuilds it from the f32 rows x,
+// mean and rstd.  Two instantiations, not a branch: with both forms behind a wave-uniform branch in one kernel the register allocator
+// spilled 57 registers of a write-out that lives at exactly 128 (either form alone: 1 .. 4)
+constexpr int EPI_LNBWD_X32 = EPI_COUNT + EPI_LNBWD;
+template <int EPI_T>
 __global__ __launch_bounds__(64 * R1_WAVES, 1) void gemm_ring1_kernel(GemmArgs p, int R) {
+  constexpr int EPI = EPI_T == EPI_LNBWD_X32 ? (int)EPI_LNBWD : EPI_T;
+  constexpr bool XH = EPI_T == EPI_LNBWD;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef __attribute__((address_space(3))) unsigned char lds_u8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -542,6 +549,7 @@ __global__ __launch_bounds__(64 * R1_WAVES, 1) void gemm_ring1_kernel(GemmArgs p
 #pragma unroll
     for (int r = 8; r < 16; ++r)
       *reinterpret_cast<float4*>(stash + ((r - 8) * 64 + lane) * 4) = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
+    const bf16_t* const xh16 = p.lnb_xhat;
     float xq[2][4][4], mu[2][4], rs[2][4];
     unsigned ro[2][4];
     auto issue_x = [&](int q, int i) __attribute__((always_inline)) {
@@ -549,9 +557,16 @@ __global__ __launch_bounds__(64 * R1_WAVES, 1) void gemm_ring1_kernel(GemmArgs p
       const int row = wrow0 + i + 8 * q + 4 * hw;      // = wrow0 + rg_frag_row(4 q + i, lane)
       const int rc = (full || row < row_end) ? row : row_end - 1;
       ro[b][i] = ((unsigned)rc * (unsigned)p.ldc + col0) * 4u;
-      mu[b][i] = p.lnb_mean[rc]; rs[b][i] = p.lnb_rstd[rc];
+      rs[b][i] = p.lnb_rstd[rc];
+      if constexpr (XH) {
+        // (the 16-bit load zero-extends into its register: the bit cast is no instruction, nothing waits for the value here)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) xq[b][i][j] = rg_ld(xin, ro[b][i], j * 128);
+        for (int j = 0; j < 4; ++j) xq[b][i][j] = __uint_as_float((unsigned)rg_ld(xh16, ro[b][i] >> 1, j * 64));
+      } else {
+        mu[b][i] = p.lnb_mean[rc];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xq[b][i][j] = rg_ld(xin, ro[b][i], j * 128);
+      }
     };
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_x(0, i);
@@ -587,7 +602,7 @@ __global__ __launch_bounds__(64 * R1_WAVES, 1) void gemm_ring1_kernel(GemmArgs p
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float a = acc[j][4 * q + i];
-          const float xn = (xq[b][i][j] - mu[b][i]) * rs[b][i];
+          const float xn = XH ? __uint_as_float(__float_as_uint(xq[b][i][j]) << 16) : (xq[b][i][j] - mu[b][i]) * rs[b][i];
           const float g = a * gm[j];
           s1 += g; s2 += g * xn;
           dgam[j] += a * xn; dbet[j] += a;
@@ -632,11 +647,16 @@ __global__ __launch_bounds__(64 * R1_WAVES, 1) void gemm_ring1_kernel(GemmArgs p
       for (int i = 0; i < 4; ++i) {
         const int row = wrow0 + i + 8 * q + 4 * hw;
         if (full || row < row_end) {
+          // (XH: the halved offset is formed again from a laundered copy -- shared with the one issue_x used, it stays alive from the load
+          //  to here, a second address register per row slot)
+          unsigned roh = ro[b][i];
+          if constexpr (XH) asm volatile("" : "+v"(roh));
+          roh >>= 1;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float o = rs[b][i] * (acc[j][4 * q + i] * gm[j] - c1[i] - xq[b][i][j] * c2[i]) + dr[i][j];
             rg_st(out, ro[b][i], j * 128, o);
-            if (has16) rg_st(out16, ro[b][i] >> 1, j * 64, f2bf(o));
+            if (has16) rg_st(out16, roh, j * 64, f2bf(o));
           }
         }
         if (q < 3) issue_x(q + 1, i);
@@ -1022,11 +1042,11 @@ int launch_gemm_ring256(const GemmArgs& a, int epi, hipStream_t s) {
   if (epi == EPI_LNBWD) {
     int nwg = 0;
     COATI_CHECK_SHAPE(gemm_ring_lnbwd_supported(a, &nwg), "gemm_ring: EPI_LNBWD needs N = 256 and 40 961 .. 57 344 rows (M=%d N=%d K=%d)", a.M, a.N, a.K);
-    COATI_CHECK_ARG(a.lnb_x && a.lnb_mean && a.lnb_rstd && a.lnb_gamma && a.lnb_partial && a.C && a.bias == nullptr, "gemm_ring: EPI_LNBWD operands missing");
+    COATI_CHECK_ARG((a.lnb_xhat || (a.lnb_x && a.lnb_mean)) && a.lnb_rstd && a.lnb_gamma && a.lnb_partial && a.C && a.bias == nullptr, "gemm_ring: EPI_LNBWD operands missing");
     COATI_CHECK_ARG(a.chain_W == nullptr || (a.aux_out != nullptr && a.chain_C != nullptr && a.chain_ldw % 8 == 0 && a.chain_ldc % 8 == 0 && 260LL * a.chain_ldw < (1LL << 30)),
                     "gemm_ring: EPI_LNBWD chained product needs the bf16 copy (aux_out), chain_C and aligned pitches");
-    COATI_CHECK_SHAPE(a.lnb_ldx == a.ldc && (a.aux_in == nullptr || a.ld_aux == a.ldc) && ((long long)a.M + 8) * a.ldc * 4 < (1LL << 32), "gemm_ring: EPI_LNBWD wants one row pitch for x / dres / dx (ldx=%lld ld_aux=%lld ldc=%lld)", a.lnb_ldx, a.ld_aux, a.ldc);
-    return launch_ring1_t<EPI_LNBWD>(a, cdiv(cdiv(a.M, 256), 8) * 8, s);
+    COATI_CHECK_SHAPE((a.lnb_xhat != nullptr || a.lnb_ldx == a.ldc) && (a.aux_in == nullptr || a.ld_aux == a.ldc) && ((long long)a.M + 8) * a.ldc * 4 < (1LL << 32), "gemm_ring: EPI_LNBWD wants one row pitch for x / dres / dx (ldx=%lld ld_aux=%lld ldc=%lld)", a.lnb_ldx, a.ld_aux, a.ldc);
+    return a.lnb_xhat != nullptr ? launch_ring1_t<EPI_LNBWD>(a, cdiv(cdiv(a.M, 256), 8) * 8, s) : launch_ring1_t<EPI_LNBWD_X32>(a, cdiv(cdiv(a.M, 256), 8) * 8, s);
   }
   // block height: rows the busiest of the 256 persistent workgroups walks = rounds x block rows; ties go to the 160-row form
   // (less weight re-streaming per row).

@@ -86,8 +86,12 @@ struct GemmArgs {
   const float* ln_beta;     // [K]
   float* ln_mean;           // [M]
   float* ln_rstd;           // [M]
+  int ln_save_xhat;         // 16-row-slab kernel only: A receives xhat = (ln_x - mean) * rstd (bf16) instead of xhat * gamma + beta; the product is the
+                            // same bit for bit.  The LayerNorm backward then reads those 2 bytes per element (lnb_xhat) instead of 4 of f32 x, and
+                            // the weight gradient applies gamma / beta to its finished tile (WgradArgs::b_gamma / b_beta)
   // EPI_LNBWD: the LayerNorm whose OUTPUT gradient this product computes
   const float* lnb_x;       // [M, N] f32: the LayerNorm's input rows
+  const bf16_t* lnb_xhat;   // optional [M, N] bf16, row pitch ldc: the normalised rows as the forward saved them (ln_save_xhat); read INSTEAD of lnb_x / lnb_mean
   long long lnb_ldx;
   const float* lnb_mean;    // [M]
   const float* lnb_rstd;    // [M]
@@ -172,6 +176,11 @@ struct WgradArgs {
   float* dbias;
   int n_out;   // rows of dW that exist (0 -> N); columns of A beyond it must be zero
   const int* m_dev = nullptr;   // optional: rows that exist, read on the device (<= M)
+  // grouped 256-wide tiles with K = 256 only (one workgroup owns a tile and its whole column sum): B holds the NORMALISED rows xhat of a
+  // LayerNorm whose output a = xhat * gamma + beta is the Linear's real input (GemmArgs::ln_save_xhat); the finished tile is committed as
+  // dW[n, k] += b_gamma[k] * acc[n, k] + b_beta[k] * colsum(A)[n].  Both or neither; applied only by a launch that says so (b_affine)
+  const float* b_gamma = nullptr;   // [K]
+  const float* b_beta = nullptr;    // [K]
 };
 int launch_wgrad(const WgradArgs& a, int a_f32, hipStream_t s);
 // Grouped, atomics-free form (gemm.hip, wgrad_dma_table_kernel): one workgroup per 128 x 128 output tile of a list of
@@ -182,7 +191,9 @@ struct WgradTile {
   int tile;      // tile index inside the problem (tile_n * tiles_k + tile_k)
   int c_begin = 0, c_end = 0;   // split tables only: the 64-row chunks [c_begin, c_end) of M this entry streams
 };
-int launch_wgrad_table(const WgradTile* dev_table, int n_tiles, hipStream_t s, int tile_size = 128, int M_rt = 0);   // M_rt > 0: rows of this launch (<= the M of the table entries)   // every entry of a table has the same tile size
+int launch_wgrad_table(const WgradTile* dev_table, int n_tiles, hipStream_t s, int tile_size = 128, int M_rt = 0, int b_affine = 1);   // M_rt > 0: rows of this launch (<= the M of the table entries)   // every entry of a table has the same tile size
+// b_affine: whether THIS launch's B operands hold xhat where an entry carries b_gamma / b_beta (0: they hold the Linear's input itself and the
+// entries' b_gamma / b_beta are ignored) -- a cached table serves batches of either kind
 bool wgrad_table_tile256_ok(const WgradArgs& a);
 // Grouped form for SMALL row counts (the E(3)-GNN's node-level Linears: 16 384 rows): the entries of a problem's 128 x 128 tiles
 // are repeated over n_splits slices of M, every entry adds its partial tile with fp32 atomics (dbias may be null)

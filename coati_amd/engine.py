@@ -289,6 +289,14 @@ class Engine:
         """second half of a forward(..., stop_after_heads=True): decoder pass with the injected token, lm_head + AR cross-entropy"""
         _lib.check(self.l.coati_engine_forward_decoder(self.h, stream()), "coati_engine_forward_decoder")
 
+    def ln_saves_xhat(self, which):
+        """whether the LayerNorm-fused launches of the last forward left xhat (True) or the LayerNorm's output (False) in the saved rows of
+        the encoder pass (which = 0) / decoder pass (1): the engine's per-pass, per-step decision (coati_engine_ln_saves_xhat)"""
+        rc = self.l.coati_engine_ln_saves_xhat(self.h, which)
+        if rc < 0:
+            _lib.check(rc, "coati_engine_ln_saves_xhat")
+        return bool(rc)
+
     def contrastive_under_decoder(self, head_fn):
         """Runs head_fn() -- the contrastive head of the step: InfoNCE / Barlow and, data-parallel, the embedding all-gather and the
         reduce-scatter around it -- on a side stream WHILE the decoder pass runs on the current one: the head only needs the

@@ -68,6 +68,39 @@ def gemm_lnbwd(dY, WT, x, mean, rstd, gamma, dres, want16=True, chain_W=None):
     return dx, dx16, s[:256], s[256:]
 
 
+def gemm_lnbwd_xhat(dY, WT, xhat, rstd, gamma, dres, want16=True, chain_W=None, out=None):
+    """gemm_lnbwd with the normalised rows read as the forward saved them (xhat [M, 256] bf16) instead of rebuilt from x and mean
+    (coati_gemm_lnbwd_xhat).  out: the tensor that receives dx (dres itself: in place)."""
+    _need_cuda(dY, WT, xhat)
+    M, K = dY.shape
+    dx = torch.empty(M, 256, device=dY.device, dtype=torch.float32) if out is None else out
+    dx16 = torch.empty(M, 256, device=dY.device, dtype=BF16) if want16 else None
+    partial = torch.zeros(256, 512, device=dY.device, dtype=torch.float32)
+    n = ctypes.c_int32(0)
+    chain_C = torch.empty(M, 256, device=dY.device, dtype=BF16) if chain_W is not None else None
+    _lib.call("coati_gemm_lnbwd_xhat", ptr(dY), dY.stride(0), ptr(WT), WT.stride(0), M, K, ptr(xhat), ptr(rstd), ptr(gamma), ptr(dres),
+              ptr(dx), ptr(dx16), ptr(partial), ctypes.byref(n), ptr(chain_W), ptr(chain_C), stream())
+    s = partial[: n.value].sum(0)
+    if chain_W is not None:
+        return dx, dx16, s[:256], s[256:], chain_C
+    return dx, dx16, s[:256], s[256:]
+
+
+def gemm_ln_gelu_grad(x, gamma, beta, W, bias, save_xhat):
+    """The LayerNorm-fused FC1 product (coati_gemm_ln_gelu_grad): returns (g bf16 [M, N], codes u8 [M, N], saved bf16 [M, 256], mean, rstd);
+    saved = LayerNorm(x) (save_xhat False) or xhat (True)."""
+    _need_cuda(x, W)
+    M, N, dev = x.shape[0], W.shape[0], x.device
+    saved = torch.empty(M, 256, device=dev, dtype=BF16)
+    mean = torch.empty(M, device=dev, dtype=torch.float32)
+    rstd = torch.empty(M, device=dev, dtype=torch.float32)
+    g = torch.empty(M, N, device=dev, dtype=BF16)
+    codes = torch.empty(M, N, device=dev, dtype=torch.uint8)
+    _lib.call("coati_gemm_ln_gelu_grad", ptr(x), x.stride(0), ptr(gamma), ptr(beta), ptr(W), W.stride(0), ptr(bias), M, N, ptr(saved), ptr(mean),
+              ptr(rstd), ptr(g), ptr(codes), 1 if save_xhat else 0, stream())
+    return g, codes, saved, mean, rstd
+
+
 def mlp_fwd(x, gamma, beta, W1, b1, W2, b2):
     """out = x + c_proj(NewGELU(c_fc(ln_2(x)))) in one launch (coati_mlp_fwd): returns (out f32, a2 bf16, mean, rstd, g bf16, codes u8)."""
     _need_cuda(x, W1, W2)
@@ -152,6 +185,30 @@ def wgrad_grouped(problems, tile_size=256):
               Ns, Ks,
               PP(*[ptr(q[2]) for q in problems]), LL(*[q[2].stride(0) for q in problems]),
               PP(*[ptr(q[3]) for q in problems]), tile_size, ptr(ws), nbytes, stream())
+    return ws
+
+
+def wgrad_grouped_affine(problems, tile_size=256):
+    """wgrad_grouped with problems (A, Bm, dW, dbias, gamma | None, beta | None): where gamma / beta [K] are given, Bm holds the xhat of a
+    LayerNorm whose output xhat * gamma + beta is the Linear's input -- dW += A^T @ (Bm * gamma + beta), applied to the finished tile
+    (coati_wgrad_grouped_affine: tile 256 and K = 256 for such a problem)."""
+    n = len(problems)
+    for A, Bm, dW, db, ga, be in problems:
+        _need_cuda(A, Bm, dW, db, ga, be)
+        assert A.dtype == torch.bfloat16 and Bm.dtype == torch.bfloat16 and dW.dtype == torch.float32 and db.dtype == torch.float32
+        assert (ga is None) == (be is None) and (ga is None or (ga.dtype == torch.float32 and be.dtype == torch.float32))
+    M = problems[0][0].shape[0]
+    PP, LL, II = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int * n
+    Ns, Ks = II(*[q[0].shape[1] for q in problems]), II(*[q[1].shape[1] for q in problems])
+    nbytes = int(_lib.lib().coati_wgrad_grouped_workspace_bytes(n, Ns, Ks, tile_size))
+    ws = torch.empty(max(nbytes, 1), device=problems[0][0].device, dtype=torch.uint8)   # the caller owns the tile table
+    _lib.call("coati_wgrad_grouped_affine", n,
+              PP(*[ptr(q[0]) for q in problems]), LL(*[q[0].stride(0) for q in problems]),
+              PP(*[ptr(q[1]) for q in problems]), LL(*[q[1].stride(0) for q in problems]), M,
+              Ns, Ks,
+              PP(*[ptr(q[2]) for q in problems]), LL(*[q[2].stride(0) for q in problems]),
+              PP(*[ptr(q[3]) for q in problems]), PP(*[ptr(q[4]) for q in problems]), PP(*[ptr(q[5]) for q in problems]),
+              tile_size, ptr(ws), nbytes, stream())
     return ws
 
 
