@@ -8,6 +8,7 @@
 #include "../../include/coati_screen.h"
 #include "../../include/coati_guide.h"
 #include "../../include/coati_ln_xhat.h"
+#include "../../include/coati_gp.h"
 #include <vector>
 #include "kernels.h"
 
@@ -334,6 +335,14 @@ int coati_head_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint
                     int D, const float* wl, const float* bl, int P, int F, const uint16_t* w0t, const uint16_t* wrt, const float* cot,
                     int64_t ldc, float* out, int64_t ldo, float* g, int64_t ldg, void* stream) {
   return launch_head_grad(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, F, w0t, wrt, cot, ldc, out, ldo, g, ldg, S_(stream));
+}
+// the GP head on the property head's features (include/coati_gp.h)
+int coati_head_gp(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
+                  int D, int F, const float* wl, const float* bl, int P_lin, float* out, int64_t ldo, const uint16_t* z, const float* zn,
+                  const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, int64_t ldm,
+                  float* var, void* stream) {
+  return launch_head_gp(x, ldx, N, E, w0, b0, wr, br, D, F, wl, bl, P_lin, out, ldo, z, zn, alpha, q, c, inv2l2, s2, P, Mp, mean, ldm, var,
+                        S_(stream));
 }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,

@@ -1,5 +1,5 @@
 // The gradient of a property head with respect to its input rows (include/coati_guide.h): out = head(x) and g = d (cot . out) / dx as one
-// launch.  head_grad_kernel<F, WAVES, NP> is head_body<F, WAVES, NP, true> of head_dev.h: coati_head_eval's forward, instruction for
+// launch.  head_grad_kernel<F, WAVES, NP> is head_body<F, WAVES, NP, HEAD_MODE_GRAD> of head_dev.h: coati_head_eval's forward, instruction for
 // instruction, which also leaves the ReLU decisions as bits in LDS, then the backward through the same chunked, register-chained product
 // loop over the transposed weights.  No activation, mask or d ever exists in memory; no atomics, no workspace.
 //
@@ -16,7 +16,7 @@ __global__ __launch_bounds__(64 * WAVES) void head_grad_kernel(const bf16_t* __r
                                                                const bf16_t* __restrict__ w0t, const bf16_t* __restrict__ wrt,
                                                                const float* __restrict__ cot, long long ldc, float* __restrict__ out,
                                                                long long ldo, float* __restrict__ g, long long ldg) {
-  head_body<F, WAVES, NP, true>(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, out, ldo, w0t, wrt, cot, ldc, g, ldg);
+  head_body<F, WAVES, NP, HEAD_MODE_GRAD>(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, out, ldo, w0t, wrt, cot, ldc, g, ldg, HeadGpOps{});
 }
 
 struct HeadGradArgs {

@@ -1,6 +1,7 @@
-// The property head's device body, shared by head_eval_kernel (screen.hip) and head_grad_kernel (guide.hip): one text, two kernels.
+// The property head's device body, shared by head_eval_kernel (screen.hip), head_grad_kernel (guide.hip) and head_gp_kernel (gp.hip): one
+// text, three kernels.
 //
-// head_body<F, WAVES, NP, GRAD>, one workgroup per tile of WAVES * NP * 32 rows; a wave owns NP panels of 32 rows for the whole kernel:
+// head_body<F, WAVES, NP, MODE>, one workgroup per tile of WAVES * NP * 32 rows; a wave owns NP panels of 32 rows for the whole kernel:
 //  * every product is computed TRANSPOSED on v_mfma_f32_32x32x16_bf16: the weights are the M side (32 output features x 16 inputs, read
 //    from LDS), the rows of the library the N side.  The result map (column = lane & 31 = the lane's ROW of the library, register r =
 //    feature 8 (r >> 2) + 4 (lane >> 5) + (r & 3) of the 32-feature tile) then is, register for register, the B operand of the next
@@ -18,7 +19,7 @@
 //  * the last layer (P <= 8 outputs) is VALU work: a lane's dot over the features it holds, plus the other half-wave's;
 //  * rows >= N (ragged last tile) are read at row N - 1 and never written.
 //
-// GRAD = true goes on where the forward ends (include/coati_guide.h).  The forward leaves, next to `h += max(acc, 0)`, the tile's 16 sign
+// MODE = HEAD_MODE_GRAD goes on where the forward ends (include/coati_guide.h).  The forward leaves, next to `h += max(acc, 0)`, the tile's 16 sign
 // decisions as one 16-bit word per (layer, 32-feature tile, panel, thread) in LDS: the thread that writes a word is the one that reads it,
 // so the words need no barrier of their own.  After `out`, h is dead and d = cot . wl (VALU, like the last layer) takes its registers.  A
 // backward layer is the residual-layer loop once more: chunks of wrt[l] (wr[l] transposed, the same middle-group swap), the operand rb(m (.)
@@ -26,6 +27,13 @@
 // with E output features: its 32-feature tiles go straight to memory (a lane's registers 4 q .. 4 q + 3 are 4 consecutive floats of its row:
 // one 16-byte store).  The chunk sequence is C0 + 2 D MCH + ceil(E / MC), again the same for every thread.
 // No atomics, no workspace.
+//
+// MODE = HEAD_MODE_GP adds the GP head (include/coati_gp.h) where the forward ends.  The inducing points z [Mp, F] are one more residual
+// "layer" of Mp <= 64 <= MC output features: one more chunk of the sequence (C0 + D MCH + 1), staged with the same middle-group swap, rows
+// past Mp not loaded; its operand is phi = rb(h), its accumulators phi . z_j of the lane's row.  After the exponential, register r of tile
+// tt holds k_j, j = 32 tt + 8 (r >> 2) + 4 hh + (r & 3): register for register the B operand (k index = hh) of a v_mfma_f32_32x32x2_f32
+// step against q[m][j0 + 4 hh] read from LDS, so w = q k comes out in k's own map without lane movement and without leaving f32.  mean and
+// k . w are per-lane dots plus half_xchg_sum, like the last layer.  One more barrier (q in LDS), the same for every thread.
 #pragma once
 #include "kernels.h"
 
@@ -51,12 +59,37 @@ constexpr size_t head_grad_lds_bytes(int D) {
   return (size_t)4 * head_buf_elems<F>() + (size_t)D * (F / 32) * NP * (64 * WAVES) * 2;
 }
 
-template <int F, int WAVES, int NP, bool GRAD>
+// what follows the forward: nothing, the input gradient, or the GP head
+#define HEAD_MODE_EVAL 0
+#define HEAD_MODE_GRAD 1
+#define HEAD_MODE_GP 2
+#define HEAD_GP_M_MAX 64   // inducing points (padded to 32 or 64)
+#define HEAD_GP_LDQ 68     // LDS row stride of q (floats): 32 rows' ds_read_b128 start on 8 different 16-byte slots
+
+typedef float head_f32x4 __attribute__((ext_vector_type(4)));
+
+// the operands of the GP tail (HEAD_MODE_GP); the other modes pass an empty one
+struct HeadGpOps {
+  const bf16_t* z;      // [Mp, F]
+  const float* zn;      // [Mp]
+  const float* alpha;   // [P, Mp]
+  const float* q;       // [Mp, Mp]
+  const float* c;       // [P]
+  float inv2l2, s2;
+  int P, Mp;
+  float* mean;          // [N, P], row stride ldm
+  long long ldm;
+  float* var;           // [N]
+};
+
+template <int F, int WAVES, int NP, int MODE>
 __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long long ldx, long long N, int E, const bf16_t* __restrict__ w0,
                                           const float* __restrict__ b0, const bf16_t* __restrict__ wr, const float* __restrict__ br, int D,
                                           const float* __restrict__ wl, const float* __restrict__ bl, int P, float* __restrict__ out,
                                           long long ldo, const bf16_t* __restrict__ w0t, const bf16_t* __restrict__ wrt,
-                                          const float* __restrict__ cot, long long ldc, float* __restrict__ g, long long ldg) {
+                                          const float* __restrict__ cot, long long ldc, float* __restrict__ g, long long ldg,
+                                          const HeadGpOps& gp) {
+  constexpr bool GRAD = MODE == HEAD_MODE_GRAD, GP = MODE == HEAD_MODE_GP;
   constexpr int NT = 64 * WAVES, MT = F / 32, KS = F / 16;
   constexpr int MC = HEAD_CHUNK / F < F ? HEAD_CHUNK / F : F;   // output features per residual chunk: 64 (F = 256), 128, 64
   constexpr int MCH = F / MC, TPC = MC / 32;                    // chunks per residual layer, 32-feature tiles per chunk
@@ -77,7 +110,7 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hh = lane >> 5;
   const int C0 = (E + HEAD_KC - 1) / HEAD_KC;
-  const int CT = GRAD ? C0 + 2 * D * MCH + (E + MC - 1) / MC : C0 + D * MCH;
+  const int CT = GRAD ? C0 + 2 * D * MCH + (E + MC - 1) / MC : C0 + D * MCH + (GP ? 1 : 0);
   const long long row0 = (long long)blockIdx.x * (WAVES * NP * 32) + wave * (NP * 32);
 
   // chunk gc of the sequence: global -> st (stage_load), st -> lds[gc & 1] (stage_store)
@@ -91,10 +124,13 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
       if (first) {   // (a 16-column unit past E, in the last chunk of E % 64 == 32, is neither loaded nor read)
         on = u < U0 && HEAD_KC * gc + 16 * (u & 3) < E;
         src = w0 + (long long)(u >> 2) * E + HEAD_KC * gc + 16 * (u & 3);
-      } else if (!GRAD || gc - C0 < D * MCH) {
+      } else if (MODE == HEAD_MODE_EVAL || gc - C0 < D * MCH) {
         const int cc = gc - C0;
         on = u < UR;
         src = wr + ((long long)(cc / MCH) * F + (cc % MCH) * MC + u / KS) * F + 16 * (u % KS);
+      } else if (GP) {                      // z [Mp, F], one chunk (Mp <= 64 <= MC): its rows, none past Mp
+        on = u < UR && u / KS < gp.Mp;
+        src = gp.z + (long long)(u / KS) * F + 16 * (u % KS);
       } else if (gc - C0 < 2 * D * MCH) {   // backward layer D - 1 - cc / MCH: the same chunks of the transposed weights
         const int cc = gc - C0 - D * MCH;
         on = u < UR;
@@ -289,6 +325,170 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
       const float tot = half_xchg_sum(sum[p]) + bo;
       const long long row = row0 + 32 * p + n;
       if (hh == 0 && row < N) out[row * ldo + o] = tot;
+    }
+  }
+
+  if constexpr (GP) {
+    // phi = rb(h) is the operand of one more chained product, against z: its chunk (number gc) came in under the last residual chunk.
+    // |phi|^2 is summed over the rounded values the lane holds, then over the two half-waves
+    const int Mp = gp.Mp;
+    bf16x8 bfr[NP][KS];
+    float pn[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      pn[p] = 0.f;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          uint4 v;
+          v.x = pack2bf(h[mt][p][8 * t], h[mt][p][8 * t + 1]);
+          v.y = pack2bf(h[mt][p][8 * t + 2], h[mt][p][8 * t + 3]);
+          v.z = pack2bf(h[mt][p][8 * t + 4], h[mt][p][8 * t + 5]);
+          v.w = pack2bf(h[mt][p][8 * t + 6], h[mt][p][8 * t + 7]);
+          bfr[p][2 * mt + t] = __builtin_bit_cast(bf16x8, v);
+          float f[8];
+          unpack8(v, f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) pn[p] = fmaf(f[e], f[e], pn[p]);
+        }
+      pn[p] = half_xchg_sum(pn[p]);
+    }
+
+    // q [Mp, Mp] f32 travels global -> registers under the z product and registers -> LDS behind it: into the weight buffer that the
+    // chunk sequence has left (its last reader is behind the previous barrier), or, where that is too small (F = 64), an array of its own
+    constexpr int QPT = HEAD_GP_M_MAX * HEAD_GP_M_MAX / 4 / NT;
+    constexpr bool QOWN = 2 * BUF < 4 * HEAD_GP_M_MAX * HEAD_GP_LDQ;
+    float* qs;
+    if constexpr (QOWN) {
+      __shared__ __attribute__((aligned(16))) float head_q[HEAD_GP_M_MAX * HEAD_GP_LDQ];
+      qs = head_q;
+    } else {
+      qs = reinterpret_cast<float*>(lds + ((gc + 1) & 1) * BUF);
+    }
+    const int QU = Mp * Mp / 4;   // 16-byte units of q
+    head_f32x4 qv[QPT];
+#pragma unroll
+    for (int i = 0; i < QPT; ++i) {
+      const int u = tid + NT * i;
+      qv[i] = u < QU ? *reinterpret_cast<const head_f32x4*>(gp.q + 4 * u) : head_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    // k[tt][p][r] = s2 exp(-d2 inv2l2) of inducing point 32 tt + 8 (r >> 2) + 4 hh + (r & 3) and the lane's row; exp as exp2 (v_exp_f32)
+    const float nl = -gp.inv2l2 * 1.44269504088896341f;
+    f32x16 kk[HEAD_GP_M_MAX / 32][NP];
+    {
+      const bf16_t* a = lds + (gc & 1) * BUF + n * LDR + 8 * hh;
+#pragma unroll
+      for (int tt = 0; tt < HEAD_GP_M_MAX / 32; ++tt) {
+        if (32 * tt < Mp) {   // (the same for every thread)
+          f32x16 acc[NP];
+#pragma unroll
+          for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+#pragma unroll
+          for (int s = 0; s < KS; ++s) {
+            const bf16x8 af = *reinterpret_cast<const bf16x8*>(a + 32 * tt * LDR + 16 * s);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[p][s], acc[p], 0, 0, 0);
+          }
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 zv = *reinterpret_cast<const float4*>(gp.zn + 32 * tt + 8 * q4 + 4 * hh);
+            const float ze[4] = {zv.x, zv.y, zv.z, zv.w};
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float d2 = fmaxf(fmaf(-2.f, acc[p][4 * q4 + e], pn[p] + ze[e]), 0.f);
+                kk[tt][p][4 * q4 + e] = gp.s2 * __builtin_amdgcn_exp2f(d2 * nl);
+              }
+          }
+        } else {
+#pragma unroll
+          for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) kk[tt][p][r] = 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < QPT; ++i) {
+      const int u = tid + NT * i;
+      if (u < QU) *reinterpret_cast<head_f32x4*>(qs + ((4 * u) / Mp) * HEAD_GP_LDQ + (4 * u) % Mp) = qv[i];
+    }
+
+    // mean: the lane's k against alpha, then the other half-wave's (like the last layer)
+    for (int o = 0; o < gp.P; ++o) {
+      float sum[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) sum[p] = 0.f;
+      const float* ao = gp.alpha + (long long)o * Mp + 4 * hh;
+#pragma unroll
+      for (int tt = 0; tt < HEAD_GP_M_MAX / 32; ++tt)
+        if (32 * tt < Mp) {
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            const float4 av = *reinterpret_cast<const float4*>(ao + 32 * tt + 8 * q4);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+              sum[p] = fmaf(av.x, kk[tt][p][4 * q4], sum[p]);
+              sum[p] = fmaf(av.y, kk[tt][p][4 * q4 + 1], sum[p]);
+              sum[p] = fmaf(av.z, kk[tt][p][4 * q4 + 2], sum[p]);
+              sum[p] = fmaf(av.w, kk[tt][p][4 * q4 + 3], sum[p]);
+            }
+          }
+        }
+      const float co = gp.c[o];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const float tot = half_xchg_sum(sum[p]) + co;
+        const long long row = row0 + 32 * p + n;
+        if (hh == 0 && row < N) gp.mean[row * gp.ldm + o] = tot;
+      }
+    }
+    __syncthreads();   // q is in LDS
+
+    // w = q k on v_mfma_f32_32x32x2_f32, all f32: register r of k's tile tt is the B operand (k index = hh) of the step against
+    // q[32 mi + n][32 tt + 8 (r >> 2) + 4 hh + (r & 3)], and w comes out in k's own map; var = s2 - k . w
+    const float* qa = qs + n * HEAD_GP_LDQ + 4 * hh;
+    float quad[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) quad[p] = 0.f;
+#pragma unroll
+    for (int mi = 0; mi < HEAD_GP_M_MAX / 32; ++mi)
+      if (32 * mi < Mp) {
+        f32x16 w[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) w[p][r] = 0.f;
+#pragma unroll
+        for (int tt = 0; tt < HEAD_GP_M_MAX / 32; ++tt)
+          if (32 * tt < Mp) {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+              const float4 av = *reinterpret_cast<const float4*>(qa + 32 * mi * HEAD_GP_LDQ + 32 * tt + 8 * q4);
+#pragma unroll
+              for (int p = 0; p < NP; ++p) {
+                w[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, kk[tt][p][4 * q4], w[p], 0, 0, 0);
+                w[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, kk[tt][p][4 * q4 + 1], w[p], 0, 0, 0);
+                w[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, kk[tt][p][4 * q4 + 2], w[p], 0, 0, 0);
+                w[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, kk[tt][p][4 * q4 + 3], w[p], 0, 0, 0);
+              }
+            }
+          }
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) quad[p] = fmaf(kk[mi][p][r], w[p][r], quad[p]);
+      }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const float v = fmaxf(gp.s2 - half_xchg_sum(quad[p]), 0.f);
+      const long long row = row0 + 32 * p + n;
+      if (hh == 0 && row < N) gp.var[row] = v;
     }
   }
 

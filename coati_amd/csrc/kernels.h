@@ -385,6 +385,12 @@ int launch_head_eval(const bf16_t* x, long long ldx, long long N, int E, const b
 int launch_head_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
                      int D, const float* wl, const float* bl, int P, int F, const bf16_t* w0t, const bf16_t* wrt, const float* cot,
                      long long ldc, float* out, long long ldo, float* g, long long ldg, hipStream_t s);
+// the GP head (gp.hip, include/coati_gp.h): launch_head_eval's forward (out only if wl is given), then mean [N, P] and var [N] of an RBF GP
+// on Mp inducing points z over the rounded last stream
+int launch_head_gp(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
+                   int D, int F, const float* wl, const float* bl, int P_lin, float* out, long long ldo, const bf16_t* z, const float* zn,
+                   const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, long long ldm,
+                   float* var, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

@@ -1,7 +1,7 @@
 // Property heads on rows of embeddings (include/coati_screen.h): out = last(resnet(first(x))) for every row of a bf16 library, as one
 // kernel.  The library is read once, nothing but [N, P] floats is written, and no activation ever exists in memory.
 //
-// head_eval_kernel<F, WAVES, NP> is head_body<F, WAVES, NP, false> of head_dev.h, where the layout is described: the body is shared with the
+// head_eval_kernel<F, WAVES, NP> is head_body<F, WAVES, NP, HEAD_MODE_EVAL> of head_dev.h, where the layout is described: the body is shared with the
 // input-gradient kernel (guide.hip), which runs the same forward, instruction for instruction, before its backward.
 // No atomics, no workspace.
 #include "head_dev.h"
@@ -12,7 +12,8 @@ __global__ __launch_bounds__(64 * WAVES) void head_eval_kernel(const bf16_t* __r
                                                                const bf16_t* __restrict__ wr, const float* __restrict__ br, int D,
                                                                const float* __restrict__ wl, const float* __restrict__ bl, int P,
                                                                float* __restrict__ out, long long ldo) {
-  head_body<F, WAVES, NP, false>(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, out, ldo, nullptr, nullptr, nullptr, 0, nullptr, 0);
+  head_body<F, WAVES, NP, HEAD_MODE_EVAL>(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, out, ldo, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                                          HeadGpOps{});
 }
 
 template <int F, int WAVES, int NP>

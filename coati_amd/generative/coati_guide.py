@@ -57,6 +57,9 @@ def guided_ascent(start, head, weights=None, steps=100, lr=0.05, anchor=0.0, bum
     if start.dim() != 2 or not start.is_floating_point():
         raise ValueError(f"guided_ascent: start must be a float tensor [n, dim], got {tuple(start.shape)}")
     if value_and_grad is None:
+        if getattr(head, "has_input_gradient", True) is False:
+            raise TypeError(f"guided_ascent: a {type(head).__name__} has no gradient with respect to the embedding (uncertainty-aware ascent "
+                            "is not implemented); climb its extractor (head.extractor) or pass value_and_grad=")
         value_and_grad = head.value_and_grad
         start = start.to(head.device)
     start = start.detach()

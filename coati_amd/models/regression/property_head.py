@@ -295,8 +295,8 @@ def fit_property_head(dataset, x_field="emb_smiles", y_field="pic50", steps=1e5,
     the first int(test_frac * n) records are the test set.  Adam on the mean squared error for `steps` steps of shuffled batches.
 
     Returns (model, (Xs, Ys, None)): the test targets, the model's predictions on the test set, and None where basic_due returns
-    standard deviations.  What is NOT here: the GP head (inducing points, ELBO) with its predictive uncertainty, and spectral
-    normalisation of the feature extractor; both need gpytorch / due, which are not dependencies."""
+    standard deviations: fit_gp_head (gp_head.py) puts a GP head on this extractor and fills that slot.  What is NOT here: spectral
+    normalisation of the feature extractor."""
     np.random.seed(seed=random_seed)
     x = np.stack([np.asarray(r[x_field]) for r in dataset], 0)
     if isinstance(y_field, (list, tuple)):

@@ -217,28 +217,54 @@ class EmbeddingIndex:
                               _ptr(rows[lo:lo + n]), stream)
         return scores, rows
 
-    def property_scores(self, head):
-        """[N, P] f32: head (coati_amd.models.regression.PropertyHead, on the index's device) on every stored row -- one fused kernel
-        over the bf16 rows, removed rows included.  A cosine index stores unit rows, so the head must be one of unit inputs
-        (unit_input=True), and only then."""
+    def _check_head(self, head, what):
         if head.input_dim != self.dim:
-            raise ValueError(f"EmbeddingIndex.property_scores: the head's input_dim={head.input_dim}, the index's dim={self.dim}")
+            raise ValueError(f"EmbeddingIndex.{what}: the head's input_dim={head.input_dim}, the index's dim={self.dim}")
         if bool(head.unit_input) != (self.metric == "cosine"):
-            raise ValueError(f"EmbeddingIndex.property_scores: a head with unit_input={bool(head.unit_input)} on a {self.metric!r} index "
+            raise ValueError(f"EmbeddingIndex.{what}: a head with unit_input={bool(head.unit_input)} on a {self.metric!r} index "
                              "(cosine indices store unit rows, the others rows as given)")
+
+    def property_scores(self, head):
+        """[N, P] f32: head (coati_amd.models.regression.PropertyHead, or a GPHead: its mean; on the index's device) on every stored
+        row -- one fused kernel over the bf16 rows, removed rows included.  A cosine index stores unit rows, so the head must be one of
+        unit inputs (unit_input=True), and only then."""
+        self._check_head(head, "property_scores")
         return head.predict_rows(self.vectors)
 
-    def screen(self, head, k, output=0, largest=True):
+    def property_uncertainty(self, head):
+        """(mean [N, P], std [N, P]) f32 of a coati_amd.models.regression.GPHead on every stored row: one fused kernel
+        (GPHead.predict_rows_with_std), under property_scores' rules."""
+        self._check_head(head, "property_uncertainty")
+        if not hasattr(head, "predict_rows_with_std"):
+            raise ValueError("EmbeddingIndex.property_uncertainty: the head gives no standard deviation (a GPHead does)")
+        return head.predict_rows_with_std(self.vectors)
+
+    def screen(self, head, k, output=0, largest=True, acquisition=None, beta=1.0, best=None):
         """(scores [k] f32, rows [k] int64): the k best live rows by the head's output `output` -- the largest values first (the smallest
         first for largest=False; the scores returned are the head's own values either way), row index ascending among equal values.
         Removed rows are never returned; fewer than k live rows: the tail is (-inf, -1).  The selection is one call of the search
-        kernel, so 1 <= k <= 128: for larger selections sort property_scores(head) yourself."""
+        kernel, so 1 <= k <= 128: for larger selections sort property_scores(head) yourself.
+
+        acquisition: None or "mean" rank by the head's value.  With a GPHead, "ucb" = mean + beta std, "lcb" = mean - beta std and "ei" =
+        the expected improvement over `best` (regression.acquisition_values) rank by that value, computed in torch from the GP kernel's
+        two outputs; the scores returned are the acquisition values."""
         k, output = int(k), int(output)
         if k < 1 or k > K_MAX:
             raise ValueError(f"EmbeddingIndex.screen: k={k} outside 1 .. {K_MAX} (for more, sort property_scores)")
         if output < 0 or output >= head.num_outputs:
             raise ValueError(f"EmbeddingIndex.screen: output={output} outside 0 .. {head.num_outputs - 1}")
-        values = self.property_scores(head)[:, output]
+        if acquisition not in (None, "mean"):
+            from .models.regression.gp_head import ACQUISITIONS, acquisition_values
+            if acquisition not in ACQUISITIONS:
+                raise ValueError(f"EmbeddingIndex.screen: acquisition={acquisition!r} is not one of {ACQUISITIONS}")
+            if not hasattr(head, "predict_rows_with_std"):
+                raise ValueError(f"EmbeddingIndex.screen: acquisition={acquisition!r} needs a head with a standard deviation (a GPHead)")
+            if acquisition == "ei" and best is None:
+                raise ValueError("EmbeddingIndex.screen: acquisition='ei' needs best=, the value to improve on")
+            mean, std = self.property_uncertainty(head)
+            values = acquisition_values(mean[:, output], std[:, output], acquisition, beta, best).to(torch.float32).contiguous()
+        else:
+            values = self.property_scores(head)[:, output]
         if self._n == 0:
             return (torch.full((k,), float("-inf"), dtype=torch.float32, device=self.device),
                     torch.full((k,), -1, dtype=torch.int64, device=self.device))
