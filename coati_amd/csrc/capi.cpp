@@ -9,6 +9,7 @@
 #include "../../include/coati_guide.h"
 #include "../../include/coati_ln_xhat.h"
 #include "../../include/coati_gp.h"
+#include "../../include/coati_acq.h"
 #include <vector>
 #include "kernels.h"
 
@@ -343,6 +344,15 @@ int coati_head_gp(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16
                   float* var, void* stream) {
   return launch_head_gp(x, ldx, N, E, w0, b0, wr, br, D, F, wl, bl, P_lin, out, ldo, z, zn, alpha, q, c, inv2l2, s2, P, Mp, mean, ldm, var,
                         S_(stream));
+}
+// the gradient of a GP acquisition with respect to the input rows (include/coati_acq.h)
+int coati_head_gp_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr,
+                       const float* br, int D, int F, const uint16_t* w0t, const uint16_t* wrt, const uint16_t* z, const uint16_t* zt,
+                       const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
+                       const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, int64_t ldm,
+                       float* var, float* acq, float* g, int64_t ldg, void* stream) {
+  return launch_head_gp_grad(x, ldx, N, E, w0, b0, wr, br, D, F, w0t, wrt, z, zt, zn, alpha, qs, c, inv2l2, s2, P, Mp, wm, kappa, var_add, mode,
+                             best, rs, mean, ldm, var, acq, g, ldg, S_(stream));
 }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,

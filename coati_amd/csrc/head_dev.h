@@ -1,5 +1,5 @@
-// The property head's device body, shared by head_eval_kernel (screen.hip), head_grad_kernel (guide.hip) and head_gp_kernel (gp.hip): one
-// text, three kernels.
+// The property head's device body, shared by head_eval_kernel (screen.hip), head_grad_kernel (guide.hip), head_gp_kernel (gp.hip) and
+// head_gp_grad_kernel (gp_grad.hip): one text, four kernels.
 //
 // head_body<F, WAVES, NP, MODE>, one workgroup per tile of WAVES * NP * 32 rows; a wave owns NP panels of 32 rows for the whole kernel:
 //  * every product is computed TRANSPOSED on v_mfma_f32_32x32x16_bf16: the weights are the M side (32 output features x 16 inputs, read
@@ -34,6 +34,15 @@
 // tt holds k_j, j = 32 tt + 8 (r >> 2) + 4 hh + (r & 3): register for register the B operand (k index = hh) of a v_mfma_f32_32x32x2_f32
 // step against q[m][j0 + 4 hh] read from LDS, so w = q k comes out in k's own map without lane movement and without leaving f32.  mean and
 // k . w are per-lane dots plus half_xchg_sum, like the last layer.  One more barrier (q in LDS), the same for every thread.
+//
+// MODE = HEAD_MODE_GPGRAD joins the two (include/coati_acq.h): the forward with mask words, the GP tail, an acquisition a(mean, var) of the
+// row, and the gradient of a with respect to the row.  The tail keeps w = qs k (qs the symmetric part of q, so dvar / dk = -2 w) next to
+// k; t_j = rs (A ca_j - 2 B w_j) k_j (ca = wm . alpha; A, B: the row's da / d(wm . mean) and da / dvar) takes k's registers and is, rounded
+// to bf16, the B operand of one more chained product: against zt [F, Mp] (z transposed), staged like a first-layer chunk (F rows x Mp <=
+// 64 columns at row stride 72) with the middle-group swap.  dphi = 2 inv2l2 (tb . zt - phi S), S the row's sum of tb (per-lane sum plus
+// half_xchg_sum), phi unpacked from the operand registers of the z product, lands in the registers of h and seeds the backward loop of
+// HEAD_MODE_GRAD.  qs has a region of its own in the dynamic LDS (between the weight buffers and the mask words): the buffer q uses in
+// HEAD_MODE_GP is the prefetch target of the zt chunk here.  The chunk sequence is C0 + D MCH + 1 + 1 + D MCH + ceil(E / MC).
 #pragma once
 #include "kernels.h"
 
@@ -63,10 +72,18 @@ constexpr size_t head_grad_lds_bytes(int D) {
 #define HEAD_MODE_EVAL 0
 #define HEAD_MODE_GRAD 1
 #define HEAD_MODE_GP 2
+#define HEAD_MODE_GPGRAD 3
 #define HEAD_GP_M_MAX 64   // inducing points (padded to 32 or 64)
 #define HEAD_GP_LDQ 68     // LDS row stride of q (floats): 32 rows' ds_read_b128 start on 8 different 16-byte slots
 
 typedef float head_f32x4 __attribute__((ext_vector_type(4)));
+
+// bytes of dynamic LDS of the GPGRAD body: the two weight buffers, qs, then D layers of mask words
+#define HEAD_GP_Q_BYTES (4 * HEAD_GP_M_MAX * HEAD_GP_LDQ)
+template <int F, int WAVES, int NP>
+constexpr size_t head_gpgrad_lds_bytes(int D) {
+  return head_grad_lds_bytes<F, WAVES, NP>(D) + HEAD_GP_Q_BYTES;
+}
 
 // the operands of the GP tail (HEAD_MODE_GP); the other modes pass an empty one
 struct HeadGpOps {
@@ -82,14 +99,26 @@ struct HeadGpOps {
   float* var;           // [N]
 };
 
+// what HEAD_MODE_GPGRAD needs on top of HeadGpOps (whose q then is qs, the symmetric part); the other modes pass an empty one
+struct HeadAcqOps {
+  const bf16_t* zt;     // [F, Mp]: z transposed
+  const float* wm;      // [P] weights on the means
+  float kappa, var_add, best;
+  int mode;             // 0: wm . mean + kappa sqrt(var + var_add);  1: expected improvement over best
+  const float* rs;      // [N] row scales of the gradient, or null
+  float* acq;           // [N]
+};
+
 template <int F, int WAVES, int NP, int MODE>
 __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long long ldx, long long N, int E, const bf16_t* __restrict__ w0,
                                           const float* __restrict__ b0, const bf16_t* __restrict__ wr, const float* __restrict__ br, int D,
                                           const float* __restrict__ wl, const float* __restrict__ bl, int P, float* __restrict__ out,
                                           long long ldo, const bf16_t* __restrict__ w0t, const bf16_t* __restrict__ wrt,
                                           const float* __restrict__ cot, long long ldc, float* __restrict__ g, long long ldg,
-                                          const HeadGpOps& gp) {
-  constexpr bool GRAD = MODE == HEAD_MODE_GRAD, GP = MODE == HEAD_MODE_GP;
+                                          const HeadGpOps& gp, const HeadAcqOps& aq = HeadAcqOps{}) {
+  constexpr bool GRAD = MODE == HEAD_MODE_GRAD, GP = MODE == HEAD_MODE_GP, GPG = MODE == HEAD_MODE_GPGRAD;
+  constexpr bool BACK = GRAD || GPG;   // mask words in the forward, dynamic LDS, the backward loop
+  constexpr int ZC = GPG ? 2 : 0;      // the z and zt chunks between the forward's and the backward's
   constexpr int NT = 64 * WAVES, MT = F / 32, KS = F / 16;
   constexpr int MC = HEAD_CHUNK / F < F ? HEAD_CHUNK / F : F;   // output features per residual chunk: 64 (F = 256), 128, 64
   constexpr int MCH = F / MC, TPC = MC / 32;                    // chunks per residual layer, 32-feature tiles per chunk
@@ -98,11 +127,13 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
   constexpr int U0 = F * HEAD_KC / 16, UR = MC * F / 16;        // 32-byte units of a chunk
   constexpr int UPT = ((U0 > UR ? U0 : UR) + NT - 1) / NT;
   bf16_t* lds;                                                  // [2][BUF]
-  unsigned short* masks = nullptr;                              // GRAD: [D][MT][NP][NT]
-  if constexpr (GRAD) {
+  unsigned short* masks = nullptr;                              // GRAD, GPGRAD: [D][MT][NP][NT]
+  float* qown = nullptr;                                        // GPGRAD: qs [HEAD_GP_M_MAX][HEAD_GP_LDQ]
+  if constexpr (BACK) {
     extern __shared__ __attribute__((aligned(16))) unsigned char head_smem[];
     lds = reinterpret_cast<bf16_t*>(head_smem);
-    masks = reinterpret_cast<unsigned short*>(head_smem + 4 * BUF);
+    if constexpr (GPG) qown = reinterpret_cast<float*>(head_smem + 4 * BUF);
+    masks = reinterpret_cast<unsigned short*>(head_smem + 4 * BUF + (GPG ? HEAD_GP_Q_BYTES : 0));
   } else {
     __shared__ __attribute__((aligned(16))) bf16_t head_lds[2 * BUF];
     lds = head_lds;
@@ -110,7 +141,7 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hh = lane >> 5;
   const int C0 = (E + HEAD_KC - 1) / HEAD_KC;
-  const int CT = GRAD ? C0 + 2 * D * MCH + (E + MC - 1) / MC : C0 + D * MCH + (GP ? 1 : 0);
+  const int CT = BACK ? C0 + 2 * D * MCH + ZC + (E + MC - 1) / MC : C0 + D * MCH + (GP ? 1 : 0);
   const long long row0 = (long long)blockIdx.x * (WAVES * NP * 32) + wave * (NP * 32);
 
   // chunk gc of the sequence: global -> st (stage_load), st -> lds[gc & 1] (stage_store)
@@ -128,15 +159,15 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
         const int cc = gc - C0;
         on = u < UR;
         src = wr + ((long long)(cc / MCH) * F + (cc % MCH) * MC + u / KS) * F + 16 * (u % KS);
-      } else if (GP) {                      // z [Mp, F], one chunk (Mp <= 64 <= MC): its rows, none past Mp
+      } else if (GP || (GPG && gc - C0 == D * MCH)) {   // z [Mp, F], one chunk (Mp <= 64 <= MC): its rows, none past Mp
         on = u < UR && u / KS < gp.Mp;
         src = gp.z + (long long)(u / KS) * F + 16 * (u % KS);
-      } else if (gc - C0 < 2 * D * MCH) {   // backward layer D - 1 - cc / MCH: the same chunks of the transposed weights
-        const int cc = gc - C0 - D * MCH;
+      } else if (gc - C0 - ZC < 2 * D * MCH) {   // backward layer D - 1 - cc / MCH: the same chunks of the transposed weights
+        const int cc = gc - C0 - D * MCH - ZC;
         on = u < UR;
         src = wrt + ((long long)(D - 1 - cc / MCH) * F + (cc % MCH) * MC + u / KS) * F + 16 * (u % KS);
       } else {                              // w0t [E, F]: MC of its rows, none past E
-        const int cc = gc - C0 - 2 * D * MCH;
+        const int cc = gc - C0 - 2 * D * MCH - ZC;
         on = u < UR && cc * MC + u / KS < E;
         src = w0t + ((long long)cc * MC + u / KS) * F + 16 * (u % KS);
       }
@@ -160,6 +191,32 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
         }
       } else if (u < UR) {   // groups of 4 elements (g0 g1 | g2 g3) -> (g0 g2 | g1 g3): the k order of the chained operand
         uint4* d = reinterpret_cast<uint4*>(buf + (u / KS) * LDR + 16 * (u % KS));   // (rows of w0t past E: stale registers, never read)
+        d[0] = make_uint4(a.x, a.y, b.x, b.y);
+        d[1] = make_uint4(a.z, a.w, b.z, b.w);
+      }
+    }
+  };
+
+  // GPGRAD: the zt chunk [F, Mp]: a first-layer chunk's layout (F rows, 16-column units, none past Mp), a residual chunk's group swap
+  auto stage_load_zt = [&]() {
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+      const int u = tid + NT * i;
+      if (u < U0 && 16 * (u & 3) < gp.Mp) {
+        const bf16_t* src = aq.zt + (long long)(u >> 2) * gp.Mp + 16 * (u & 3);
+        st[i][0] = reinterpret_cast<const uint4*>(src)[0];
+        st[i][1] = reinterpret_cast<const uint4*>(src)[1];
+      }
+    }
+  };
+  auto stage_store_zt = [&](int gc) {
+    bf16_t* buf = lds + (gc & 1) * BUF;
+#pragma unroll
+    for (int i = 0; i < UPT; ++i) {
+      const int u = tid + NT * i;
+      const uint4 a = st[i][0], b = st[i][1];
+      if (u < U0 && 16 * (u & 3) < gp.Mp) {
+        uint4* d = reinterpret_cast<uint4*>(buf + (u >> 2) * LD0 + 16 * (u & 3));
         d[0] = make_uint4(a.x, a.y, b.x, b.y);
         d[1] = make_uint4(a.z, a.w, b.z, b.w);
       }
@@ -287,7 +344,7 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
         for (int p = 0; p < NP; ++p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) h[mt][p][r] += fmaxf(acc[p][r], 0.f);
-          if constexpr (GRAD) {   // the tile's ReLU decisions, bit r = register r
+          if constexpr (BACK) {   // the tile's ReLU decisions, bit r = register r
             unsigned m = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) m |= (acc[p][r] > 0.f ? 1u : 0u) << r;
@@ -328,7 +385,7 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
     }
   }
 
-  if constexpr (GP) {
+  if constexpr (GP || GPG) {
     // phi = rb(h) is the operand of one more chained product, against z: its chunk (number gc) came in under the last residual chunk.
     // |phi|^2 is summed over the rounded values the lane holds, then over the two half-waves
     const int Mp = gp.Mp;
@@ -360,7 +417,10 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
     constexpr int QPT = HEAD_GP_M_MAX * HEAD_GP_M_MAX / 4 / NT;
     constexpr bool QOWN = 2 * BUF < 4 * HEAD_GP_M_MAX * HEAD_GP_LDQ;
     float* qs;
-    if constexpr (QOWN) {
+    if constexpr (GPG) {   // (that buffer is where the zt chunk goes: qs has a region of the dynamic LDS)
+      qs = qown;
+      stage_load_zt();
+    } else if constexpr (QOWN) {
       __shared__ __attribute__((aligned(16))) float head_q[HEAD_GP_M_MAX * HEAD_GP_LDQ];
       qs = head_q;
     } else {
@@ -418,8 +478,12 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
       const int u = tid + NT * i;
       if (u < QU) *reinterpret_cast<head_f32x4*>(qs + ((4 * u) / Mp) * HEAD_GP_LDQ + (4 * u) % Mp) = qv[i];
     }
+    if constexpr (GPG) stage_store_zt(gc + 1);
 
     // mean: the lane's k against alpha, then the other half-wave's (like the last layer)
+    float am[NP];   // GPGRAD: wm . mean of the row
+#pragma unroll
+    for (int p = 0; p < NP; ++p) am[p] = 0.f;
     for (int o = 0; o < gp.P; ++o) {
       float sum[NP];
 #pragma unroll
@@ -446,14 +510,20 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
         const float tot = half_xchg_sum(sum[p]) + co;
         const long long row = row0 + 32 * p + n;
         if (hh == 0 && row < N) gp.mean[row * gp.ldm + o] = tot;
+        if constexpr (GPG) am[p] = fmaf(aq.wm[o], tot, am[p]);
       }
     }
-    __syncthreads();   // q is in LDS
+    __syncthreads();   // q is in LDS (GPGRAD: and the zt chunk)
+    if constexpr (GPG) {   // the zt chunk is the current one; the backward's first chunk travels under the rest of the tail
+      ++gc;
+      stage_load(gc + 1, false);
+    }
 
     // w = q k on v_mfma_f32_32x32x2_f32, all f32: register r of k's tile tt is the B operand (k index = hh) of the step against
     // q[32 mi + n][32 tt + 8 (r >> 2) + 4 hh + (r & 3)], and w comes out in k's own map; var = s2 - k . w
     const float* qa = qs + n * HEAD_GP_LDQ + 4 * hh;
     float quad[NP];
+    f32x16 wk[GPG ? HEAD_GP_M_MAX / 32 : 1][NP];   // GPGRAD keeps w, in k's map
 #pragma unroll
     for (int p = 0; p < NP; ++p) quad[p] = 0.f;
 #pragma unroll
@@ -483,12 +553,126 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
         for (int p = 0; p < NP; ++p)
 #pragma unroll
           for (int r = 0; r < 16; ++r) quad[p] = fmaf(kk[mi][p][r], w[p][r], quad[p]);
+        if constexpr (GPG) {
+#pragma unroll
+          for (int p = 0; p < NP; ++p) wk[mi][p] = w[p];
+        }
       }
+    float cA[NP], cB[NP];   // GPGRAD: rs A and -2 rs B of the row
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const float v = fmaxf(gp.s2 - half_xchg_sum(quad[p]), 0.f);
       const long long row = row0 + 32 * p + n;
       if (hh == 0 && row < N) gp.var[row] = v;
+      if constexpr (GPG) {
+        // the acquisition a and its derivatives A = da / d(wm . mean), B = da / dvar.  B = 0 where var was clamped or has no digits left
+        const float va = v + aq.var_add, sd = sqrtf(va);
+        const bool dead = !(v > 0.f) || !(va > 1e-6f * gp.s2);
+        const float hb = dead ? 0.f : aq.kappa / (2.f * sd);
+        float a, A, B;
+        if (aq.mode == 0) {
+          a = fmaf(aq.kappa, sd, am[p]);
+          A = 1.f;
+          B = hb;
+        } else {
+          const float mu = am[p] - aq.best, s = aq.kappa * sd;
+          if (s > 0.f) {
+            const float u = mu / s;
+            const float Phi = 0.5f * (1.f + erff(u * 0.70710678118654752f));
+            const float ph = 0.39894228040143268f * expf(-0.5f * u * u);
+            a = fmaf(mu, Phi, s * ph);
+            A = Phi;
+            B = ph * hb;
+          } else {
+            a = fmaxf(mu, 0.f);
+            A = mu > 0.f ? 1.f : 0.f;
+            B = 0.f;
+          }
+        }
+        if (hh == 0 && row < N) aq.acq[row] = a;
+        const float r = aq.rs ? aq.rs[min(row, N - 1)] : 1.f;
+        cA[p] = r * A;
+        cB[p] = -2.f * r * B;
+      }
+    }
+
+    if constexpr (GPG) {
+      // t_j = (cA ca_j + cB w_j) k_j in k's registers, ca = wm . alpha; tb = rb(t) is the B operand of the zt product (k-step 2 tt + t =
+      // registers 8 t .. 8 t + 7 of tile tt, like any chained operand); S = sum_j tb_j over the rounded values
+      bf16x8 tbf[NP][HEAD_GP_M_MAX / 16];
+      float S[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) S[p] = 0.f;
+#pragma unroll
+      for (int tt = 0; tt < HEAD_GP_M_MAX / 32; ++tt) {
+        if (32 * tt < Mp) {   // (the same for every thread)
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            float ca[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int o = 0; o < gp.P; ++o) {
+              const float wo = aq.wm[o];
+              const float4 av = *reinterpret_cast<const float4*>(gp.alpha + (long long)o * Mp + 32 * tt + 8 * q4 + 4 * hh);
+              ca[0] = fmaf(wo, av.x, ca[0]);
+              ca[1] = fmaf(wo, av.y, ca[1]);
+              ca[2] = fmaf(wo, av.z, ca[2]);
+              ca[3] = fmaf(wo, av.w, ca[3]);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                kk[tt][p][4 * q4 + e] = fmaf(cB[p], wk[tt][p][4 * q4 + e], cA[p] * ca[e]) * kk[tt][p][4 * q4 + e];
+          }
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            uint4 v;
+            v.x = pack2bf(kk[tt][p][8 * t], kk[tt][p][8 * t + 1]);
+            v.y = pack2bf(kk[tt][p][8 * t + 2], kk[tt][p][8 * t + 3]);
+            v.z = pack2bf(kk[tt][p][8 * t + 4], kk[tt][p][8 * t + 5]);
+            v.w = pack2bf(kk[tt][p][8 * t + 6], kk[tt][p][8 * t + 7]);
+            tbf[p][2 * tt + t] = __builtin_bit_cast(bf16x8, v);
+            float f[8];
+            unpack8(v, f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) S[p] += f[e];
+          }
+      }
+#pragma unroll
+      for (int p = 0; p < NP; ++p) S[p] = half_xchg_sum(S[p]);
+
+      // dphi = 2 inv2l2 (tb . zt - phi S) into the registers of h: F output features, K = Mp, the chunk staged at row stride LD0
+      const float c2 = 2.f * gp.inv2l2;
+      const bf16_t* a = lds + (gc & 1) * BUF + n * LD0 + 8 * hh;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        f32x16 acc[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < HEAD_GP_M_MAX / 16; ++s)
+          if (16 * s < Mp) {   // (the same for every thread)
+            const bf16x8 af = *reinterpret_cast<const bf16x8*>(a + 32 * mt * LD0 + 16 * s);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tbf[p][s], acc[p], 0, 0, 0);
+          }
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            float f[8];
+            unpack8(__builtin_bit_cast(uint4, bfr[p][2 * mt + t]), f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[mt][p][8 * t + e] = c2 * fmaf(-f[e], S[p], acc[p][8 * t + e]);
+          }
+      }
+      stage_store(gc + 1, false);
+      __syncthreads();
+      ++gc;
     }
   }
 
@@ -522,7 +706,9 @@ __device__ __forceinline__ void head_body(const bf16_t* __restrict__ x, long lon
           }
         }
     }
+  }
 
+  if constexpr (BACK) {
     // backward layers D - 1 .. 0 (masked operand, d += acc), then rb(d) . w0 as one more layer whose tiles go to memory
     for (int b = 0; b <= D; ++b) {
       const bool lastp = b == D;

@@ -391,6 +391,13 @@ int launch_head_gp(const bf16_t* x, long long ldx, long long N, int E, const bf1
                    int D, int F, const float* wl, const float* bl, int P_lin, float* out, long long ldo, const bf16_t* z, const float* zn,
                    const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, long long ldm,
                    float* var, hipStream_t s);
+// the gradient of a GP acquisition with respect to the input rows (gp_grad.hip, include/coati_acq.h): launch_head_gp's mean and var, acq [N]
+// = a(wm . mean, var) and g [N, E] = rs * d acq / dx; qs is the symmetric part of q, zt [F, Mp] is z transposed
+int launch_head_gp_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr,
+                        const float* br, int D, int F, const bf16_t* w0t, const bf16_t* wrt, const bf16_t* z, const bf16_t* zt,
+                        const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
+                        const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, long long ldm,
+                        float* var, float* acq, float* g, long long ldg, hipStream_t s);
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

@@ -3,7 +3,12 @@ pushed out of visited places by Gaussian hills (the "metadynamics" use the refer
 reference checkout, so the optimiser is this project's own and is pinned by the float64 restatement in tests/test_guide_cpu.py).
 
 The property term and its gradient come from one kernel call per step for all trajectories together (PropertyHead.value_and_grad:
-coati_head_grad, include/coati_guide.h); the anchor and hill terms are plain torch."""
+coati_head_grad, include/coati_guide.h); the anchor and hill terms are plain torch.
+
+A GPHead has P means and one shared variance and no gradient of its own; its acquisition (mean, ucb, lcb or expected improvement of one
+output: GPHead.acquisition, one coati_head_gp_grad call per step, include/coati_acq.h) is an objective this loop takes as it takes a head:
+
+    guided_ascent(start, gp.acquisition("lcb", beta=2.0), steps=..., anchor=...)"""
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional
 

@@ -35,3 +35,25 @@ class HeadFused(torch.autograd.Function):
 
 def head_fused(x, head):
     return HeadFused.apply(x, head)
+
+
+class AcquisitionFused(torch.autograd.Function):
+    """values [n, 1] = objective.predict(x) for an AcquisitionObjective (models/regression/acquisition.py); the gradient reaches `x`
+    [n, input_dim] only.  backward is one coati_head_gp_grad call (objective.value_and_grad with grad_output as the row scale, the chain
+    of unit_input included); nothing is kept between the two calls but x."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, objective):
+        ctx.objective = objective
+        ctx.save_for_backward(x)
+        return objective.predict(x)
+
+    @staticmethod
+    def backward(ctx, grad_output: torch.Tensor):
+        (x,) = ctx.saved_tensors
+        _, g = ctx.objective.value_and_grad(x, grad_output)
+        return g.to(device=x.device, dtype=x.dtype).reshape(x.shape), None
+
+
+def acquisition_fused(x, objective):
+    return AcquisitionFused.apply(x, objective)

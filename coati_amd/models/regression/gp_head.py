@@ -217,8 +217,15 @@ class GPHead(torch.nn.Module):
                 alpha = torch.nn.functional.pad(alpha.float(), (0, Mp - M)).contiguous()
                 q = torch.nn.functional.pad(self.q.float(), (0, Mp - M, 0, Mp - M)).contiguous()
                 c = c.float().contiguous()
-            self._gp_packed = (key, (z, zn, alpha, q, c, Mp))
+                zt = z.T.contiguous()                                        # the acquisition gradient's operands: z transposed [F, Mp] and
+                qs = torch.nn.functional.pad((0.5 * (self.q.double() + self.q.double().T)).float(), (0, Mp - M, 0, Mp - M)).contiguous()
+            self._gp_packed = (key, (z, zn, alpha, q, c, Mp), (zt, qs))     # the symmetric part of q, formed in float64
         return self._gp_packed[1]
+
+    def _gp_grad_operands(self):
+        """(zt [F, Mp] bf16, qs [Mp, Mp] f32): z transposed and the symmetric part of q, packed with _gp_operands() under the same cache key"""
+        self._gp_operands()
+        return self._gp_packed[2]
 
     def gp_rows(self, x16, linear=False):
         """(mean [n, P], var [n]) f32 of prepared rows, one launch of coati_head_gp; linear=True: (mean, var, out) with out [n, P_lin] the
@@ -261,6 +268,132 @@ class GPHead(torch.nn.Module):
     def predict_with_std(self, vectors, include_noise=False):
         with torch.no_grad():
             return self.predict_rows_with_std(self.prepare(vectors), include_noise)
+
+    # ---- acquisitions and their gradient with respect to the rows -----------------------------------------------------------------------
+    def reference_acq_grad(self, x16, wm, kappa, var_add=0.0, mode=0, best=0.0, row_scale=None, dtype=torch.float64, round_fn=None,
+                           f32_operands=True):
+        """(mean [n, P], var [n], acq [n], g [n, width of x16]) of coati_head_gp_grad (include/coati_acq.h) on prepared bf16 rows, computed in
+        `dtype` with the kernel's rounding points: reference()'s forward with qs = (q + q^T) / 2 in place of q; the acquisition of mode 0
+        (wm . mean + kappa sqrt(var + var_add)) or 1 (expected improvement over `best`) with its derivatives A and B (B = 0 where var was
+        clamped or var + var_add <= 1e-6 s2); t = rs (A wm . alpha - 2 B w) k, tb = rb(t), S = sum tb, dphi = 2 inv2l2 (tb . z - phi S); the
+        rounding h -> phi passed straight through; then PropertyHead.reference_grad's backward from d = dphi.  round_fn (tensor -> tensor
+        of `dtype`) replaces rb, the rounding to bf16, everywhere: with a plain cast this is the exact gradient of the unrounded model.
+        f32_operands as in reference(), for wm and the four scalars too."""
+        ex = self.extractor
+        if x16.dtype != torch.bfloat16 or x16.dim() != 2 or x16.shape[1] not in (ex.input_dim, ex.input_dim_padded):
+            raise ValueError(f"GPHead.reference_acq_grad: rows must be bf16 [n, {ex.input_dim} or {ex.input_dim_padded}], "
+                             f"got {x16.dtype} {tuple(x16.shape)}")
+        if int(mode) not in (0, 1) or (int(mode) == 1 and not float(kappa) > 0):
+            raise ValueError(f"GPHead.reference_acq_grad: mode={mode} must be 0 or 1, and kappa={kappa} positive with mode 1")
+
+        def rb(t):
+            return t.detach().to(torch.float32).to(torch.bfloat16).to(dtype)
+
+        rb = round_fn if round_fn is not None else rb
+        n = x16.shape[0]
+        with torch.no_grad():
+            w0 = rb(ex.first.weight)
+            wr = [rb(res.weight) for res in ex.residuals]
+            h = x16[:, :ex.input_dim].to(dtype) @ w0.T + ex.first.bias.to(dtype)
+            masks = []
+            for res, w in zip(ex.residuals, wr):
+                pre = rb(h) @ w.T + res.bias.to(dtype)
+                masks.append(pre > 0)
+                h = h + torch.relu(pre)
+            phi = rb(h)
+            # the operands padded to Mp = 32 or 64 inducing points as the kernel reads them: every sum over the points then has the kernel's
+            # terms, and a head that carries its padding explicitly (zero alpha, zero rows and columns of q, any z) gives the same bits
+            M = self.z.shape[0]
+            pad = (32 if M <= 32 else 64) - M
+            z = torch.nn.functional.pad(self.z.to(dtype), (0, 0, 0, pad))
+            alpha, c = self._folded()
+            alpha = torch.nn.functional.pad(alpha, (0, pad))
+            qs = torch.nn.functional.pad(0.5 * (self.q.double() + self.q.double().T), (0, pad, 0, pad))
+            zn = torch.nn.functional.pad((self.z.double() ** 2).sum(dim=1), (0, pad))
+            wm = torch.as_tensor(wm, dtype=torch.float64, device=alpha.device).reshape(-1)
+            if wm.shape[0] != self.num_outputs:
+                raise ValueError(f"GPHead.reference_acq_grad: wm must be [{self.num_outputs}], got {tuple(wm.shape)}")
+            inv2l2, s2 = 1.0 / (2.0 * self.lengthscale ** 2), self.signal_var
+            kappa, var_add, best = float(kappa), float(var_add), float(best)
+            if f32_operands:
+                alpha, c, qs, zn, wm = alpha.float(), c.float(), qs.float(), zn.float(), wm.float()
+                inv2l2, s2, kappa, var_add, best = (float(np.float32(v)) for v in (inv2l2, s2, kappa, var_add, best))
+            alpha, c, qs, zn, wm = alpha.to(dtype), c.to(dtype), qs.to(dtype), zn.to(dtype), wm.to(dtype)
+            d2 = ((phi * phi).sum(dim=1)[:, None] + zn[None, :] - 2.0 * (phi @ z.T)).clamp_min(0.0)
+            k = s2 * torch.exp(-d2 * inv2l2)
+            mean = c[None, :] + k @ alpha.T
+            w = k @ qs.T
+            var = (s2 - (w * k).sum(dim=1)).clamp_min(0.0)
+            m = mean @ wm
+            va = var + var_add
+            sd = va.sqrt()
+            dead = (var <= 0) | (va <= 1e-6 * s2)
+            hb = torch.where(dead, torch.zeros_like(sd), kappa / (2.0 * torch.where(dead, torch.ones_like(sd), sd)))
+            if int(mode) == 0:
+                acq, A, B = m + kappa * sd, torch.ones_like(m), hb
+            else:
+                mu, s = m - best, kappa * sd
+                pos = s > 0
+                u = mu / torch.where(pos, s, torch.ones_like(s))
+                Phi = 0.5 * (1.0 + torch.erf(u / math.sqrt(2.0)))
+                ph = torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
+                acq = torch.where(pos, mu * Phi + s * ph, mu.clamp_min(0.0))
+                A = torch.where(pos, Phi, (mu > 0).to(dtype))
+                B = torch.where(pos, ph * hb, torch.zeros_like(hb))
+            rs = torch.ones(n, dtype=dtype, device=k.device) if row_scale is None else torch.as_tensor(row_scale).detach().to(k).reshape(n)
+            ca = wm @ alpha
+            tb = rb(rs[:, None] * (A[:, None] * ca[None, :] - 2.0 * B[:, None] * w) * k)
+            S = tb.sum(dim=1)
+            d = 2.0 * inv2l2 * (tb @ z - phi * S[:, None])
+            for msk, wl in zip(reversed(masks), reversed(wr)):
+                d = d + rb(torch.where(msk, d, torch.zeros_like(d))) @ wl
+            g = rb(d) @ w0
+            return mean, var, acq, torch.nn.functional.pad(g, (0, x16.shape[1] - ex.input_dim))
+
+    def acq_rows(self, x16, wm, kappa, var_add=0.0, mode=0, best=0.0, row_scale=None):
+        """(mean [n, P], var [n], acq [n], g [n, input_dim_padded]) f32 of prepared rows, one launch of coati_head_gp_grad: mean as gp_rows
+        gives it, bit for bit, acq the acquisition (reference_acq_grad names the two modes) and g the gradient of row_scale * acq with respect
+        to the rows as the kernel reads them.  x16 under PropertyHead.predict_rows' stride rules; wm [P] weights on the means; row_scale
+        [n] or None.  There is no CPU fallback."""
+        ex = self.extractor
+        x16, ldx = ex._kernel_rows(x16, "acq_rows")
+        n, E, P = x16.shape[0], ex.input_dim_padded, self.num_outputs
+        wm = torch.as_tensor(wm).detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        if wm.shape[0] != P:
+            raise ValueError(f"GPHead.acq_rows: wm must be [{P}], got {tuple(wm.shape)}")
+        if int(mode) not in (0, 1) or (int(mode) == 1 and not float(kappa) > 0):
+            raise ValueError(f"GPHead.acq_rows: mode={mode} must be 0 or 1, and kappa={kappa} positive with mode 1")
+        if row_scale is not None:
+            if not isinstance(row_scale, torch.Tensor) or row_scale.numel() != n:
+                raise ValueError(f"GPHead.acq_rows: row_scale must be a tensor of {n} elements")
+            if row_scale.device != self.device:
+                raise ValueError(f"GPHead.acq_rows: row_scale on {row_scale.device}, the head on {self.device}")
+            row_scale = row_scale.detach().to(torch.float32).reshape(n).contiguous()
+        mean = torch.empty(n, P, dtype=torch.float32, device=self.device)
+        var = torch.empty(n, dtype=torch.float32, device=self.device)
+        acq = torch.empty(n, dtype=torch.float32, device=self.device)
+        g = torch.empty(n, E, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return mean, var, acq, g
+        if self.device.type != "cuda":
+            raise RuntimeError("GPHead.acq_rows: the head is not on a GPU; there is no CPU fallback (reference_acq_grad() is plain torch)")
+        w0, b0, wr, br, _, _ = ex._operands()
+        w0t, wrt = ex._grad_operands()
+        z, zn, alpha, _, c, Mp = self._gp_operands()
+        zt, qs = self._gp_grad_operands()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.call("coati_head_gp_grad", _ptr(x16), ldx, n, E, _ptr(w0), _ptr(b0), _ptr(wr), _ptr(br), ex.depth, ex.features, _ptr(w0t),
+                      _ptr(wrt), _ptr(z), _ptr(zt), _ptr(zn), _ptr(alpha), _ptr(qs), _ptr(c), 1.0 / (2.0 * self.lengthscale ** 2),
+                      self.signal_var, P, Mp, _ptr(wm), float(kappa), float(var_add), int(mode), float(best), _ptr(row_scale), _ptr(mean), P,
+                      _ptr(var), _ptr(acq), _ptr(g), E, stream)
+        return mean, var, acq, g
+
+    def acquisition(self, kind="ucb", beta=1.0, best=None, output=0, include_noise=False):
+        """An AcquisitionObjective (acquisition.py) on this head: the scalar that guided_ascent, guided_generation and torch autograd climb.
+        guided_ascent(start, gp.acquisition("lcb", beta=2.0), steps=..., anchor=...)"""
+        from .acquisition import AcquisitionObjective
+        return AcquisitionObjective(self, kind=kind, beta=beta, best=best, output=output, include_noise=include_noise)
 
     def value_and_grad(self, vectors, cotangent=None):
         raise NotImplementedError("GPHead.value_and_grad: the gradient of the GP's mean or std with respect to the embedding is not "
