@@ -10,6 +10,7 @@
 #include "../../include/coati_ln_xhat.h"
 #include "../../include/coati_gp.h"
 #include "../../include/coati_acq.h"
+#include "../../include/coati_cluster.h"
 #include <vector>
 #include "kernels.h"
 
@@ -354,6 +355,17 @@ int coati_head_gp_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const u
   return launch_head_gp_grad(x, ldx, N, E, w0, b0, wr, br, D, F, w0t, wrt, z, zt, zn, alpha, qs, c, inv2l2, s2, P, Mp, wm, kappa, var_add, mode,
                              best, rs, mean, ldm, var, acq, g, ldg, S_(stream));
 }
+// library clustering (include/coati_cluster.h)
+int coati_cluster_assign(const uint16_t* lib, int64_t N, int E, const float* row_bias, const uint16_t* c, int K, const float* cbias,
+                         int32_t* assign, float* best, int blocks, void* stream) {
+  return launch_cluster_assign(lib, N, E, row_bias, c, K, cbias, assign, best, blocks, S_(stream));
+}
+int coati_cluster_sums(const uint16_t* lib, int64_t N, int E, const int32_t* order, int64_t M, const int32_t* offsets,
+                       const int32_t* item_off, int K, float* part, int64_t items_max, float* sums, int blocks, void* stream) {
+  return launch_cluster_sums(lib, N, E, order, M, offsets, item_off, K, part, items_max, sums, blocks, S_(stream));
+}
+int coati_cluster_chunk(void) { return cluster_chunk(); }
+int64_t coati_cluster_items_max(int64_t M, int K) { return cluster_items_max(M, K); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

@@ -398,6 +398,15 @@ int launch_head_gp_grad(const bf16_t* x, long long ldx, long long N, int E, cons
                         const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
                         const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, long long ldm,
                         float* var, float* acq, float* g, long long ldg, hipStream_t s);
+// library clustering (cluster.hip, include/coati_cluster.h): assign[n] = the centre of c [K, E] with the largest dot + cbias (lowest k among
+// equal scores; -1 where row_bias is -inf), best[n] = that score; sums [K, E] = the per-cluster sums of the rows listed in order / offsets,
+// through part [items_max, E] in chunks of cluster_chunk() rows.  blocks = 0: the default grid; no result depends on it
+int launch_cluster_assign(const bf16_t* lib, long long N, int E, const float* row_bias, const bf16_t* c, int K, const float* cbias, int* assign,
+                          float* best, int blocks, hipStream_t s);
+int launch_cluster_sums(const bf16_t* lib, long long N, int E, const int* order, long long M, const int* offsets, const int* item_off, int K,
+                        float* part, long long items_max, float* sums, int blocks, hipStream_t s);
+int cluster_chunk(void);                           // host only
+long long cluster_items_max(long long M, int K);   // host only
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

@@ -276,6 +276,42 @@ class EmbeddingIndex:
         scores = torch.where(rows >= 0, values[rows.clamp_min(0)], torch.full((k,), float("-inf"), dtype=torch.float32, device=self.device))
         return scores, rows
 
+    def _cluster_operands(self, what, rows=None):
+        """(x16, row_bias, rows) for coati_amd.cluster: the stored rows and their bias (-inf = removed), or a gathered subset of them"""
+        from .cluster import _check_metric as check_cluster_metric
+        check_cluster_metric(self.metric)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"EmbeddingIndex.{what}: the index is not on a GPU; there is no CPU fallback")
+        if rows is None:
+            return self.vectors, self.bias, None
+        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1).to(self.device)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self._n):
+            raise IndexError(f"EmbeddingIndex.{what}: rows outside 0 .. {self._n - 1}")
+        return self.vectors[rows].contiguous(), self.bias[rows].contiguous(), rows
+
+    def assign(self, centres):
+        """(assign [N] int32, score [N] f32): every stored row's nearest of centres [K, dim] (K <= 4096) under the index's metric ("cosine"
+        or "l2"; "dot" raises ValueError), the lowest index among equally near ones, and the cosine / negated squared distance to it.
+        A removed row gets (-1, -inf).  One streaming kernel (coati_amd.cluster.assign_rows); no [N, K] scores exist."""
+        from . import cluster
+        x16, bias, _ = self._cluster_operands("assign")
+        centres = torch.as_tensor(centres)
+        if centres.dim() != 2 or centres.shape[1] != self.dim:
+            raise ValueError(f"EmbeddingIndex.assign: centres must be [K, {self.dim}], got {tuple(centres.shape)}")
+        return cluster.assign_rows(x16, bias, centres, self.metric)
+
+    def kmeans(self, k, iters=20, seed=0, init=None, rows=None):
+        """A coati_amd.cluster.Clustering of the live rows into k clusters (spherical k-means on a "cosine" index, plain k-means on an "l2"
+        one), reproducible bit for bit from `seed`.  init: a [k, dim] tensor instead of k seeded rows.  rows: cluster this subset only (a
+        gathered temporary); the Clustering then carries it as .rows and answers members() / representatives() in library rows."""
+        from . import cluster
+        x16, bias, rows = self._cluster_operands("kmeans", rows)
+        if init is not None and (torch.as_tensor(init).dim() != 2 or torch.as_tensor(init).shape[1] != self.dim):
+            raise ValueError(f"EmbeddingIndex.kmeans: init must be [{int(k)}, {self.dim}]")
+        out = cluster.kmeans_rows(x16, bias, self.metric, k, iters, seed, init, dim=self.dim)
+        out.rows = rows
+        return out
+
     def _rescore(self, q32, scores, rows, k):
         """the candidates' scores from the f32 copies (a gather and a bmm over [Q, m k, E]), re-sorted: score descending, row ascending"""
         pad = rows < 0
