@@ -11,6 +11,7 @@
 #include "../../include/coati_gp.h"
 #include "../../include/coati_acq.h"
 #include "../../include/coati_cluster.h"
+#include "../../include/coati_ivf.h"
 #include <vector>
 #include "kernels.h"
 
@@ -366,6 +367,20 @@ int coati_cluster_sums(const uint16_t* lib, int64_t N, int E, const int32_t* ord
 }
 int coati_cluster_chunk(void) { return cluster_chunk(); }
 int64_t coati_cluster_items_max(int64_t M, int K) { return cluster_items_max(M, K); }
+// IVF approximate search (include/coati_ivf.h)
+int coati_ivf_scan(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                   const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P, int k,
+                   float alpha, int seg_rows, int segs, float* part_score, int32_t* part_row, int blocks, void* stream) {
+  return launch_ivf_scan(lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs, part_score, part_row,
+                         blocks, S_(stream));
+}
+int coati_ivf_merge(const float* part_score, const int32_t* part_row, const int32_t* probes, const int32_t* pair_slot, int64_t P,
+                    const int32_t* list_off, int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, int64_t* out_row,
+                    void* stream) {
+  return launch_ivf_merge(part_score, part_row, probes, pair_slot, P, list_off, L, Q, nprobe, k, seg_rows, segs, out_score,
+                          reinterpret_cast<long long*>(out_row), S_(stream));
+}
+int64_t coati_ivf_plan(int64_t max_list_rows, int Q, int nprobe, int k) { return ivf_plan(max_list_rows, Q, nprobe, k); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

@@ -407,6 +407,15 @@ int launch_cluster_sums(const bf16_t* lib, long long N, int E, const int* order,
                         float* part, long long items_max, float* sums, int blocks, hipStream_t s);
 int cluster_chunk(void);                           // host only
 long long cluster_items_max(long long M, int K);   // host only
+// IVF approximate search (ivf.hip, include/coati_ivf.h): the scan of every (query, list) pair's rows -- lib [M, E] in list order, the pairs
+// sorted by (list, query), work items from item_off -- into part_* [P, segs, k], and the merge of a query's partial lists through pair_slot.
+// blocks = 0: the default grid; no result depends on it, nor on seg_rows
+int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q, int Q,
+                    const int* pair_q, const int* pair_off, const int* item_off, long long P, int k, float alpha, int seg_rows, int segs,
+                    float* part_score, int* part_row, int blocks, hipStream_t s);
+int launch_ivf_merge(const float* part_score, const int* part_row, const int* probes, const int* pair_slot, long long P, const int* list_off,
+                     int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, long long* out_row, hipStream_t s);
+long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k);   // host only: the default seg_rows
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

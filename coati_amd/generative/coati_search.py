@@ -23,9 +23,10 @@ def _usable(strings, tokenizer, canon_smiles):
 
 
 def build_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 1024, metric: str = "cosine", canon_smiles=None,
-                keep_f32: bool = False) -> Tuple[EmbeddingIndex, List[str]]:
+                keep_f32: bool = False, nlist: Optional[int] = None, iters: int = 20, seed: int = 0):
     """An index of the strings' embeddings on the encoder's device and kept, the strings of its rows (kept[i] is row i's, as given).
-    Strings that do not canonicalise or tokenize are skipped, as the density fit skips them."""
+    Strings that do not canonicalise or tokenize are skipped, as the density fit skips them.  nlist: return a coati_amd.ivf.IVFIndex of
+    that many inverted lists over the rows (k-means with `iters`, `seed`) instead of the exact EmbeddingIndex; nearest_smiles takes either."""
     index = EmbeddingIndex(encoder.embed_dim, metric=metric, device=encoder.device, keep_f32=keep_f32)
     kept: List[str] = []
     for batch in batch_indexable(smiles, batch_size):
@@ -37,13 +38,16 @@ def build_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 102
             raise RuntimeError(f"build_index: {len(usable)} usable strings gave {emb.shape[0]} embeddings")
         index.add(emb)
         kept += usable
+    if nlist is not None:
+        return index.ivf(nlist, iters=iters, seed=seed), kept
     return index, kept
 
 
-def nearest_smiles(queries: Union[List[str], torch.Tensor], index: EmbeddingIndex, kept: List[str], encoder, tokenizer, k: int = 10,
+def nearest_smiles(queries: Union[List[str], torch.Tensor], index, kept: List[str], encoder, tokenizer, k: int = 10,
                    canon_smiles=None) -> List[List[Tuple[str, float]]]:
     """Per query its k nearest library strings as (string, score), best first (fewer when the index has fewer rows left).  queries: a
-    list of SMILES (one that does not canonicalise or tokenize gets an empty list) or embeddings [Q, E], e.g. encode_points'."""
+    list of SMILES (one that does not canonicalise or tokenize gets an empty list) or embeddings [Q, E], e.g. encode_points'.  index: an
+    EmbeddingIndex or an IVFIndex (then over its default nprobe lists)."""
     if len(kept) != len(index):
         raise ValueError(f"nearest_smiles: {len(kept)} strings for an index of {len(index)} rows")
     if isinstance(queries, torch.Tensor):

@@ -312,6 +312,12 @@ class EmbeddingIndex:
         out.rows = rows
         return out
 
+    def ivf(self, nlist, iters=20, seed=0, centres=None):
+        """A coati_amd.ivf.IVFIndex over the live rows: kmeans(nlist, iters, seed)'s clusters (or the nearest of `centres`) as inverted
+        lists, for approximate search over the nprobe nearest lists of every query.  Rows added or removed afterwards are not seen by it."""
+        from .ivf import IVFIndex
+        return IVFIndex.build(self, nlist, iters=iters, seed=seed, centres=centres)
+
     def _rescore(self, q32, scores, rows, k):
         """the candidates' scores from the f32 copies (a gather and a bmm over [Q, m k, E]), re-sorted: score descending, row ascending"""
         pad = rows < 0
