@@ -10,18 +10,15 @@ every cluster's rows in a fixed order (no atomics), and the mean is taken in f32
 their launch geometry, so neither does a whole run from one seed.  "cosine" is spherical k-means (unit rows, the mean renormalised), "l2"
 plain k-means (the centre's -|c|^2 / 2 goes in as the kernel's per-centre bias); "dot" has no nearest centre and raises.  There is no CPU
 fallback: off a GPU these raise RuntimeError, like EmbeddingIndex.search.  The reference has no counterpart."""
-import ctypes
-
 import torch
 
 from . import _lib
+from .ops import ptr, stream
 
 K_MAX = 4096
 CLUSTER_METRICS = ("cosine", "l2")
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _check_metric(metric):
@@ -67,8 +64,8 @@ def assign_call(x16, row_bias, c16, cbias=None, blocks=0):
     best = torch.empty(N, dtype=torch.float32, device=x16.device)
     if N:
         with torch.cuda.device(x16.device):
-            _lib.call("coati_cluster_assign", _ptr(x16), N, E, _ptr(row_bias), _ptr(c16), c16.shape[0], _ptr(cbias), _ptr(assign), _ptr(best),
-                      int(blocks), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.call("coati_cluster_assign", ptr(x16), N, E, ptr(row_bias), ptr(c16), c16.shape[0], ptr(cbias), ptr(assign), ptr(best),
+                      int(blocks), stream())
     return assign, best
 
 
@@ -101,8 +98,8 @@ def sums_call(x16, order32, offsets, item_off, part=None, blocks=0):
         if part is None or part.numel() < items_max * E:
             part = torch.empty(items_max * E, dtype=torch.float32, device=x16.device)
         with torch.cuda.device(x16.device):
-            _lib.call("coati_cluster_sums", _ptr(x16), N, E, _ptr(order32), M, _ptr(offsets), _ptr(item_off), K, _ptr(part), items_max,
-                      _ptr(sums), int(blocks), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.call("coati_cluster_sums", ptr(x16), N, E, ptr(order32), M, ptr(offsets), ptr(item_off), K, ptr(part), items_max,
+                      ptr(sums), int(blocks), stream())
     return sums
 
 

@@ -165,12 +165,7 @@ __global__ __launch_bounds__(256) void cluster_partial_kernel(const bf16_t* __re
   const int p = tid / lpr, pc = tid - p * lpr;
   const long long items = min((long long)item_off[K], items_max);
   for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-    // the cluster of item `it`: the last k with item_off[k] <= it (clusters without items share their successor's entry)
-    int lo = 0, hi = K;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (item_off[mid] <= it) lo = mid; else hi = mid;
-    }
+    const int lo = item_owner(item_off, K, it);   // the cluster of item `it`
     const long long beg = max(0ll, (long long)offsets[lo] + (it - item_off[lo]) * CL_CH);
     const long long end = min(min((long long)offsets[lo + 1], beg + CL_CH), M);
     float acc[8];

@@ -5,32 +5,24 @@
 // group of <= 16 of its pairs, segment of seg_rows of its rows); a workgroup takes items blockIdx.x, + gridDim.x, ... and finds an item's
 // list by bisection of item_off, so the grid is sized without the host knowing the item count.  Items are numbered segment-major: items
 // i, i + 1 share the row segment and differ in the pair group, so a segment brought in for one group is found in the caches by the next.
-// The body is search_topk_kernel's (search.hip) with ONE 16-query panel:
-//  * library rows are the M side of v_mfma_f32_16x16x32_bf16, the group's queries its N side: the result map (column = lane & 15, row =
-//    4 (lane >> 4) + register) gives a lane four scores of ONE pair;
-//  * the B fragments are gathered from q[pair_q[..]] once per item and stay in registers (E / 32 steps x 4 VGPRs); a wave streams 16-row
-//    slabs of the segment as 16-B loads per lane, the next slab's (and its bias) in flight under the current one's MFMAs.  One iteration of
-//    the workgroup is 4 slabs = IVF_ROWS_IT rows in ascending position order; the k-steps over E run in search_topk_kernel's order, so a
-//    (query, row) score has the same bits in both kernels;
-//  * LDS holds per pair cap = k + 2 IVF_ROWS_IT candidates as 64-bit keys (order-preserving score key << 32 | ~position), a count and a
-//    threshold (-inf at first).  A lane appends a score iff it is > the threshold, strictly: the threshold is the k-th best of positions that
-//    are all SMALLER, and inside a list a smaller position is a smaller original row (the header's precondition), so an equal score correctly
-//    loses.  An iteration adds at most IVF_ROWS_IT candidates to a pair and a compaction (to <= k, by counting: one wave per pair) runs
-//    after every iteration that left some count above cap - IVF_ROWS_IT: no append runs past its buffer, no candidate is dropped;
-//  * whether to compact is decided by ALL threads from one LDS word read after a barrier (two words, by iteration parity).  Every trip
-//    count -- items of the workgroup, iterations of the item -- is computed by every thread from the same global words: workgroup-uniform.
-//    No barrier is under a lane-, wave- or item-dependent condition (an item that is skipped is skipped whole, by every thread);
-//  * written: part[pair][segment][0 .. k-1] in rank order, the row being ids[position], padded with (-inf, -1).
-// Positions >= the segment's end are read from a clamped address (inside lib) and masked to -inf after the MFMA; columns past the group's
-// last pair are zero fragments that are neither filtered nor stored.
+// Per item a workgroup gathers the group's queries through pair_q into B fragments (columns past the group's last pair, or with a query
+// outside 0 .. Q - 1, are zero fragments that are neither filtered nor stored), runs topk_stream<KSMAX, 1> (topk_stream_dev.h: the exact
+// search's body, so a (query, row) score has the same bits in both kernels) over the segment's positions, and writes
+// part[pair][segment][0 .. k-1] in rank order, the row being ids[position], padded with (-inf, -1).
+//  * the body's "row" is a position of lib here.  Its strict > stays the tie rule: the threshold is the k-th best of positions that are
+//    all SMALLER, and inside a list a smaller position is a smaller original row (the header's precondition), so an equal score correctly
+//    loses;
+//  * every trip count -- items of the workgroup, iterations of the item -- is computed by every thread from the same global words:
+//    workgroup-uniform.  No barrier is under a lane-, wave- or item-dependent condition (an item that is skipped is skipped whole, by
+//    every thread, before the body is entered).
+// Positions >= the segment's end are read from a clamped address (inside lib) and masked to -inf after the MFMA.
 //
 // ivf_merge_kernel, one workgroup per query: its partial lists (through pair_slot; of entry j only the segments its list really has, from
 // list_off -- a slot no item wrote is never read) become 64-bit keys (score key << 32 | ~row) in LDS, unique over the query since a row
 // lives in one list.  An 8-pass radix select finds the k-th largest key, the <= k survivors are ranked by counting.  Key descending is
 // score descending, original row ascending among equal scores.
-#include "decode_dev.h"
+#include "topk_stream_dev.h"
 
-#define IVF_ROWS_IT 64
 #define IVF_E_MAX 512
 #define IVF_L_MAX 4096
 #define IVF_NPROBE_MAX 128
@@ -39,165 +31,46 @@
 #define IVF_SEG_MIN 128        // rows of the shortest segment ivf_plan proposes
 #define IVF_GRID_MAX 2048
 
-typedef float ivf_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long ivf_key_t;
-
-__device__ __forceinline__ ivf_key_t ivf_key(float s, int row) {
-  return ((ivf_key_t)f2key(s) << 32) | (ivf_key_t)(~(unsigned)row);
-}
-
-// search_compact of search.hip, restated for 16 pairs: the k best of every pair's candidates, in rank order at the front of its buffer;
-// count and threshold follow.  Wave w takes the pairs w, w + 4, ...; nothing here crosses waves, the caller's barriers separate it from the
-// appends.  In the loop only the pairs with more than k + IVF_ROWS_IT / 2 candidates are taken; FINAL: every list that has any.
-template <bool FINAL>
-__device__ __forceinline__ void ivf_compact(ivf_key_t* sbuf, int* s_cnt, float* s_thr, int cap, int k, int wave, int lane) {
-  for (int ql = wave; ql < 16; ql += 4) {
-    const int n = s_cnt[ql];
-    if (FINAL ? n == 0 : n <= k + IVF_ROWS_IT / 2) continue;   // (n is the wave's: one LDS word)
-    ivf_key_t* b = sbuf + ql * cap;
-    ivf_key_t mine[4];
-    int rank[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = lane + 64 * i;
-      mine[i] = e < n ? b[e] : 0ull;
-      rank[i] = 0;
-    }
-    for (int j = 0; j < n; ++j) {
-      const ivf_key_t kj = b[j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rank[i] += kj > mine[i] ? 1 : 0;
-    }
-    __builtin_amdgcn_wave_barrier();   // every read of the buffer above, every write below
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (lane + 64 * i < n && rank[i] < k) {
-        b[rank[i]] = mine[i];
-        if (rank[i] == k - 1) s_thr[ql] = key2f((unsigned)(mine[i] >> 32));
-      }
-    }
-    if (lane == 0) s_cnt[ql] = n < k ? n : k;
-  }
-}
-
 template <int KSMAX>
 __global__ __launch_bounds__(256) void ivf_scan_kernel(const bf16_t* __restrict__ lib, const int* __restrict__ ids, const float* __restrict__ bias,
                                                        const int* __restrict__ list_off, long long M, int E, int L, const bf16_t* __restrict__ q,
                                                        int Q, const int* __restrict__ pair_q, const int* __restrict__ pair_off,
                                                        const int* __restrict__ item_off, long long P, int k, float alpha, int seg_rows, int segs,
                                                        int cap, float* __restrict__ part_score, int* __restrict__ part_row) {
-  extern __shared__ ivf_key_t sbuf[];   // [16][cap]
+  extern __shared__ topk_key_t sbuf[];   // [16][cap]
   __shared__ int s_cnt[16];
   __shared__ float s_thr[16];
   __shared__ int s_flag[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, g = lane >> 4;
+  const int lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
   const int ks = E >> 5;
   const long long items = item_off[L];
 
   for (long long item = blockIdx.x; item < items; item += gridDim.x) {
-    // the list of the item: the last l with item_off[l] <= item (lists without items share their successor's entry)
-    int lo = 0, hi = L;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (item_off[mid] <= item) lo = mid; else hi = mid;
-    }
-    const long long p_begin = min(max((long long)pair_off[lo], 0ll), P), p_end = min(max((long long)pair_off[lo + 1], p_begin), P);
-    const long long l_begin = min(max((long long)list_off[lo], 0ll), M), l_end = min(max((long long)list_off[lo + 1], l_begin), M);
-    const long long groups = (p_end - p_begin + 15) >> 4, j = item - item_off[lo];
+    const int l = item_owner(item_off, L, item);   // (lists without items share their successor's entry)
+    const long long p_begin = min(max((long long)pair_off[l], 0ll), P), p_end = min(max((long long)pair_off[l + 1], p_begin), P);
+    const long long l_begin = min(max((long long)list_off[l], 0ll), M), l_end = min(max((long long)list_off[l + 1], l_begin), M);
+    const long long groups = (p_end - p_begin + 15) >> 4, j = item - item_off[l];
     if (groups < 1 || j < 0) continue;   // (not the documented table; every thread reads the same words: skipped by all)
     const long long sg = j / groups, pg = j - sg * groups;
     const long long r_begin = l_begin + sg * seg_rows, r_end = min(l_end, r_begin + seg_rows);
     if (sg >= segs || r_begin >= r_end) continue;
     const long long p0 = p_begin + 16 * pg;
     const int nq = (int)min(16ll, p_end - p0);
-    const int iters = (int)((r_end - r_begin + IVF_ROWS_IT - 1) / IVF_ROWS_IT);
 
     // the group's queries: B[k = 32 s + 8 g + j][column = col]
     int qi = -1;
     if (col < nq) qi = pair_q[p0 + col];
-    const bool stored = qi >= 0 && qi < Q;
-    bf16x8 bq[KSMAX];
+    const bool stored[1] = {qi >= 0 && qi < Q};
+    bf16x8 bq[1][KSMAX];
 #pragma unroll
     for (int s = 0; s < KSMAX; ++s) {
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (s < ks && stored) v = *reinterpret_cast<const uint4*>(q + (long long)qi * E + 32 * s + 8 * g);
-      bq[s] = __builtin_bit_cast(bf16x8, v);
+      if (s < ks && stored[0]) v = *reinterpret_cast<const uint4*>(q + (long long)qi * E + 32 * s + 8 * g);
+      bq[0][s] = __builtin_bit_cast(bf16x8, v);
     }
-    if (tid < 16) {
-      s_cnt[tid] = 0;
-      s_thr[tid] = -INFINITY;
-    }
-    if (tid < 2) s_flag[tid] = 0;
-    __syncthreads();
-
-    // a wave's slab of iteration it: positions r_begin + 16 (4 it + wave) .. + 15; A[row = col][k = 32 s + 8 g + j].  A position >= M is
-    // read at M - 1 (inside the allocation) and masked after the MFMA; bn = the bias of the lane's four result rows (-inf: masked)
-    uint4 an[KSMAX];
-    float bn[4];
-#pragma unroll
-    for (int s = 0; s < KSMAX; ++s) an[s] = make_uint4(0u, 0u, 0u, 0u);
-    auto load_slab = [&](int it) {
-      const long long slab = r_begin + 16ll * (4 * it + wave);
-      const long long row = min(slab + col, M - 1);
-      const uint4* src = reinterpret_cast<const uint4*>(lib + row * E + 8 * g);
-#pragma unroll
-      for (int s = 0; s < KSMAX; ++s)
-        if (s < ks) an[s] = src[4 * s];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long long br = slab + 4 * g + r;
-        bn[r] = br < r_end ? (bias ? bias[br] : 0.f) : -INFINITY;
-      }
-    };
-    load_slab(0);
-
-    for (int it = 0; it < iters; ++it) {
-      uint4 ac[KSMAX];
-      float bc[4];
-#pragma unroll
-      for (int s = 0; s < KSMAX; ++s) ac[s] = an[s];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bc[r] = bn[r];
-      if (it + 1 < iters) load_slab(it + 1);
-
-      ivf_f32x4 acc = ivf_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < KSMAX; ++s) {
-        if (s < ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ac[s]), bq[s], acc, 0, 0, 0);
-      }
-
-      // filter: the lane's four positions against its pair's threshold
-      const int pos0 = (int)(r_begin + 16ll * (4 * it + wave)) + 4 * g;
-      const float thr = s_thr[col];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float sc = alpha * acc[r] + bc[r];
-        sc += 0.0f;   // -0 -> +0: the two must tie
-        if (stored && sc > thr) {
-          const int slot = atomicAdd(&s_cnt[col], 1);   // < cap: the count was <= cap - IVF_ROWS_IT when this iteration began
-          sbuf[col * cap + slot] = ivf_key(sc, pos0 + r);
-          if (slot + 1 > cap - IVF_ROWS_IT) s_flag[it & 1] = 1;
-        }
-      }
-      __syncthreads();
-      const int full = s_flag[it & 1];   // read by every thread between two barriers with no write to it: workgroup-uniform
-      if (full) {
-        ivf_compact<false>(sbuf, s_cnt, s_thr, cap, k, wave, lane);
-        __syncthreads();
-        if (tid == 0) s_flag[it & 1] = 0;   // (this word's next use is two iterations on, behind the next iteration's barrier)
-      }
-    }
-
-    ivf_compact<true>(sbuf, s_cnt, s_thr, cap, k, wave, lane);
-    __syncthreads();
-    for (int i = tid; i < nq * k; i += 256) {
-      const int ql = i / k, r = i - ql * k;
-      const long long o = ((p0 + ql) * segs + sg) * k + r;
-      const bool have = r < s_cnt[ql];
-      const ivf_key_t key = sbuf[ql * cap + r];
-      part_score[o] = have ? key2f((unsigned)(key >> 32)) : -INFINITY;
-      part_row[o] = have ? ids[(int)~(unsigned)key] : -1;   // (a stored position is one of r_begin .. r_end - 1 < M)
-    }
+    topk_stream<KSMAX, 1>(lib, M, E, bias, bq, 1, stored, r_begin, r_end, alpha, k, cap, sbuf, s_cnt, s_thr, s_flag);
+    // (a stored position is one of r_begin .. r_end - 1 < M)
+    topk_write_out(sbuf, s_cnt, cap, k, nq, (p0 * segs + sg) * k, (long long)segs * k, [&](int pos) { return ids[pos]; }, part_score, part_row);
     __syncthreads();   // the next item's reset of the counts, behind this one's reads
   }
 }
@@ -206,11 +79,11 @@ __global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict_
                                                         const int* __restrict__ probes, const int* __restrict__ pair_slot, long long P,
                                                         const int* __restrict__ list_off, int L, int nprobe, int k, int seg_rows, int segs,
                                                         float* __restrict__ out_score, long long* __restrict__ out_row) {
-  extern __shared__ ivf_key_t mkeys[];   // [nprobe * segs * k]
+  extern __shared__ topk_key_t mkeys[];   // [nprobe * segs * k]
   __shared__ int hist[256];
-  __shared__ ivf_key_t s_prefix;
+  __shared__ topk_key_t s_prefix;
   __shared__ int s_need, s_n;
-  __shared__ ivf_key_t top[TOPK_MAX];
+  __shared__ topk_key_t top[TOPK_MAX];
   __shared__ long long s_slot[IVF_NPROBE_MAX];
   __shared__ int s_nseg[IVF_NPROBE_MAX];
   const int tid = threadIdx.x;
@@ -236,12 +109,12 @@ __global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict_
   const int sk = segs * k, V = nprobe * sk;
   for (int i = tid; i < V; i += 256) {
     const int j = i / sk, rem = i - j * sk, sg = rem / k;
-    ivf_key_t key = 0ull;
+    topk_key_t key = 0ull;
     if (sg < s_nseg[j]) {
       const long long o = s_slot[j] * sk + rem;
       const float sc = part_score[o];
       const int row = part_row[o];
-      if (row >= 0 && sc > -INFINITY) key = ivf_key(sc, row);
+      if (row >= 0 && sc > -INFINITY) key = topk_key(sc, row);
     }
     mkeys[i] = key;
   }
@@ -249,12 +122,12 @@ __global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict_
   // radix select of the k-th largest key (V >= k): after pass p the top 8 (p + 1) bits of it are known
   for (int pass = 0; pass < 8; ++pass) {
     const int shift = 56 - 8 * pass;
-    const ivf_key_t mask = pass == 0 ? 0ull : (~0ull << (shift + 8));
+    const topk_key_t mask = pass == 0 ? 0ull : (~0ull << (shift + 8));
     hist[tid] = 0;
     __syncthreads();
-    const ivf_key_t prefix = s_prefix;
+    const topk_key_t prefix = s_prefix;
     for (int i = tid; i < V; i += 256) {
-      const ivf_key_t key = mkeys[i];
+      const topk_key_t key = mkeys[i];
       if ((key & mask) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255)], 1);
     }
     __syncthreads();
@@ -265,15 +138,15 @@ __global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict_
         need -= hist[bin];
       }
       s_need = need;
-      s_prefix = prefix | ((ivf_key_t)bin << shift);
+      s_prefix = prefix | ((topk_key_t)bin << shift);
     }
     __syncthreads();
   }
   // survivors: the real keys >= the k-th largest.  Real keys are unique, so there are at most k (the bound check only guards a caller that
   // named a list twice)
-  const ivf_key_t tau = s_prefix;
+  const topk_key_t tau = s_prefix;
   for (int i = tid; i < V; i += 256) {
-    const ivf_key_t key = mkeys[i];
+    const topk_key_t key = mkeys[i];
     if (key != 0ull && key >= tau) {
       const int slot = atomicAdd(&s_n, 1);
       if (slot < TOPK_MAX) top[slot] = key;
@@ -283,7 +156,7 @@ __global__ __launch_bounds__(256) void ivf_merge_kernel(const float* __restrict_
   const int n = min(min(s_n, k), TOPK_MAX);
   if (tid < k) {
     if (tid < n) {
-      const ivf_key_t mine = top[tid];
+      const topk_key_t mine = top[tid];
       int rank = 0;
       for (int j2 = 0; j2 < n; ++j2) rank += top[j2] > mine ? 1 : 0;
       out_score[qi * k + rank] = key2f((unsigned)(mine >> 32));
@@ -299,8 +172,8 @@ static int ivf_check_common(const char* what, int L, int Q, int k, int seg_rows,
   COATI_CHECK_SHAPE(L >= 1 && L <= IVF_L_MAX, "%s: L=%d outside 1 .. %d", what, L, IVF_L_MAX);
   COATI_CHECK_SHAPE(Q >= 1, "%s: Q=%d < 1", what, Q);
   COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX, "%s: k=%d outside 1 .. %d", what, k, TOPK_MAX);
-  COATI_CHECK_SHAPE(seg_rows >= IVF_ROWS_IT && seg_rows % IVF_ROWS_IT == 0, "%s: seg_rows=%d is not a positive multiple of %d", what, seg_rows,
-                    IVF_ROWS_IT);
+  COATI_CHECK_SHAPE(seg_rows >= TOPK_ROWS_IT && seg_rows % TOPK_ROWS_IT == 0, "%s: seg_rows=%d is not a positive multiple of %d", what, seg_rows,
+                    TOPK_ROWS_IT);
   COATI_CHECK_SHAPE(segs >= 1, "%s: segs=%d < 1", what, segs);
   return COATI_OK;
 }
@@ -325,8 +198,8 @@ int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const 
   // the most items P pairs can make: every list with pairs has at most pairs_l / 16 + 1 groups, each of at most segs segments
   const long long lists = P < L ? P : L, most = (P / 16 + lists) * segs;
   const int grid = (int)(blocks > 0 ? (blocks < most ? blocks : most) : (most < IVF_GRID_MAX ? most : IVF_GRID_MAX));
-  const int cap = k + 2 * IVF_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
-  const size_t lds = (size_t)16 * cap * sizeof(ivf_key_t);   // <= 32 KiB
+  const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
+  const size_t lds = (size_t)16 * cap * sizeof(topk_key_t);   // <= 32 KiB
   if (E <= 256)
     hipLaunchKernelGGL((ivf_scan_kernel<8>), dim3(grid), dim3(256), lds, s, lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P,
                        k, alpha, seg_rows, segs, cap, part_score, part_row);
@@ -354,14 +227,14 @@ int launch_ivf_merge(const float* part_score, const int* part_row, const int* pr
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       IVF_MERGE_MAX * (int)sizeof(ivf_key_t));
+                                       IVF_MERGE_MAX * (int)sizeof(topk_key_t));
     if (e != hipSuccess) {
       coati_set_error("ivf_merge: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       return COATI_EHIP;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL(ivf_merge_kernel, dim3(Q), dim3(256), (size_t)nprobe * segs * k * sizeof(ivf_key_t), s, part_score, part_row, probes,
+  hipLaunchKernelGGL(ivf_merge_kernel, dim3(Q), dim3(256), (size_t)nprobe * segs * k * sizeof(topk_key_t), s, part_score, part_row, probes,
                      pair_slot, P, list_off, L, nprobe, k, seg_rows, segs, out_score, out_row);
   COATI_LAUNCH_CHECK("ivf_merge");
   return COATI_OK;
@@ -379,9 +252,9 @@ long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k) {
   const long long pairs = (long long)Q * nprobe;
   long long segs = (IVF_DEVICE_SLOTS + pairs - 1) / pairs;
   segs = segs < by_merge ? segs : by_merge;
-  long long seg_rows = ((max_list_rows + segs - 1) / segs + IVF_ROWS_IT - 1) / IVF_ROWS_IT * IVF_ROWS_IT;
+  long long seg_rows = ((max_list_rows + segs - 1) / segs + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT * TOPK_ROWS_IT;
   seg_rows = seg_rows > IVF_SEG_MIN ? seg_rows : IVF_SEG_MIN;
   COATI_CHECK_SHAPE(seg_rows < (1ll << 31), "ivf_plan: max_list_rows=%lld in %lld segments: no multiple of %d below 2^31 holds a segment", max_list_rows,
-                    segs, IVF_ROWS_IT);
+                    segs, TOPK_ROWS_IT);
   return seg_rows;
 }

@@ -416,6 +416,16 @@ int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const 
 int launch_ivf_merge(const float* part_score, const int* part_row, const int* probes, const int* pair_slot, long long P, const int* list_off,
                      int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, long long* out_row, hipStream_t s);
 long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k);   // host only: the default seg_rows
+// the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
+// item_off[i] <= item (owners without items share their successor's entry), by bisection
+__device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (item_off[mid] <= item) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 // batch tail (batch.hip)
 int launch_batch_ncols(const long long* tok, int B, int S, int* ncols, hipStream_t s);
 int launch_batch_tail(const long long* tok, int B, int S, int ncol, long long* tok_out, long long* y_out,

@@ -12,21 +12,16 @@ partial lists.  The scores are the exact kernel's bits, the rows returned are or
 lists the result IS EmbeddingIndex.search's.  Nothing depends on the launch geometry; building is reproducible bit for bit from the seed.
 "dot" has no nearest centre and raises.  There is no CPU fallback.  Out of scope: add() after build (rebuild instead), rescore, more than
 4096 lists, storage below bf16, several GPUs.  The reference has no counterpart."""
-import ctypes
-
 import torch
 
 from . import _lib, cluster
-from .search import K_MAX, SCRATCH_BYTES, finish_scores, metric_alpha, prepare_queries
+from .ops import ptr, stream
+from .search import K_MAX, SCRATCH_BYTES, finish_scores, metric_alpha, prepare_queries, scratch_pair
 
 NLIST_MAX = 4096
 NPROBE_MAX = 128
 MERGE_MAX = 16384                # nprobe * segs * k: one query's partial lists are one row of the merge's select
 PAIR_GROUP = 16                  # the pairs of one work item
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def invert_probes(probes, sizes, seg_rows, cache=None):
@@ -188,14 +183,11 @@ class IVFIndex:
         S = lib.coati_search_slices(self.nlist, Q, nprobe)
         if S < 1:
             raise RuntimeError(f"coati_search_slices({self.nlist}, {Q}, {nprobe}) = {S}: {lib.coati_last_error().decode('utf-8', 'replace')}")
-        need = Q * S * nprobe
-        if self._coarse is None or self._coarse[0].numel() < need:
-            self._coarse = (torch.empty(need, dtype=torch.float32, device=self.device), torch.empty(need, dtype=torch.int32, device=self.device))
+        self._coarse = scratch_pair(self._coarse, Q * S * nprobe, self.device)
         scores = torch.empty(Q, nprobe, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.call("coati_search_topk", _ptr(self._c16), self.nlist, self.dim_padded, _ptr(self._cbias), _ptr(q16), Q, nprobe,
-                      metric_alpha(self.metric), S, _ptr(self._coarse[0]), _ptr(self._coarse[1]), _ptr(scores), _ptr(lists),
-                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.call("coati_search_topk", ptr(self._c16), self.nlist, self.dim_padded, ptr(self._cbias), ptr(q16), Q, nprobe,
+                      metric_alpha(self.metric), S, ptr(self._coarse[0]), ptr(self._coarse[1]), ptr(scores), ptr(lists), stream())
         return lists
 
     def probe(self, queries, nprobe):
@@ -258,22 +250,19 @@ class IVFIndex:
             table32 = table.to(torch.int32).contiguous()
             per_query = nprobe * segs * k * 8
             qc = max(1, min(Q, SCRATCH_BYTES // per_query))
-            need = qc * nprobe * segs * k
-            if self._scratch is None or self._scratch[0].numel() < need:
-                self._scratch = (torch.empty(need, dtype=torch.float32, device=self.device),
-                                 torch.empty(need, dtype=torch.int32, device=self.device))
+            self._scratch = scratch_pair(self._scratch, qc * nprobe * segs * k, self.device)
             with torch.cuda.device(self.device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                s = stream()
                 for lo in range(0, Q, qc):
                     n = min(qc, Q - lo)
                     pair_q, pair_off, item_off, pair_slot = invert_probes(table32[lo:lo + n], self._sizes, seg_rows, self._tables)
                     P = n * nprobe
-                    _lib.call("coati_ivf_scan", _ptr(self._vec), _ptr(self._ids), _ptr(pos_bias), _ptr(self._list_off), self._m,
-                              self.dim_padded, self.nlist, _ptr(q16[lo:lo + n]), n, _ptr(pair_q), _ptr(pair_off), _ptr(item_off), P, k,
-                              metric_alpha(self.metric), seg_rows, segs, _ptr(self._scratch[0]), _ptr(self._scratch[1]), int(blocks), stream)
-                    _lib.call("coati_ivf_merge", _ptr(self._scratch[0]), _ptr(self._scratch[1]), _ptr(table32[lo:lo + n]), _ptr(pair_slot),
-                              P, _ptr(self._list_off), self.nlist, n, nprobe, k, seg_rows, segs, _ptr(scores[lo:lo + n]),
-                              _ptr(rows[lo:lo + n]), stream)
+                    _lib.call("coati_ivf_scan", ptr(self._vec), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m,
+                              self.dim_padded, self.nlist, ptr(q16[lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off), P, k,
+                              metric_alpha(self.metric), seg_rows, segs, ptr(self._scratch[0]), ptr(self._scratch[1]), int(blocks), s)
+                    _lib.call("coati_ivf_merge", ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(table32[lo:lo + n]), ptr(pair_slot),
+                              P, ptr(self._list_off), self.nlist, n, nprobe, k, seg_rows, segs, ptr(scores[lo:lo + n]),
+                              ptr(rows[lo:lo + n]), s)
         scores = finish_scores(scores, self.metric, q16)
         return (scores, rows, table.long()) if return_probes else (scores, rows)
 

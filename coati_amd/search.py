@@ -9,11 +9,10 @@ score matrix exists -- and a second one merges the library slices' lists.  The t
 top of that one kernel: "dot" (alpha 1, no bias), "cosine" (rows and queries normalised in f32, then rounded to bf16) and "l2" (alpha 2,
 bias = -|x|^2 of the STORED bf16 values; the score returned is the negated squared distance).  Removing a row sets its bias to -inf.
 There is no CPU fallback: search() on an index that is not on a GPU raises.  The reference has no counterpart."""
-import ctypes
-
 import torch
 
 from . import _lib
+from .ops import ptr, stream
 
 METRICS = ("dot", "cosine", "l2")
 DIM_MAX = 512
@@ -85,8 +84,11 @@ def finish_scores(scores, metric, q16):
     return (scores - (q16.float() ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+def scratch_pair(pair, need, device):
+    """`pair` if it is an (f32, int32) pair of at least `need` elements each, else a new one: a kernel's partial lists, kept between calls"""
+    if pair is None or pair[0].numel() < need:
+        pair = (torch.empty(need, dtype=torch.float32, device=device), torch.empty(need, dtype=torch.int32, device=device))
+    return pair
 
 
 class EmbeddingIndex:
@@ -204,17 +206,14 @@ class EmbeddingIndex:
             if self.device.type != "cuda":
                 raise RuntimeError("EmbeddingIndex.search: the index is not on a GPU; there is no CPU fallback")
             qc, S = self._plan(Q, kk, slices)
-            need = qc * S * kk
-            if self._scratch is None or self._scratch[0].numel() < need:
-                self._scratch = (torch.empty(need, dtype=torch.float32, device=self.device),
-                                 torch.empty(need, dtype=torch.int32, device=self.device))
+            self._scratch = scratch_pair(self._scratch, qc * S * kk, self.device)
             with torch.cuda.device(self.device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                s = stream()
                 for lo in range(0, Q, qc):
                     n = min(qc, Q - lo)
-                    _lib.call("coati_search_topk", _ptr(self._vec), self._n, self.dim_padded, _ptr(bias), _ptr(q16[lo:lo + n]), n, kk,
-                              metric_alpha(self.metric), S, _ptr(self._scratch[0]), _ptr(self._scratch[1]), _ptr(scores[lo:lo + n]),
-                              _ptr(rows[lo:lo + n]), stream)
+                    _lib.call("coati_search_topk", ptr(self._vec), self._n, self.dim_padded, ptr(bias), ptr(q16[lo:lo + n]), n, kk,
+                              metric_alpha(self.metric), S, ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(scores[lo:lo + n]),
+                              ptr(rows[lo:lo + n]), s)
         return scores, rows
 
     def _check_head(self, head, what):

@@ -1,6 +1,6 @@
 """A pure-torch restatement of the embedding-library search of include/coati_search.h, in float64, for the tests: scores from the
 STORED bf16 rows and the bf16-rounded queries, a stable descending sort (row index ascending among equal scores), rows whose score is
--inf never returned, padding with (-inf, -1)."""
+-inf never returned, padding with (-inf, -1).  And the synthetic data test_gpu_search.py and test_gpu_ivf.py share."""
 import torch
 
 NEG_INF = float("-inf")
@@ -47,3 +47,26 @@ def index_search(index, queries, k):
     s = index_scores(index, queries)
     val, idx = topk(s, k)
     return val, idx, s
+
+
+def ints(shape, seed, lo=-4, hi=4):
+    """integer-valued f32 in lo .. hi: every score is exact, and ties abound"""
+    return torch.randint(lo, hi + 1, shape, generator=torch.Generator().manual_seed(seed)).to(torch.float32)
+
+
+def canon(s):
+    if not s or "X" in s:
+        return None
+    return min(s, s[::-1])
+
+
+def strings(tokens, n, seed):
+    """n distinct strings of 2 .. 6 tokens that are their own canonical form"""
+    g = torch.Generator().manual_seed(seed)
+    out, seen = [], set()
+    while len(out) < n:
+        s = "".join(tokens[int(i)] for i in torch.randint(0, len(tokens), (int(torch.randint(2, 7, (1,), generator=g)),), generator=g))
+        if canon(s) == s and s not in seen:
+            seen.add(s)
+            out.append(s)
+    return out

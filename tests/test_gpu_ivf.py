@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import ivf_util, search_util  # noqa: E402
 from tests.gpu_util import log  # noqa: E402
+from tests.search_util import canon as _canon, ints as _ints, strings as _strings  # noqa: E402
 
 DEV = "cuda:0"
 NEG_INF = float("-inf")
@@ -26,10 +27,6 @@ N, L = 3000, 7
 SIZES = [0, 1, 15, 150, 203, 1200, 1431]
 ONE_SEGMENT = 1472                                   # the longest list in one segment: the next multiple of 64
 SMALL = dict(n_layer_e3gnn=2, n_layer_xformer=2, n_hidden_xformer=64, n_hidden_e3nn=64, n_embd_common=64, n_head=4, n_seq=24, n_tok=48)
-
-
-def _ints(shape, seed, lo=-4, hi=4):
-    return torch.randint(lo, hi + 1, shape, generator=torch.Generator().manual_seed(seed)).to(torch.float32)
 
 
 def _hand_assign(seed=0):
@@ -314,24 +311,6 @@ def test_build_is_reproducible_and_probes_the_nearest_lists(metric):
     seen = [ivf_util.recall(a.search(q, 10, nprobe=n)[1], exact) for n in (1, 2, 4, 12)]
     log(f"ivf {metric} k-means lists, mixture of 12 Gaussians: recall@10 at nprobe 1, 2, 4, 12 = {seen}")
     assert seen == sorted(seen) and seen[-1] == 1.0
-
-
-def _canon(s):
-    if not s or "X" in s:
-        return None
-    return min(s, s[::-1])
-
-
-def _strings(tokens, n, seed):
-    """n distinct strings of 2 .. 6 tokens that are their own canonical form (test_gpu_search.py's synthetic library)"""
-    g = torch.Generator().manual_seed(seed)
-    out, seen = [], set()
-    while len(out) < n:
-        s = "".join(tokens[int(i)] for i in torch.randint(0, len(tokens), (int(torch.randint(2, 7, (1,), generator=g)),), generator=g))
-        if _canon(s) == s and s not in seen:
-            seen.add(s)
-            out.append(s)
-    return out
 
 
 def test_nearest_smiles_through_an_ivf_index(golden_dir):

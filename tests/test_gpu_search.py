@@ -15,14 +15,11 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import search_util  # noqa: E402
 from tests.gpu_util import log  # noqa: E402
+from tests.search_util import canon as _canon, ints as _ints, strings as _strings  # noqa: E402
 
 DEV = "cuda:0"
 NEG_INF = float("-inf")
 SMALL = dict(n_layer_e3gnn=2, n_layer_xformer=2, n_hidden_xformer=64, n_hidden_e3nn=64, n_embd_common=64, n_head=4, n_seq=24, n_tok=48)
-
-
-def _ints(shape, seed, lo=-4, hi=4):
-    return torch.randint(lo, hi + 1, shape, generator=torch.Generator().manual_seed(seed)).to(torch.float32)
 
 
 def _index(vectors, metric="dot", **kw):
@@ -191,24 +188,6 @@ def test_rescore_from_the_f32_copies():
 
 
 # ---- 7. end to end ---------------------------------------------------------------------------------------------------------------
-def _canon(s):
-    if not s or "X" in s:
-        return None
-    return min(s, s[::-1])
-
-
-def _strings(tokens, n, seed):
-    """n distinct strings of 2 .. 6 tokens that are their own canonical form"""
-    g = torch.Generator().manual_seed(seed)
-    out, seen = [], set()
-    while len(out) < n:
-        s = "".join(tokens[int(i)] for i in torch.randint(0, len(tokens), (int(torch.randint(2, 7, (1,), generator=g)),), generator=g))
-        if _canon(s) == s and s not in seen:
-            seen.add(s)
-            out.append(s)
-    return out
-
-
 def _end_to_end(model, tk, tokens, points=None):
     from coati.generative import build_index, nearest_smiles
     strings = _strings(tokens, 40, 5)
