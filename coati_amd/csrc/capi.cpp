@@ -12,6 +12,7 @@
 #include "../../include/coati_acq.h"
 #include "../../include/coati_cluster.h"
 #include "../../include/coati_ivf.h"
+#include "../../include/coati_radius.h"
 #include <vector>
 #include "kernels.h"
 
@@ -381,6 +382,18 @@ int coati_ivf_merge(const float* part_score, const int32_t* part_row, const int3
                           reinterpret_cast<long long*>(out_row), S_(stream));
 }
 int64_t coati_ivf_plan(int64_t max_list_rows, int Q, int nprobe, int k) { return ivf_plan(max_list_rows, Q, nprobe, k); }
+// radius search (include/coati_radius.h)
+int coati_radius_count(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
+                       int clamp0, const float* thr, const int32_t* row_hi, int S, int32_t* counts, void* stream) {
+  return launch_radius_count(lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, S_(stream));
+}
+int coati_radius_fill(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
+                      int clamp0, const float* thr, const int32_t* row_hi, int S, const int32_t* counts, const int64_t* offsets,
+                      float* out_score, int64_t* out_row, void* stream) {
+  return launch_radius_fill(lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, LL(offsets), out_score,
+                            reinterpret_cast<long long*>(out_row), S_(stream));
+}
+int coati_radius_slices(int64_t N, int Q) { return radius_slices(N, Q); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

@@ -416,6 +416,14 @@ int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const 
 int launch_ivf_merge(const float* part_score, const int* part_row, const int* probes, const int* pair_slot, long long P, const int* list_off,
                      int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, long long* out_row, hipStream_t s);
 long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k);   // host only: the default seg_rows
+// radius search (radius.hip, include/coati_radius.h): counts [Q, S] = the rows of every slice with alpha * dot + bias > -inf, that value - sub[q]
+// (min 0 with clamp0) >= thr[q] and row < row_hi[q]; the fill writes them at offsets (the caller's exclusive prefix sum of counts), row ascending
+int launch_radius_count(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,
+                        int clamp0, const float* thr, const int* row_hi, int S, int* counts, hipStream_t s);
+int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,
+                       int clamp0, const float* thr, const int* row_hi, int S, const int* counts, const long long* offsets, float* out_score,
+                       long long* out_row, hipStream_t s);
+int radius_slices(long long N, int Q);   // host only: the default S
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

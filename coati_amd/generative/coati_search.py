@@ -43,21 +43,24 @@ def build_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 102
     return index, kept
 
 
+def _query_embeddings(what, queries, index, kept, encoder, tokenizer, canon_smiles):
+    """(where, emb): per query its row of emb (None: a string that does not canonicalise or tokenize), emb None when no query is usable"""
+    if len(kept) != len(index):
+        raise ValueError(f"{what}: {len(kept)} strings for an index of {len(index)} rows")
+    if isinstance(queries, torch.Tensor):
+        return list(range(queries.shape[0] if queries.dim() == 2 else 1)), queries
+    mask = _usable(queries, tokenizer, canon_smiles)
+    it = iter(range(sum(mask)))
+    where: List[Optional[int]] = [next(it) if ok else None for ok in mask]
+    return where, _D._batch_embeds([s for s, ok in zip(queries, mask) if ok], encoder, tokenizer, canon_smiles)
+
+
 def nearest_smiles(queries: Union[List[str], torch.Tensor], index, kept: List[str], encoder, tokenizer, k: int = 10,
                    canon_smiles=None) -> List[List[Tuple[str, float]]]:
     """Per query its k nearest library strings as (string, score), best first (fewer when the index has fewer rows left).  queries: a
     list of SMILES (one that does not canonicalise or tokenize gets an empty list) or embeddings [Q, E], e.g. encode_points'.  index: an
     EmbeddingIndex or an IVFIndex (then over its default nprobe lists)."""
-    if len(kept) != len(index):
-        raise ValueError(f"nearest_smiles: {len(kept)} strings for an index of {len(index)} rows")
-    if isinstance(queries, torch.Tensor):
-        where: List[Optional[int]] = list(range(queries.shape[0] if queries.dim() == 2 else 1))
-        emb = queries
-    else:
-        mask = _usable(queries, tokenizer, canon_smiles)
-        it = iter(range(sum(mask)))
-        where = [next(it) if ok else None for ok in mask]
-        emb = _D._batch_embeds([s for s, ok in zip(queries, mask) if ok], encoder, tokenizer, canon_smiles)
+    where, emb = _query_embeddings("nearest_smiles", queries, index, kept, encoder, tokenizer, canon_smiles)
     out: List[List[Tuple[str, float]]] = [[] for _ in where]
     if emb is None:
         return out
@@ -67,3 +70,32 @@ def nearest_smiles(queries: Union[List[str], torch.Tensor], index, kept: List[st
         if w is not None:
             out[i] = [(kept[r], s) for s, r in zip(scores[w], rows[w]) if r >= 0]
     return out
+
+
+def smiles_within(queries: Union[List[str], torch.Tensor], index, kept: List[str], encoder, tokenizer, threshold: float,
+                  canon_smiles=None) -> List[List[Tuple[str, float]]]:
+    """Per query ALL library strings whose score reaches `threshold` as (string, score), best first (row ascending among equal scores) --
+    nearest_smiles without a k.  threshold is in the units EmbeddingIndex.search returns: cosine or dot score >= threshold; on an "l2"
+    index the negated squared distance, so pass -r * r for "within r".  queries: as in nearest_smiles.  index: an EmbeddingIndex."""
+    where, emb = _query_embeddings("smiles_within", queries, index, kept, encoder, tokenizer, canon_smiles)
+    out: List[List[Tuple[str, float]]] = [[] for _ in where]
+    if emb is None:
+        return out
+    offsets, scores, rows = index.radius_search(emb, threshold, order="score")
+    offsets, scores, rows = offsets.cpu().tolist(), scores.cpu().tolist(), rows.cpu().tolist()
+    for i, w in enumerate(where):
+        if w is not None:
+            out[i] = [(kept[r], s) for s, r in zip(scores[offsets[w]:offsets[w + 1]], rows[offsets[w]:offsets[w + 1]])]
+    return out
+
+
+def drop_near_duplicates(index, kept: List[str], threshold: float) -> List[int]:
+    """Removes from `index` (an EmbeddingIndex) every row that EmbeddingIndex.dedup(threshold) drops -- the later ones of every group of rows
+    within the threshold of each other, e.g. one molecule embedded from two spellings -- and returns the row numbers that stay.  Row
+    numbers and `kept` do not change (a removed row is only never returned again): kept[i] is still row i's string."""
+    if len(kept) != len(index):
+        raise ValueError(f"drop_near_duplicates: {len(kept)} strings for an index of {len(index)} rows")
+    live = (index.bias > float("-inf")).cpu()
+    keep = index.dedup(threshold).cpu()
+    index.remove((live & ~keep).nonzero().reshape(-1))
+    return keep.nonzero().reshape(-1).tolist()

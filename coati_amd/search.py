@@ -317,6 +317,39 @@ class EmbeddingIndex:
         from .ivf import IVFIndex
         return IVFIndex.build(self, nlist, iters=iters, seed=seed, centres=centres)
 
+    def radius_count(self, queries, threshold, row_below=None):
+        """int64 [Q]: how many live rows score >= threshold for each query (threshold, row_below: as in radius_search) -- the count pass
+        of coati_amd.radius alone; nothing is allocated per hit."""
+        from . import radius
+        return radius.radius_count(self, queries, threshold, row_below)
+
+    def radius_search(self, queries, threshold, order="row", row_below=None, slices=None, max_results=1 << 28):
+        """(offsets int64 [Q + 1], scores f32 [T], rows int64 [T]): EVERY live row within the threshold of each query, in CSR form -- query
+        i's hits are scores / rows [offsets[i] : offsets[i + 1]].  threshold (a float, or a [Q] tensor) is in the units search() returns:
+        cosine or dot score >= threshold; for "l2" the NEGATED squared distance >= threshold, so pass -r * r for "within r".  +inf matches
+        nothing, -inf every live row.  A score has the bits search() returns for the same (query, row).
+        order: "row" = ascending row (the kernel's order); "score" = score descending, row ascending among equal scores, so that a
+        segment begins with what search() returns.  row_below: int [Q], only rows < row_below[i] are hits of query i.  slices: the
+        library slices of the kernel's grid (default: coati_radius_slices); the result does not depend on it.  The total is known after the
+        count pass (the one synchronisation); above max_results a ValueError names it before anything is allocated."""
+        from . import radius
+        return radius.radius_search(self, queries, threshold, order, row_below, slices, max_results)
+
+    def near_duplicates(self, threshold, chunk=4096):
+        """(offsets int64 [N + 1], scores f32 [T], rows int64 [T]): for every live row i the EARLIER live rows j < i whose score with it is
+        >= threshold (units as in radius_search), row ascending -- the self-join, `chunk` rows at a time, of which only the triangle
+        j < i is computed.  The queries are the stored bf16 rows themselves, so a copy of a row scores exactly what the stored bits
+        give.  A removed row has no neighbours and is nobody's neighbour."""
+        from . import radius
+        return radius.near_duplicates(self, threshold, chunk)
+
+    def dedup(self, threshold):
+        """bool [N] keep mask of the greedy leader rule in row order over near_duplicates(threshold): a live row is kept iff none of its
+        earlier neighbours is kept; removed rows are False.  No two kept rows are within the threshold of each other, and every dropped
+        live row is within the threshold of a kept one.  The sequential pass runs on the CPU over the rows that have a neighbour."""
+        from . import radius
+        return radius.dedup(self, threshold)
+
     def _rescore(self, q32, scores, rows, k):
         """the candidates' scores from the f32 copies (a gather and a bmm over [Q, m k, E]), re-sorted: score descending, row ascending"""
         pad = rows < 0
