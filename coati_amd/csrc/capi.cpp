@@ -13,6 +13,7 @@
 #include "../../include/coati_cluster.h"
 #include "../../include/coati_ivf.h"
 #include "../../include/coati_radius.h"
+#include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
 
@@ -427,6 +428,96 @@ int coati_gnn_edge_pre(const uint16_t* P, int64_t ldp, const int32_t* seg, const
 }
 int coati_gnn_edge_reduce(const uint16_t* s2, const int32_t* seg, const float* e_w, uint16_t* mi, int64_t ldmi, int BA, int H, void* stream) {
   return launch_gnn_edge_reduce_c(s2, seg, e_w, mi, ldmi, BA, H, S_(stream));
+}
+
+// the point encoder's kernels one by one (include/coati_gnn_ops.h): the launchers the engine calls, argument for argument
+int coati_gnn_edge_fwd_fused(const uint16_t* P, int64_t ldp, const int32_t* seg, const int32_t* e_bk, const float* e_d2, const float* e_w,
+                             const float* w1c, int64_t w1c_stride, const float* b1, const uint16_t* W3, int64_t ldw, const float* b3,
+                             uint16_t* e1, uint16_t* s2, uint16_t* mi, int64_t ldmi, int BA, int H, void* stream) {
+  return launch_gnn_edge_fwd_fused(P, ldp, seg, e_bk, e_d2, e_w, w1c, w1c_stride, b1, W3, ldw, b3, e1, s2, mi, ldmi, BA, H, S_(stream));
+}
+int coati_gnn_edge_reduce_bwd(const uint16_t* dmi, int64_t lddmi, const uint16_t* s2, const int32_t* seg, const float* e_w, uint16_t* ds2,
+                              int BA, int H, void* stream) {
+  COATI_CHECK_SHAPE(BA > 0 && H > 0, "gnn_edge_reduce_bwd: empty problem");
+  return launch_gnn_edge_reduce_bwd_c(dmi, lddmi, s2, seg, e_w, ds2, BA, H, S_(stream));
+}
+int coati_gnn_edge_pre_bwd(const uint16_t* dpre, const int32_t* seg, const int32_t* e_rev, const float* e_d2, uint16_t* dP, int64_t lddp,
+                           float* dw1c, int64_t dw1c_stride, float* db1, int BA, int H, void* stream) {
+  COATI_CHECK_SHAPE(BA > 0 && H > 0, "gnn_edge_pre_bwd: empty problem");
+  return launch_gnn_edge_pre_bwd_c(dpre, seg, e_rev, e_d2, dP, lddp, dw1c, dw1c_stride, db1, BA, H, S_(stream));
+}
+int coati_gnn_node_res_silu(const float* u32, const int64_t* atoms, const int32_t* lut_ix, const int32_t* lut_iy, const float* W3c,
+                            int64_t ldw, uint16_t* upre, uint16_t* t16, int BA, int H, void* stream) {
+  COATI_CHECK_SHAPE(BA > 0 && H > 0, "gnn_node_res_silu: empty problem");
+  return launch_gnn_node_res_silu(u32, LL(atoms), lut_ix, lut_iy, W3c, ldw, upre, t16, BA, H, S_(stream));
+}
+int coati_gnn_onehot_wgrad(const int64_t* atoms, const int32_t* lut_ix, const int32_t* lut_iy, const uint16_t* du, float* dW, int64_t ldw,
+                           int BA, int H, void* stream) {
+  COATI_CHECK_SHAPE(BA > 0 && H > 0, "gnn_onehot_wgrad: empty problem");
+  return launch_gnn_onehot_wgrad(LL(atoms), lut_ix, lut_iy, du, dW, ldw, BA, H, S_(stream));
+}
+int coati_gnn_embed_bwd(const int64_t* atoms, const int32_t* lut_ix, const int32_t* lut_iy, const float* de, float* dW, float* db, int BA,
+                        int H, void* stream) {
+  COATI_CHECK_SHAPE(BA > 0 && H > 0, "gnn_embed_bwd: empty problem");
+  return launch_gnn_embed_bwd(LL(atoms), lut_ix, lut_iy, de, dW, db, BA, H, S_(stream));
+}
+int coati_gnn_readout(const float* o, const float* mask, float* hp, int B, int A, int H, void* stream) {
+  COATI_CHECK_SHAPE(B > 0 && A > 0 && H > 0, "gnn_readout: empty problem");
+  return launch_gnn_readout(o, mask, hp, B, A, H, S_(stream));
+}
+int coati_gnn_readout_bwd(const float* dhp, const float* mask, uint16_t* dout, int B, int A, int H, void* stream) {
+  COATI_CHECK_SHAPE(B > 0 && A > 0 && H > 0, "gnn_readout_bwd: empty problem");
+  return launch_gnn_readout_bwd(dhp, mask, dout, B, A, H, S_(stream));
+}
+int coati_gemm_rows_dev(const int32_t* m_dev, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K,
+                        uint16_t* C, int64_t ldc, const float* bias, int epi, const uint16_t* P, int64_t ldp, const float* d2,
+                        const float* w1c, int64_t w1c_stride, const float* b1, int natom, int H, const int32_t* e_bj,
+                        const int32_t* e_bk, int32_t* resident, void* stream) {
+  COATI_CHECK_ARG(m_dev && A && B && C && resident, "gemm_rows_dev: null argument");
+  COATI_CHECK_ARG(epi == EPI_BF16 || epi == EPI_EDGE_DPRE, "gemm_rows_dev: epilogue %d (EPI_BF16 and EPI_EDGE_DPRE only)", epi);
+  COATI_CHECK_SHAPE(M > 0 && N > 0 && K > 0, "gemm_rows_dev: empty problem");
+  if (epi == EPI_EDGE_DPRE)
+    COATI_CHECK_ARG(N == H && (e_bj == nullptr) == (e_bk == nullptr), "gemm_rows_dev: EPI_EDGE_DPRE needs N == H (N=%d H=%d) and e_bj with e_bk", N, H);
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.m_dev = m_dev; a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.M = M; a.N = N; a.K = K; a.C = C; a.ldc = ldc; a.bias = bias;
+  a.P = P; a.ldp = ldp; a.d2 = d2; a.w1c = w1c; a.w1c_stride = w1c_stride; a.b1 = b1; a.natom = natom; a.H = H; a.e_bj = e_bj; a.e_bk = e_bk;
+  *resident = gemm_rb16_resident_supported(a, 0, epi) ? 1 : 0;
+  return launch_gemm_nt(a, 0, epi, S_(stream));
+}
+int coati_wgrad_rows_dev(const int32_t* m_dev, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, int M, int N, int K,
+                         float* dW, int64_t ldw, float* dbias, void* stream) {
+  COATI_CHECK_ARG(m_dev, "wgrad_rows_dev: null m_dev");
+  WgradArgs a;
+  a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.M = M; a.N = N; a.K = K; a.dW = dW; a.ldw = ldw; a.dbias = dbias; a.n_out = 0; a.m_dev = m_dev;
+  return launch_wgrad(a, 0, S_(stream));
+}
+int64_t coati_wgrad_split_workspace_bytes(int n_problems, const int* N, const int* K, int n_splits) {
+  if (n_problems <= 0 || !N || !K || n_splits < 1) return 0;
+  int64_t entries = 0;
+  for (int i = 0; i < n_problems; ++i) entries += (int64_t)cdiv(N[i], 128) * cdiv(K[i], 128) * n_splits;
+  return entries * (int64_t)sizeof(WgradTile);
+}
+int coati_wgrad_split(int n_problems, const uint16_t* const* A, const int64_t* lda, const uint16_t* const* B, const int64_t* ldb, int M,
+                      const int* N, const int* K, float* const* dW, const int64_t* ldw, float* const* dbias, int n_splits,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+  COATI_CHECK_ARG(n_problems > 0 && A && lda && B && ldb && N && K && dW && ldw && dbias && workspace, "wgrad_split: null argument");
+  COATI_CHECK_ARG(n_splits >= 1, "wgrad_split: n_splits=%d", n_splits);
+  std::vector<WgradTile> tab;
+  for (int i = 0; i < n_problems; ++i) {
+    WgradArgs a;
+    a.A = A[i]; a.lda = lda[i]; a.B = B[i]; a.ldb = ldb[i]; a.M = M; a.N = N[i]; a.K = K[i]; a.dW = dW[i]; a.ldw = ldw[i]; a.dbias = dbias[i]; a.n_out = 0;
+    COATI_TRY(wgrad_table_append_split(tab, a, n_splits));
+  }
+  COATI_CHECK_ARG((int64_t)(tab.size() * sizeof(WgradTile)) <= workspace_bytes, "wgrad_split: workspace too small (%zu entries)", tab.size());
+  hipStream_t s = S_(stream);
+  // as coati_wgrad_grouped: the table goes into the caller's workspace and the upload is waited for, `tab` lives on this frame
+  if (hipMemcpyAsync(workspace, tab.data(), tab.size() * sizeof(WgradTile), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    coati_set_error("wgrad_split: table upload failed");
+    return COATI_EHIP;
+  }
+  return launch_wgrad_split_table(reinterpret_cast<const WgradTile*>(workspace), (int)tab.size(), s);
 }
 
 int coati_infonce_rows(float* logits, int64_t ld, int R, int N, int label0, const uint8_t* bad, float* loss_sum,

@@ -102,8 +102,8 @@ __global__ __launch_bounds__(256) void gnn_embed_bwd_kernel(const long long* __r
       const int ix = lut_ix[z], iy = lut_iy[z];
       const float v = de[(long long)row * H + c];
       bsum += v;
-      acc[ix * H + c] += v;
-      if (iy != ix) acc[iy * H + c] += v;
+      if (ix >= 0) acc[ix * H + c] += v;                // (iy = -1: the actinides, whose period bit overflows the 28-wide one-hot --
+      if (iy >= 0 && iy != ix) acc[iy * H + c] += v;    // gnn_embed_kernel adds no column for it; the guards of gnn_onehot_wgrad_kernel)
     }
     acc[28 * H + c] = bsum;
   }
