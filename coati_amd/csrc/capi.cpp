@@ -13,6 +13,7 @@
 #include "../../include/coati_cluster.h"
 #include "../../include/coati_ivf.h"
 #include "../../include/coati_radius.h"
+#include "../../include/coati_search8.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -395,6 +396,21 @@ int coati_radius_fill(const uint16_t* lib, int64_t N, int E, const float* bias, 
                             reinterpret_cast<long long*>(out_row), S_(stream));
 }
 int coati_radius_slices(int64_t N, int Q) { return radius_slices(N, Q); }
+// quantised search (include/coati_search8.h)
+int coati_quant_rows_fp8(const uint16_t* x, int64_t n, int E, uint8_t* out, float* scale, void* stream) {
+  return launch_quant_rows_fp8(x, n, E, out, scale, S_(stream));
+}
+int coati_search8_topk(const uint8_t* lib8, const float* scale, int64_t N, int E, const float* bias, const uint8_t* q8, const float* qscale,
+                       int Q, int k, float alpha, int S, float* part_score, int32_t* part_row, float* out_score, int64_t* out_row,
+                       void* stream) {
+  return launch_search8_topk(lib8, scale, N, E, bias, q8, qscale, Q, k, alpha, S, part_score, part_row, out_score,
+                             reinterpret_cast<long long*>(out_row), S_(stream));
+}
+int coati_search_rescore(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, const int64_t* cand, int R, int k,
+                         float alpha, float* out_score, int64_t* out_row, void* stream) {
+  return launch_search_rescore(lib, N, E, bias, q, Q, LL(cand), R, k, alpha, out_score, reinterpret_cast<long long*>(out_row), S_(stream));
+}
+int coati_search8_slices(int64_t N, int Q, int k) { return search8_slices(N, Q, k); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

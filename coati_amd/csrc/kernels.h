@@ -424,6 +424,16 @@ int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias,
                        int clamp0, const float* thr, const int* row_hi, int S, const int* counts, const long long* offsets, float* out_score,
                        long long* out_row, hipStream_t s);
 int radius_slices(long long N, int Q);   // host only: the default S
+// quantised search (search8.hip, include/coati_search8.h): rows as e4m3 bytes + one power-of-two scale, the streaming stage over them
+// (partial lists as launch_search_topk's, merged by launch_search_merge of search.hip), and the candidates' exact scores from the bf16 rows
+int launch_search_merge(const float* part_score, const int* part_row, int Q, int V, int k, float* out_score, long long* out_row, hipStream_t s);
+int launch_quant_rows_fp8(const bf16_t* x, long long n, int E, unsigned char* out, float* scale, hipStream_t s);
+int launch_search8_topk(const unsigned char* lib, const float* scale, long long N, int E, const float* bias, const unsigned char* q,
+                        const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
+                        long long* out_row, hipStream_t s);
+int launch_search_rescore(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, const long long* cand, int R, int k,
+                          float alpha, float* out_score, long long* out_row, hipStream_t s);
+int search8_slices(long long N, int Q, int k);   // host only: the default S
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

@@ -119,6 +119,25 @@ int launch_search_topk(const bf16_t* lib, long long N, int E, const float* bias,
   return COATI_OK;
 }
 
+// The merge alone, for a stream kernel of another file that writes the same partial lists (search8.hip): out [Q, k] from part [Q, V].
+int launch_search_merge(const float* part_score, const int* part_row, int Q, int V, int k, float* out_score, long long* out_row, hipStream_t s) {
+  COATI_CHECK_ARG(part_score && part_row && out_score && out_row, "search_merge: null operand");
+  COATI_CHECK_SHAPE(Q >= 1 && k >= 1 && k <= TOPK_MAX && V >= k && V <= SEARCH_MERGE_MAX, "search_merge: Q=%d V=%d k=%d out of range", Q, V, k);
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       SEARCH_MERGE_MAX * 4);
+    if (e != hipSuccess) {
+      coati_set_error("search_merge: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+      return COATI_EHIP;
+    }
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(256), (size_t)V * 4, s, part_score, part_row, V, k, out_score, out_row);
+  COATI_LAUNCH_CHECK("search_merge");
+  return COATI_OK;
+}
+
 // The number of slices launch_search_topk is given by default: enough workgroups to fill the device at this Q (tiles of 64 queries),
 // no slice shorter than one workgroup iteration, S * k within the merge's row.  Host arithmetic only.
 int search_slices(long long N, int Q, int k) {

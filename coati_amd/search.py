@@ -317,6 +317,14 @@ class EmbeddingIndex:
         from .ivf import IVFIndex
         return IVFIndex.build(self, nlist, iters=iters, seed=seed, centres=centres)
 
+    def fp8(self, keep_rows=True):
+        """A coati_amd.fp8_index.Fp8Index over the rows present now: every row as e4m3 bytes plus one scale (half the bytes), searched in
+        two stages -- a stream over the bytes keeps oversample * k candidates, their exact scores from the bf16 rows decide.
+        keep_rows=True holds a view of these bf16 rows; keep_rows=False nothing but bytes, scales and bias (stage 1 alone).  Rows
+        added or removed afterwards are not seen by it."""
+        from .fp8_index import Fp8Index
+        return Fp8Index.build(self, keep_rows=keep_rows)
+
     def radius_count(self, queries, threshold, row_below=None):
         """int64 [Q]: how many live rows score >= threshold for each query (threshold, row_below: as in radius_search) -- the count pass
         of coati_amd.radius alone; nothing is allocated per hit."""
