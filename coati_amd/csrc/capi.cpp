@@ -14,6 +14,7 @@
 #include "../../include/coati_ivf.h"
 #include "../../include/coati_radius.h"
 #include "../../include/coati_search8.h"
+#include "../../include/coati_ivf8.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -384,6 +385,14 @@ int coati_ivf_merge(const float* part_score, const int32_t* part_row, const int3
                           reinterpret_cast<long long*>(out_row), S_(stream));
 }
 int64_t coati_ivf_plan(int64_t max_list_rows, int Q, int nprobe, int k) { return ivf_plan(max_list_rows, Q, nprobe, k); }
+// IVF search over fp8 lists (include/coati_ivf8.h)
+int coati_ivf8_scan(const uint8_t* lib8, const float* scale, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E,
+                    int L, const uint8_t* q8, const float* qscale, int Q, const int32_t* pair_q, const int32_t* pair_off,
+                    const int32_t* item_off, int64_t P, int k, float alpha, int seg_rows, int segs, float* part_score, int32_t* part_row,
+                    int blocks, void* stream) {
+  return launch_ivf8_scan(lib8, scale, ids, bias, list_off, M, E, L, q8, qscale, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs,
+                          part_score, part_row, blocks, S_(stream));
+}
 // radius search (include/coati_radius.h)
 int coati_radius_count(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
                        int clamp0, const float* thr, const int32_t* row_hi, int S, int32_t* counts, void* stream) {

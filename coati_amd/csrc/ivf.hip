@@ -178,6 +178,19 @@ static int ivf_check_common(const char* what, int L, int Q, int k, int seg_rows,
   return COATI_OK;
 }
 
+// The checks and the grid that the scan shares with its fp8 form (ivf8.hip): the limits of coati_ivf_scan's contract, then
+// min(blocks or IVF_GRID_MAX, the most items P pairs can make) workgroups.  Returns the grid (>= 1) or a negative code.
+int ivf_scan_grid(const char* what, long long M, int E, int L, int Q, long long P, int k, int seg_rows, int segs, int blocks) {
+  COATI_CHECK_SHAPE(E >= 32 && E <= IVF_E_MAX && E % 32 == 0, "%s: E=%d is not a multiple of 32 in 32 .. %d", what, E, IVF_E_MAX);
+  COATI_CHECK_SHAPE(M >= 1 && M < (1ll << 31), "%s: M=%lld outside 1 .. 2^31 - 1", what, M);
+  COATI_CHECK_SHAPE(P >= 1 && P < (1ll << 31), "%s: P=%lld outside 1 .. 2^31 - 1", what, P);
+  COATI_TRY(ivf_check_common(what, L, Q, k, seg_rows, segs));
+  COATI_CHECK_SHAPE(blocks >= 0, "%s: blocks=%d < 0", what, blocks);
+  // the most items P pairs can make: every list with pairs has at most pairs_l / 16 + 1 groups, each of at most segs segments
+  const long long lists = P < L ? P : L, most = (P / 16 + lists) * segs;
+  return (int)(blocks > 0 ? (blocks < most ? blocks : most) : (most < IVF_GRID_MAX ? most : IVF_GRID_MAX));
+}
+
 int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q, int Q,
                     const int* pair_q, const int* pair_off, const int* item_off, long long P, int k, float alpha, int seg_rows, int segs,
                     float* part_score, int* part_row, int blocks, hipStream_t s) {
@@ -190,14 +203,8 @@ int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const 
   COATI_CHECK_ARG(item_off, "ivf_scan: item_off is null");
   COATI_CHECK_ARG(part_score, "ivf_scan: part_score is null");
   COATI_CHECK_ARG(part_row, "ivf_scan: part_row is null");
-  COATI_CHECK_SHAPE(E >= 32 && E <= IVF_E_MAX && E % 32 == 0, "ivf_scan: E=%d is not a multiple of 32 in 32 .. %d", E, IVF_E_MAX);
-  COATI_CHECK_SHAPE(M >= 1 && M < (1ll << 31), "ivf_scan: M=%lld outside 1 .. 2^31 - 1", M);
-  COATI_CHECK_SHAPE(P >= 1 && P < (1ll << 31), "ivf_scan: P=%lld outside 1 .. 2^31 - 1", P);
-  COATI_TRY(ivf_check_common("ivf_scan", L, Q, k, seg_rows, segs));
-  COATI_CHECK_SHAPE(blocks >= 0, "ivf_scan: blocks=%d < 0", blocks);
-  // the most items P pairs can make: every list with pairs has at most pairs_l / 16 + 1 groups, each of at most segs segments
-  const long long lists = P < L ? P : L, most = (P / 16 + lists) * segs;
-  const int grid = (int)(blocks > 0 ? (blocks < most ? blocks : most) : (most < IVF_GRID_MAX ? most : IVF_GRID_MAX));
+  const int grid = ivf_scan_grid("ivf_scan", M, E, L, Q, P, k, seg_rows, segs, blocks);
+  if (grid < 0) return grid;
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
   const size_t lds = (size_t)16 * cap * sizeof(topk_key_t);   // <= 32 KiB
   if (E <= 256)

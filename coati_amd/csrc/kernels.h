@@ -416,6 +416,13 @@ int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const 
 int launch_ivf_merge(const float* part_score, const int* part_row, const int* probes, const int* pair_slot, long long P, const int* list_off,
                      int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, long long* out_row, hipStream_t s);
 long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k);   // host only: the default seg_rows
+// host only: the scan's limits checked under the name `what`, then its grid (>= 1), or a negative code
+int ivf_scan_grid(const char* what, long long M, int E, int L, int Q, long long P, int k, int seg_rows, int segs, int blocks);
+// the same scan over fp8 lists (ivf8.hip, include/coati_ivf8.h): lib [M, E] e4m3 bytes with scale [M], queries q [Q, E] e4m3 with qscale [Q],
+// bias required; launch_search8_topk's score, launch_ivf_scan's tables, partial lists and limits
+int launch_ivf8_scan(const unsigned char* lib, const float* scale, const int* ids, const float* bias, const int* list_off, long long M, int E,
+                     int L, const unsigned char* q, const float* qscale, int Q, const int* pair_q, const int* pair_off, const int* item_off,
+                     long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks, hipStream_t s);
 // radius search (radius.hip, include/coati_radius.h): counts [Q, S] = the rows of every slice with alpha * dot + bias > -inf, that value - sub[q]
 // (min 0 with clamp0) >= thr[q] and row < row_hi[q]; the fill writes them at offsets (the caller's exclusive prefix sum of counts), row ascending
 int launch_radius_count(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,

@@ -16,9 +16,10 @@ saturates, and data that e4m3 holds exactly -- integers of magnitude <= 15, for 
 quantised the same way.  Stage 1's bias is the index's for "dot" and "cosine"; for "l2" it is -|x_hat|^2 of the dequantised row (summed
 in float64, stored as f32), so that its score is the negated squared distance between the dequantised operands.
 
-There is no CPU fallback for search().  Out of scope: add() after build (rebuild instead), fp8 lists inside an IVFIndex, radius search,
-clustering or property heads over fp8 rows, fp6 / fp4, product quantisation, per-block scales, bf16 rows kept in host memory, R > 128.
-The reference has no counterpart."""
+There is no CPU fallback for search().  The same storage inside inverted lists -- the rows of the probed lists only, the same second
+stage -- is coati_amd.ivf8.Ivf8Index, which uses this module's quantiser and rescore_candidates.  Out of scope: add() after build
+(rebuild instead), radius search, clustering or property heads over fp8 rows, fp6 / fp4, product quantisation, per-block scales, bf16
+rows kept in host memory, R > 128.  The reference has no counterpart."""
 import torch
 
 from . import _lib
@@ -49,6 +50,15 @@ def quantise_rows(x16):
 def dequantise(bytes8, scale):
     """f32 [n, E]: the values the bytes and scales stand for (exact: an e4m3 value times a power of two)"""
     return bytes8.view(torch.float8_e4m3fn).to(torch.float32) * scale[:, None]
+
+
+def stage1_bias(metric, vec8, scale, bias16):
+    """stage 1's bias of rows with bytes vec8, scales `scale` and the bf16 rows' bias bias16: the latter, for "l2" -|x_hat|^2 of the
+    dequantised row (summed in float64, stored f32) where it is above -inf"""
+    if metric != "l2":
+        return bias16
+    norm = -(dequantise(vec8, scale).double() ** 2).sum(dim=1).float()
+    return torch.where(bias16 > float("-inf"), norm, bias16)
 
 
 def quantise_device(x16):
@@ -119,10 +129,7 @@ class Fp8Index:
             vec8, scale = quantise_device(x16)
         else:
             vec8, scale = quantise_rows(x16)
-        bias = bias16
-        if index.metric == "l2":
-            norm = -(dequantise(vec8, scale).double() ** 2).sum(dim=1).float()
-            bias = torch.where(bias16 > float("-inf"), norm, bias16)
+        bias = stage1_bias(index.metric, vec8, scale, bias16)
         return cls(index.dim, index.dim_padded, index.metric, vec8, scale, bias, x16 if keep_rows else None, bias16 if keep_rows else None,
                    index.device)
 

@@ -10,8 +10,10 @@ coati_search_topk on the centres (no new kernel); torch inverts the probe table 
 coati_ivf_scan scores the rows of every pair's list on the matrix cores -- no score matrix exists -- and coati_ivf_merge merges a query's
 partial lists.  The scores are the exact kernel's bits, the rows returned are original rows, and with nprobe >= the number of non-empty
 lists the result IS EmbeddingIndex.search's.  Nothing depends on the launch geometry; building is reproducible bit for bit from the seed.
-"dot" has no nearest centre and raises.  There is no CPU fallback.  Out of scope: add() after build (rebuild instead), rescore, more than
-4096 lists, storage below bf16, several GPUs.  The reference has no counterpart."""
+"dot" has no nearest centre and raises.  There is no CPU fallback.  Lists of e4m3 bytes with an exact bf16 re-scoring are
+coati_amd.ivf8.Ivf8Index (index.ivf(nlist, fp8=True), ivf.fp8(index)): the same lists, probe tables and merge, built on the helpers
+below (make_lists, ListIndex).  Out of scope: add() after build (rebuild instead), more than 4096 lists, storage below fp8, fp8 centres,
+several GPUs.  The reference has no counterpart."""
 import torch
 
 from . import _lib, cluster
@@ -57,24 +59,56 @@ def invert_probes(probes, sizes, seg_rows, cache=None):
     return pair_q, pair_off.to(torch.int32), item_off, pair_slot.reshape(Q, nprobe)
 
 
-class IVFIndex:
-    """An inverted-file index over the live rows of an EmbeddingIndex at the time of build().  len() is the source's; rows returned by
-    search are the source's rows.  Attributes: centres [L, dim] f32, nlist, metric, dim, dim_padded, device."""
+def make_lists(what, index, nlist, iters=20, seed=0, centres=None, assign=None):
+    """The inverted lists of an EmbeddingIndex ("cosine" or "l2") on a GPU: (centres [nlist, dim], order int64 [M], sizes int64 [nlist]).
+    The lists are index.kmeans(nlist, iters, seed)'s clusters, or, with centres, every live row's nearest of them (index.assign), or
+    assign [N] int32 given by hand (-1 leaving a row out).  order lists the rows list by list, ascending inside every list; removed
+    rows of the index are left out.  Reproducible bit for bit from the seed."""
+    cluster._check_metric(index.metric)
+    nlist = int(nlist)
+    if not 1 <= nlist <= NLIST_MAX:
+        raise ValueError(f"{what}: nlist={nlist} outside 1 .. {NLIST_MAX}")
+    if index.device.type != "cuda":
+        raise RuntimeError(f"{what}: the index is not on a GPU; there is no CPU fallback")
+    if centres is None:
+        if assign is not None:
+            raise ValueError(f"{what}: assign= needs centres=")
+        clustering = index.kmeans(nlist, iters=iters, seed=seed)
+        centres, assign = clustering.centres, clustering.assign
+    else:
+        centres = torch.as_tensor(centres)
+        if tuple(centres.shape) != (nlist, index.dim):
+            raise ValueError(f"{what}: centres must be [{nlist}, {index.dim}], got {tuple(centres.shape)}")
+        if assign is None:
+            assign, _ = index.assign(centres)
+        else:
+            assign = torch.as_tensor(assign).to(index.device, torch.int32)
+            if tuple(assign.shape) != (len(index),) or int(assign.max()) >= nlist:
+                raise ValueError(f"{what}: assign must be [{len(index)}] with entries below {nlist}")
+            assign = torch.where(index.bias > float("-inf"), assign, torch.full_like(assign, -1))
+    order, sizes = cluster.sorted_order(assign, nlist)
+    return centres, order[:int(sizes.sum())], sizes
 
-    def __init__(self, dim, dim_padded, metric, n, centres, vectors, ids, bias, sizes, device):
+
+class ListIndex:
+    """What IVFIndex and coati_amd.ivf8.Ivf8Index share: the lists (centres, ids, sizes, offsets), the coarse step, the checks of a
+    search's arguments and the scan + merge loop over chunks of queries.  A subclass stores the rows and supplies the scan call."""
+
+    def _init_lists(self, dim, dim_padded, metric, n, centres, ids, sizes, device):
         cluster._check_metric(metric)
+        self._name = type(self).__name__
         self.dim, self.dim_padded, self.metric, self.device = int(dim), int(dim_padded), metric, torch.device(device)
         self._n = int(n)
         self.centres = centres.to(self.device, torch.float32)
-        self._vec, self._ids, self._bias = vectors.to(self.device).contiguous(), ids.to(self.device, torch.int32).contiguous(), bias.to(self.device, torch.float32).contiguous()
+        self._ids = ids.to(self.device, torch.int32).contiguous()
         self._sizes = sizes.to(self.device, torch.int64)
         self.nlist = int(self._sizes.shape[0])
         if not 1 <= self.nlist <= NLIST_MAX or self.centres.shape[0] != self.nlist:
-            raise ValueError(f"IVFIndex: {self.nlist} lists for {self.centres.shape[0]} centres, outside 1 .. {NLIST_MAX}")
+            raise ValueError(f"{self._name}: {self.nlist} lists for {self.centres.shape[0]} centres, outside 1 .. {NLIST_MAX}")
         host = self._sizes.cpu()
         self._m, self._max_rows = int(host.sum()), int(host.max())
-        if self._vec.shape != (self._m, self.dim_padded) or self._ids.shape != (self._m,) or self._bias.shape != (self._m,):
-            raise ValueError("IVFIndex: vectors, ids and bias do not match the list sizes")
+        if self._ids.shape != (self._m,):
+            raise ValueError(f"{self._name}: vectors, ids and bias do not match the list sizes")
         self._list_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), self._sizes.cumsum(0)]).to(torch.int32)
         self._inverse = torch.full((self._n,), -1, dtype=torch.int64, device=self.device)
         self._inverse[self._ids.long()] = torch.arange(self._m, device=self.device)
@@ -86,39 +120,6 @@ class IVFIndex:
         self._tables = {}            # invert_probes' shape-only tensors
         self._coarse = None          # the coarse step's
 
-    # ---- building ----------------------------------------------------------------------------------------------------------------
-    @classmethod
-    def build(cls, index, nlist, iters=20, seed=0, centres=None, assign=None):
-        """index: an EmbeddingIndex ("cosine" or "l2") on a GPU.  The lists are index.kmeans(nlist, iters, seed)'s clusters, or, with
-        centres [nlist, dim], every live row's nearest of them (index.assign).  assign [N] int32 (with centres): the lists given by hand,
-        -1 leaving a row out.  Removed rows of the index are left out.  Reproducible bit for bit from the seed."""
-        cluster._check_metric(index.metric)
-        nlist = int(nlist)
-        if not 1 <= nlist <= NLIST_MAX:
-            raise ValueError(f"IVFIndex.build: nlist={nlist} outside 1 .. {NLIST_MAX}")
-        if index.device.type != "cuda":
-            raise RuntimeError("IVFIndex.build: the index is not on a GPU; there is no CPU fallback")
-        if centres is None:
-            if assign is not None:
-                raise ValueError("IVFIndex.build: assign= needs centres=")
-            clustering = index.kmeans(nlist, iters=iters, seed=seed)
-            centres, assign = clustering.centres, clustering.assign
-        else:
-            centres = torch.as_tensor(centres)
-            if tuple(centres.shape) != (nlist, index.dim):
-                raise ValueError(f"IVFIndex.build: centres must be [{nlist}, {index.dim}], got {tuple(centres.shape)}")
-            if assign is None:
-                assign, _ = index.assign(centres)
-            else:
-                assign = torch.as_tensor(assign).to(index.device, torch.int32)
-                if tuple(assign.shape) != (len(index),) or int(assign.max()) >= nlist:
-                    raise ValueError(f"IVFIndex.build: assign must be [{len(index)}] with entries below {nlist}")
-                assign = torch.where(index.bias > float("-inf"), assign, torch.full_like(assign, -1))
-        order, sizes = cluster.sorted_order(assign, nlist)
-        order = order[:int(sizes.sum())]
-        return cls(index.dim, index.dim_padded, index.metric, len(index), centres, index.vectors[order], order, index.bias[order], sizes,
-                   index.device)
-
     def __len__(self):
         return self._n
 
@@ -128,19 +129,9 @@ class IVFIndex:
         return self._sizes
 
     @property
-    def vectors(self):
-        """the stored bf16 rows [M, dim_padded] in list order"""
-        return self._vec
-
-    @property
     def ids(self):
         """[M] int32: the original row of every stored position, ascending inside every list"""
         return self._ids
-
-    @property
-    def bias(self):
-        """[M] f32: the positions' bias (0, -|x|^2 for l2, -inf once removed)"""
-        return self._bias
 
     @property
     def list_offsets(self):
@@ -150,25 +141,26 @@ class IVFIndex:
     def list_rows(self, l):
         """the original rows of list l, ascending"""
         if not 0 <= int(l) < self.nlist:
-            raise IndexError(f"IVFIndex.list_rows: list {l} outside 0 .. {self.nlist - 1}")
+            raise IndexError(f"{self._name}.list_rows: list {l} outside 0 .. {self.nlist - 1}")
         lo, hi = int(self._list_off[int(l)]), int(self._list_off[int(l) + 1])
         return self._ids[lo:hi].long()
 
-    def remove(self, rows):
-        """the rows (original indices) are never returned again; len() and the other rows' indices do not change"""
+    def _positions(self, rows):
+        """the stored positions of original rows (those that have one), for remove()"""
         rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
         if rows.numel() == 0:
-            return
+            return rows.to(self.device), rows.to(self.device)
         if int(rows.min()) < 0 or int(rows.max()) >= self._n:
-            raise IndexError(f"IVFIndex.remove: rows outside 0 .. {self._n - 1}")
-        pos = self._inverse[rows.to(self.device)]
-        self._bias[pos[pos >= 0]] = float("-inf")
+            raise IndexError(f"{self._name}.remove: rows outside 0 .. {self._n - 1}")
+        rows = rows.to(self.device)
+        pos = self._inverse[rows]
+        return rows, pos[pos >= 0]
 
     # ---- searching -----------------------------------------------------------------------------------------------------------------
     def _check_nprobe(self, nprobe):
         nprobe = int(nprobe)
         if not 1 <= nprobe <= NPROBE_MAX:
-            raise ValueError(f"IVFIndex: nprobe={nprobe} outside 1 .. {NPROBE_MAX}")
+            raise ValueError(f"{self._name}: nprobe={nprobe} outside 1 .. {NPROBE_MAX}")
         return nprobe
 
     def _probe16(self, q16, nprobe):
@@ -178,7 +170,7 @@ class IVFIndex:
             return torch.full((Q, nprobe), -1, dtype=torch.int64, device=self.device)
         lists = torch.empty(Q, nprobe, dtype=torch.int64, device=self.device)      # (the kernel writes every entry, -1 padding included)
         if self.device.type != "cuda":
-            raise RuntimeError("IVFIndex.probe: the index is not on a GPU; there is no CPU fallback")
+            raise RuntimeError(f"{self._name}.probe: the index is not on a GPU; there is no CPU fallback")
         lib = _lib.lib()
         S = lib.coati_search_slices(self.nlist, Q, nprobe)
         if S < 1:
@@ -202,8 +194,103 @@ class IVFIndex:
         lib = _lib.lib()
         seg_rows = int(lib.coati_ivf_plan(max(self._max_rows, 1), int(Q), int(nprobe), int(k)))
         if seg_rows < 1:
-            raise ValueError(f"IVFIndex: coati_ivf_plan: {lib.coati_last_error().decode('utf-8', 'replace')}")
+            raise ValueError(f"{self._name}: coati_ivf_plan: {lib.coati_last_error().decode('utf-8', 'replace')}")
         return seg_rows
+
+    def _search_args(self, queries, kk, nprobe, probes, seg_rows, bias):
+        """The checks of a search that keeps kk entries per partial list: (q16, table [Q, nprobe] on the device, nprobe, seg_rows, segs)"""
+        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,)):
+            raise ValueError(f"{self._name}.search: bias must be an f32 tensor [{self._n}]")
+        _, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
+        Q = q16.shape[0]
+        if probes is None:
+            nprobe = self._check_nprobe(nprobe)
+            table = self._probe16(q16, nprobe)
+        else:
+            table = torch.as_tensor(probes).to(self.device)
+            if table.dim() != 2 or table.shape[0] != Q or table.dtype not in (torch.int32, torch.int64) or not 1 <= table.shape[1] <= NPROBE_MAX:
+                raise ValueError(f"{self._name}.search: probes must be an integer table [{Q}, 1 .. {NPROBE_MAX}]")
+            nprobe = table.shape[1]
+        if nprobe * kk > MERGE_MAX:
+            raise ValueError(f"{self._name}.search: nprobe={nprobe} times k={kk} exceeds {MERGE_MAX}")
+        if seg_rows is None:
+            seg_rows = self.plan(max(Q, 1), nprobe, kk)
+        seg_rows = int(seg_rows)
+        if seg_rows < 64 or seg_rows % 64:
+            raise ValueError(f"{self._name}.search: seg_rows={seg_rows} is not a positive multiple of 64")
+        segs = max(1, -(-self._max_rows // seg_rows))
+        if nprobe * segs * kk > MERGE_MAX:
+            raise ValueError(f"{self._name}.search: nprobe={nprobe} lists of {segs} segments of k={kk} exceed nprobe * segs * k <= {MERGE_MAX}; "
+                             "pass a larger seg_rows, or none")
+        return q16, table, nprobe, seg_rows, segs
+
+    def _scan_merge(self, scan, Q, table, nprobe, kk, seg_rows, segs):
+        """(scores [Q, kk] f32, rows [Q, kk] int64): per chunk of queries (the partial lists of a chunk stay within SCRATCH_BYTES) the
+        probe table inverted, scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, stream) and coati_ivf_merge"""
+        if Q == 0 or self._m == 0:
+            return (torch.full((Q, kk), float("-inf"), dtype=torch.float32, device=self.device),
+                    torch.full((Q, kk), -1, dtype=torch.int64, device=self.device))
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{self._name}.search: the index is not on a GPU; there is no CPU fallback")
+        scores = torch.empty(Q, kk, dtype=torch.float32, device=self.device)      # (the merge writes every entry, padding included)
+        rows = torch.empty(Q, kk, dtype=torch.int64, device=self.device)
+        table32 = table.to(torch.int32).contiguous()
+        per_query = nprobe * segs * kk * 8
+        qc = max(1, min(Q, SCRATCH_BYTES // per_query))
+        self._scratch = scratch_pair(self._scratch, qc * nprobe * segs * kk, self.device)
+        with torch.cuda.device(self.device):
+            s = stream()
+            for lo in range(0, Q, qc):
+                n = min(qc, Q - lo)
+                pair_q, pair_off, item_off, pair_slot = invert_probes(table32[lo:lo + n], self._sizes, seg_rows, self._tables)
+                P = n * nprobe
+                scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, self._scratch[0], self._scratch[1], s)
+                _lib.call("coati_ivf_merge", ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(table32[lo:lo + n]), ptr(pair_slot),
+                          P, ptr(self._list_off), self.nlist, n, nprobe, kk, seg_rows, segs, ptr(scores[lo:lo + n]),
+                          ptr(rows[lo:lo + n]), s)
+        return scores, rows
+
+
+class IVFIndex(ListIndex):
+    """An inverted-file index over the live rows of an EmbeddingIndex at the time of build().  len() is the source's; rows returned by
+    search are the source's rows.  Attributes: centres [L, dim] f32, nlist, metric, dim, dim_padded, device."""
+
+    def __init__(self, dim, dim_padded, metric, n, centres, vectors, ids, bias, sizes, device):
+        self._init_lists(dim, dim_padded, metric, n, centres, ids, sizes, device)
+        self._vec, self._bias = vectors.to(self.device).contiguous(), bias.to(self.device, torch.float32).contiguous()
+        if self._vec.shape != (self._m, self.dim_padded) or self._bias.shape != (self._m,):
+            raise ValueError("IVFIndex: vectors, ids and bias do not match the list sizes")
+
+    # ---- building ----------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def build(cls, index, nlist, iters=20, seed=0, centres=None, assign=None):
+        """index: an EmbeddingIndex ("cosine" or "l2") on a GPU.  The lists are index.kmeans(nlist, iters, seed)'s clusters, or, with
+        centres [nlist, dim], every live row's nearest of them (index.assign).  assign [N] int32 (with centres): the lists given by hand,
+        -1 leaving a row out.  Removed rows of the index are left out.  Reproducible bit for bit from the seed."""
+        centres, order, sizes = make_lists("IVFIndex.build", index, nlist, iters, seed, centres, assign)
+        return cls(index.dim, index.dim_padded, index.metric, len(index), centres, index.vectors[order], order, index.bias[order], sizes,
+                   index.device)
+
+    def fp8(self, index=None):
+        """A coati_amd.ivf8.Ivf8Index of these lists: the stored rows as e4m3 bytes.  index: the source EmbeddingIndex, whose bf16 rows
+        the second stage then re-scores the candidates from (a view); without it the result is stage 1's."""
+        from .ivf8 import Ivf8Index
+        return Ivf8Index.from_ivf(self, index)
+
+    @property
+    def vectors(self):
+        """the stored bf16 rows [M, dim_padded] in list order"""
+        return self._vec
+
+    @property
+    def bias(self):
+        """[M] f32: the positions' bias (0, -|x|^2 for l2, -inf once removed)"""
+        return self._bias
+
+    def remove(self, rows):
+        """the rows (original indices) are never returned again; len() and the other rows' indices do not change"""
+        _, pos = self._positions(rows)
+        self._bias[pos] = float("-inf")
 
     def search(self, queries, k, nprobe=8, probes=None, seg_rows=None, bias=None, return_probes=False, blocks=0):
         """(scores [Q, k] f32, rows [Q, k] int64) of the k nearest rows among every query's probed lists: EmbeddingIndex.search's contract
@@ -215,54 +302,15 @@ class IVFIndex:
         k = int(k)
         if k < 1 or k > K_MAX:
             raise ValueError(f"IVFIndex.search: k={k} outside 1 .. {K_MAX}")
-        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,)):
-            raise ValueError(f"IVFIndex.search: bias must be an f32 tensor [{self._n}]")
-        _, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
-        Q = q16.shape[0]
-        if probes is None:
-            nprobe = self._check_nprobe(nprobe)
-            table = self._probe16(q16, nprobe)
-        else:
-            table = torch.as_tensor(probes).to(self.device)
-            if table.dim() != 2 or table.shape[0] != Q or table.dtype not in (torch.int32, torch.int64) or not 1 <= table.shape[1] <= NPROBE_MAX:
-                raise ValueError(f"IVFIndex.search: probes must be an integer table [{Q}, 1 .. {NPROBE_MAX}]")
-            nprobe = table.shape[1]
-        if nprobe * k > MERGE_MAX:
-            raise ValueError(f"IVFIndex.search: nprobe={nprobe} times k={k} exceeds {MERGE_MAX}")
-        if seg_rows is None:
-            seg_rows = self.plan(max(Q, 1), nprobe, k)
-        seg_rows = int(seg_rows)
-        if seg_rows < 64 or seg_rows % 64:
-            raise ValueError(f"IVFIndex.search: seg_rows={seg_rows} is not a positive multiple of 64")
-        segs = max(1, -(-self._max_rows // seg_rows))
-        if nprobe * segs * k > MERGE_MAX:
-            raise ValueError(f"IVFIndex.search: nprobe={nprobe} lists of {segs} segments of k={k} exceed nprobe * segs * k <= {MERGE_MAX}; "
-                             "pass a larger seg_rows, or none")
+        q16, table, nprobe, seg_rows, segs = self._search_args(queries, k, nprobe, probes, seg_rows, bias)
         pos_bias = self._bias if bias is None else (self._bias + bias.to(self.device)[self._ids.long()]).contiguous()
-        if Q == 0 or self._m == 0:
-            scores = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
-            rows = torch.full((Q, k), -1, dtype=torch.int64, device=self.device)
-        else:
-            if self.device.type != "cuda":
-                raise RuntimeError("IVFIndex.search: the index is not on a GPU; there is no CPU fallback")
-            scores = torch.empty(Q, k, dtype=torch.float32, device=self.device)      # (the merge writes every entry, padding included)
-            rows = torch.empty(Q, k, dtype=torch.int64, device=self.device)
-            table32 = table.to(torch.int32).contiguous()
-            per_query = nprobe * segs * k * 8
-            qc = max(1, min(Q, SCRATCH_BYTES // per_query))
-            self._scratch = scratch_pair(self._scratch, qc * nprobe * segs * k, self.device)
-            with torch.cuda.device(self.device):
-                s = stream()
-                for lo in range(0, Q, qc):
-                    n = min(qc, Q - lo)
-                    pair_q, pair_off, item_off, pair_slot = invert_probes(table32[lo:lo + n], self._sizes, seg_rows, self._tables)
-                    P = n * nprobe
-                    _lib.call("coati_ivf_scan", ptr(self._vec), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m,
-                              self.dim_padded, self.nlist, ptr(q16[lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off), P, k,
-                              metric_alpha(self.metric), seg_rows, segs, ptr(self._scratch[0]), ptr(self._scratch[1]), int(blocks), s)
-                    _lib.call("coati_ivf_merge", ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(table32[lo:lo + n]), ptr(pair_slot),
-                              P, ptr(self._list_off), self.nlist, n, nprobe, k, seg_rows, segs, ptr(scores[lo:lo + n]),
-                              ptr(rows[lo:lo + n]), s)
+
+        def scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, s):
+            _lib.call("coati_ivf_scan", ptr(self._vec), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m, self.dim_padded,
+                      self.nlist, ptr(q16[lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off), P, k, metric_alpha(self.metric),
+                      seg_rows, segs, ptr(part_score), ptr(part_row), int(blocks), s)
+
+        scores, rows = self._scan_merge(scan, q16.shape[0], table, nprobe, k, seg_rows, segs)
         scores = finish_scores(scores, self.metric, q16)
         return (scores, rows, table.long()) if return_probes else (scores, rows)
 

@@ -311,9 +311,14 @@ class EmbeddingIndex:
         out.rows = rows
         return out
 
-    def ivf(self, nlist, iters=20, seed=0, centres=None):
+    def ivf(self, nlist, iters=20, seed=0, centres=None, fp8=False, keep_rows=True):
         """A coati_amd.ivf.IVFIndex over the live rows: kmeans(nlist, iters, seed)'s clusters (or the nearest of `centres`) as inverted
-        lists, for approximate search over the nprobe nearest lists of every query.  Rows added or removed afterwards are not seen by it."""
+        lists, for approximate search over the nprobe nearest lists of every query.  fp8=True: a coati_amd.ivf8.Ivf8Index instead -- the
+        same lists stored as e4m3 bytes, the candidates re-scored from these bf16 rows (keep_rows=True: a view of them) or stage 1 alone
+        (keep_rows=False).  Rows added or removed afterwards are not seen by it."""
+        if fp8:
+            from .ivf8 import Ivf8Index
+            return Ivf8Index.build(self, nlist, iters=iters, seed=seed, centres=centres, keep_rows=keep_rows)
         from .ivf import IVFIndex
         return IVFIndex.build(self, nlist, iters=iters, seed=seed, centres=centres)
 
