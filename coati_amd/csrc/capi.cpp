@@ -15,6 +15,7 @@
 #include "../../include/coati_radius.h"
 #include "../../include/coati_search8.h"
 #include "../../include/coati_ivf8.h"
+#include "../../include/coati_ivf_radius.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -405,6 +406,21 @@ int coati_radius_fill(const uint16_t* lib, int64_t N, int E, const float* bias, 
                             reinterpret_cast<long long*>(out_row), S_(stream));
 }
 int coati_radius_slices(int64_t N, int Q) { return radius_slices(N, Q); }
+// radius search over inverted lists (include/coati_ivf_radius.h)
+int coati_ivf_radius_count(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                           const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P,
+                           float alpha, const float* sub, int clamp0, const float* thr, const int32_t* row_hi, int seg_rows, int segs,
+                           int32_t* counts, int blocks, void* stream) {
+  return launch_ivf_radius_count(lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, alpha, sub, clamp0, thr, row_hi, seg_rows,
+                                 segs, counts, blocks, S_(stream));
+}
+int coati_ivf_radius_fill(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                          const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P,
+                          float alpha, const float* sub, int clamp0, const float* thr, const int32_t* row_hi, int seg_rows, int segs,
+                          const int32_t* counts, const int64_t* offsets, float* out_score, int64_t* out_row, int blocks, void* stream) {
+  return launch_ivf_radius_fill(lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, alpha, sub, clamp0, thr, row_hi, seg_rows,
+                                segs, counts, LL(offsets), out_score, reinterpret_cast<long long*>(out_row), blocks, S_(stream));
+}
 // quantised search (include/coati_search8.h)
 int coati_quant_rows_fp8(const uint16_t* x, int64_t n, int E, uint8_t* out, float* scale, void* stream) {
   return launch_quant_rows_fp8(x, n, E, out, scale, S_(stream));

@@ -431,6 +431,16 @@ int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias,
                        int clamp0, const float* thr, const int* row_hi, int S, const int* counts, const long long* offsets, float* out_score,
                        long long* out_row, hipStream_t s);
 int radius_slices(long long N, int Q);   // host only: the default S
+// radius search over inverted lists (ivf_radius.hip, include/coati_ivf_radius.h): launch_ivf_scan's operands, pairs and work items with
+// launch_radius_*'s filter; counts [P, segs] (zero-filled by the caller) per (pair, segment), the fill writes ids[position] and the value
+// at offsets [P, segs], position ascending.  blocks = 0: the default grid; no result depends on it, nor on seg_rows
+int launch_ivf_radius_count(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q,
+                            int Q, const int* pair_q, const int* pair_off, const int* item_off, long long P, float alpha, const float* sub,
+                            int clamp0, const float* thr, const int* row_hi, int seg_rows, int segs, int* counts, int blocks, hipStream_t s);
+int launch_ivf_radius_fill(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q,
+                           int Q, const int* pair_q, const int* pair_off, const int* item_off, long long P, float alpha, const float* sub,
+                           int clamp0, const float* thr, const int* row_hi, int seg_rows, int segs, const int* counts, const long long* offsets,
+                           float* out_score, long long* out_row, int blocks, hipStream_t s);
 // quantised search (search8.hip, include/coati_search8.h): rows as e4m3 bytes + one power-of-two scale, the streaming stage over them
 // (partial lists as launch_search_topk's, merged by launch_search_merge of search.hip), and the candidates' exact scores from the bf16 rows
 int launch_search_merge(const float* part_score, const int* part_row, int Q, int V, int k, float* out_score, long long* out_row, hipStream_t s);

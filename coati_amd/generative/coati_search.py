@@ -89,7 +89,9 @@ def smiles_within(queries: Union[List[str], torch.Tensor], index, kept: List[str
                   canon_smiles=None) -> List[List[Tuple[str, float]]]:
     """Per query ALL library strings whose score reaches `threshold` as (string, score), best first (row ascending among equal scores) --
     nearest_smiles without a k.  threshold is in the units EmbeddingIndex.search returns: cosine or dot score >= threshold; on an "l2"
-    index the negated squared distance, so pass -r * r for "within r".  queries: as in nearest_smiles.  index: an EmbeddingIndex."""
+    index the negated squared distance, so pass -r * r for "within r".  queries: as in nearest_smiles.  index: an EmbeddingIndex, or an
+    IVFIndex -- then over the rows of every query's default nprobe nearest lists (IVFIndex.radius_search): a subset of the exact answer
+    with the same scores, all of it once nprobe covers the non-empty lists."""
     where, emb = _query_embeddings("smiles_within", queries, index, kept, encoder, tokenizer, canon_smiles)
     out: List[List[Tuple[str, float]]] = [[] for _ in where]
     if emb is None:
@@ -102,13 +104,27 @@ def smiles_within(queries: Union[List[str], torch.Tensor], index, kept: List[str
     return out
 
 
-def drop_near_duplicates(index, kept: List[str], threshold: float) -> List[int]:
+def drop_near_duplicates(index, kept: List[str], threshold: float, ivf=None, nprobe: int = 8) -> List[int]:
     """Removes from `index` (an EmbeddingIndex) every row that EmbeddingIndex.dedup(threshold) drops -- the later ones of every group of rows
     within the threshold of each other, e.g. one molecule embedded from two spellings -- and returns the row numbers that stay.  Row
-    numbers and `kept` do not change (a removed row is only never returned again): kept[i] is still row i's string."""
+    numbers and `kept` do not change (a removed row is only never returned again): kept[i] is still row i's string.
+    ivf: an IVFIndex over `index`; the keep mask is then IVFIndex.dedup(threshold, nprobe)'s -- a row looks for earlier neighbours in its
+    own and its nprobe - 1 nearest other lists only, so every dropped row is within the threshold of a row that stays, while two rows
+    that stay may still be within it if their lists were not probed together -- and the dropped rows are removed from BOTH."""
     if len(kept) != len(index):
         raise ValueError(f"drop_near_duplicates: {len(kept)} strings for an index of {len(index)} rows")
+    if ivf is not None and len(ivf) != len(index):
+        raise ValueError(f"drop_near_duplicates: an ivf of {len(ivf)} rows for an index of {len(index)} rows")
     live = (index.bias > float("-inf")).cpu()
-    keep = index.dedup(threshold).cpu()
-    index.remove((live & ~keep).nonzero().reshape(-1))
+    if ivf is None:
+        keep = index.dedup(threshold).cpu()
+    else:
+        keep = ivf.dedup(threshold, nprobe=nprobe).cpu()
+        stored = torch.zeros(len(ivf), dtype=torch.bool)
+        stored[ivf.ids.long().cpu()] = (ivf.bias > float("-inf")).cpu()
+        live &= stored                                   # (a row the ivf does not hold is not one it dropped)
+    gone = (live & ~keep).nonzero().reshape(-1)
+    index.remove(gone)
+    if ivf is not None:
+        ivf.remove(gone)
     return keep.nonzero().reshape(-1).tolist()

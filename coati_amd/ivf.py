@@ -12,7 +12,8 @@ partial lists.  The scores are the exact kernel's bits, the rows returned are or
 lists the result IS EmbeddingIndex.search's.  Nothing depends on the launch geometry; building is reproducible bit for bit from the seed.
 "dot" has no nearest centre and raises.  There is no CPU fallback.  Lists of e4m3 bytes with an exact bf16 re-scoring are
 coati_amd.ivf8.Ivf8Index (index.ivf(nlist, fp8=True), ivf.fp8(index)): the same lists, probe tables and merge, built on the helpers
-below (make_lists, ListIndex).  Out of scope: add() after build (rebuild instead), more than 4096 lists, storage below fp8, fp8 centres,
+below (make_lists, ListIndex).  Radius search over the lists -- IVFIndex.radius_search / radius_count / near_duplicates / dedup -- is
+coati_amd.ivf_radius (include/coati_ivf_radius.h).  Out of scope: add() after build (rebuild instead), more than 4096 lists, storage below fp8, fp8 centres,
 several GPUs.  The reference has no counterpart."""
 import torch
 
@@ -197,20 +198,24 @@ class ListIndex:
             raise ValueError(f"{self._name}: coati_ivf_plan: {lib.coati_last_error().decode('utf-8', 'replace')}")
         return seg_rows
 
+    def _given_probes(self, probes, nprobe, Q, what):
+        """(the caller's probe table [Q, n] on the device, n), or (None, the checked nprobe) where the coarse step is to decide"""
+        if probes is None:
+            return None, self._check_nprobe(nprobe)
+        table = torch.as_tensor(probes).to(self.device)
+        if table.dim() != 2 or table.shape[0] != Q or table.dtype not in (torch.int32, torch.int64) or not 1 <= table.shape[1] <= NPROBE_MAX:
+            raise ValueError(f"{self._name}.{what}: probes must be an integer table [{Q}, 1 .. {NPROBE_MAX}]")
+        return table, table.shape[1]
+
     def _search_args(self, queries, kk, nprobe, probes, seg_rows, bias):
         """The checks of a search that keeps kk entries per partial list: (q16, table [Q, nprobe] on the device, nprobe, seg_rows, segs)"""
         if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,)):
             raise ValueError(f"{self._name}.search: bias must be an f32 tensor [{self._n}]")
         _, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
         Q = q16.shape[0]
-        if probes is None:
-            nprobe = self._check_nprobe(nprobe)
+        table, nprobe = self._given_probes(probes, nprobe, Q, "search")
+        if table is None:
             table = self._probe16(q16, nprobe)
-        else:
-            table = torch.as_tensor(probes).to(self.device)
-            if table.dim() != 2 or table.shape[0] != Q or table.dtype not in (torch.int32, torch.int64) or not 1 <= table.shape[1] <= NPROBE_MAX:
-                raise ValueError(f"{self._name}.search: probes must be an integer table [{Q}, 1 .. {NPROBE_MAX}]")
-            nprobe = table.shape[1]
         if nprobe * kk > MERGE_MAX:
             raise ValueError(f"{self._name}.search: nprobe={nprobe} times k={kk} exceeds {MERGE_MAX}")
         if seg_rows is None:
@@ -313,6 +318,44 @@ class IVFIndex(ListIndex):
         scores, rows = self._scan_merge(scan, q16.shape[0], table, nprobe, k, seg_rows, segs)
         scores = finish_scores(scores, self.metric, q16)
         return (scores, rows, table.long()) if return_probes else (scores, rows)
+
+    # ---- radius search (coati_amd.ivf_radius) -----------------------------------------------------------------------------------------
+    def radius_search(self, queries, threshold, nprobe=8, probes=None, order="row", row_below=None, seg_rows=None, max_results=1 << 28,
+                      blocks=0, return_probes=False):
+        """(offsets int64 [Q + 1], scores f32 [T], rows int64 [T]): EmbeddingIndex.radius_search's contract restricted to the rows of every
+        query's probed lists -- every such live row whose score reaches the threshold (a float or a [Q] tensor, in the units search()
+        returns; +inf nothing, -inf every live probed row), original rows, the score bits EmbeddingIndex.search gives the pair.  With
+        nprobe >= the number of non-empty lists the result IS EmbeddingIndex.radius_search's.
+        nprobe / probes / seg_rows / blocks / return_probes: as in search(); the result depends on neither seg_rows nor blocks.
+        order: "row" = ascending row, "score" = score descending and row ascending among equal scores, "probe" = as the kernel writes:
+        list by list in the probe table's order, row ascending inside a list.  row_below: int [Q], only rows < row_below[i] are hits of
+        query i.  The total is known after the count pass (one synchronisation per chunk of queries); above max_results a ValueError
+        names it before the result is allocated."""
+        from . import ivf_radius
+        return ivf_radius.radius_search(self, queries, threshold, nprobe, probes, order, row_below, seg_rows, max_results, blocks, return_probes)
+
+    def radius_count(self, queries, threshold, nprobe=8, probes=None, row_below=None):
+        """int64 [Q]: how many live rows of each query's probed lists reach the threshold -- the count pass alone, nothing is allocated
+        per hit"""
+        from . import ivf_radius
+        return ivf_radius.radius_count(self, queries, threshold, nprobe, probes, row_below)
+
+    def near_duplicates(self, threshold, nprobe=8, chunk=4096):
+        """(offsets int64 [len + 1], scores f32 [T], rows int64 [T]) in ORIGINAL row order: for every live stored row i the EARLIER live
+        rows j < i within the threshold AMONG THE LISTS ROW i PROBES (its own list always, then its nearest by the coarse step), row
+        ascending -- a subset of EmbeddingIndex.near_duplicates with the same score bits, and equal to it once nprobe >= the number of
+        non-empty lists.  The queries are the stored bf16 rows themselves, taken `chunk` positions at a time in list order, so a chunk
+        probes a few neighbouring lists.  Rows without a position (left out at build) and removed rows have empty segments."""
+        from . import ivf_radius
+        return ivf_radius.near_duplicates(self, threshold, nprobe, chunk)
+
+    def dedup(self, threshold, nprobe=8):
+        """bool [len] keep mask: the greedy leader rule in row order (coati_amd.radius.greedy_leaders) over near_duplicates(threshold,
+        nprobe); removed rows and rows without a position are False.  What survives the approximation: every dropped row is within
+        the threshold of a KEPT one.  What does not: "no two kept rows within the threshold" holds only for pairs in which the later
+        row probed the earlier one's list.  Exact -- EmbeddingIndex.dedup's mask -- at nprobe >= the number of non-empty lists."""
+        from . import ivf_radius
+        return ivf_radius.dedup(self, threshold, nprobe)
 
     # ---- persistence ---------------------------------------------------------------------------------------------------------------
     def save(self, path):
