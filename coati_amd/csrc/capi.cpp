@@ -16,6 +16,7 @@
 #include "../../include/coati_search8.h"
 #include "../../include/coati_ivf8.h"
 #include "../../include/coati_ivf_radius.h"
+#include "../../include/coati_pq.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -436,6 +437,17 @@ int coati_search_rescore(const uint16_t* lib, int64_t N, int E, const float* bia
   return launch_search_rescore(lib, N, E, bias, q, Q, LL(cand), R, k, alpha, out_score, reinterpret_cast<long long*>(out_row), S_(stream));
 }
 int coati_search8_slices(int64_t N, int Q, int k) { return search8_slices(N, Q, k); }
+// product-quantised search (include/coati_pq.h)
+int coati_pq_encode(const uint16_t* x, int64_t n, int E, const uint16_t* codebook, uint8_t* codes, void* stream) {
+  return launch_pq_encode(x, n, E, codebook, codes, S_(stream));
+}
+int coati_pq_topk(const uint8_t* codes, int64_t N, int E, const uint16_t* codebook, const float* bias, const uint16_t* q, int Q, int k,
+                  float alpha, int S, float* part_score, int32_t* part_row, float* out_score, int64_t* out_row, void* stream) {
+  return launch_pq_topk(codes, N, E, codebook, bias, q, Q, k, alpha, S, part_score, part_row, out_score, reinterpret_cast<long long*>(out_row),
+                        S_(stream));
+}
+int coati_pq_k_max(int E) { return pq_k_max(E); }
+int coati_pq_slices(int64_t N, int E, int Q, int k) { return pq_slices(N, E, Q, k); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

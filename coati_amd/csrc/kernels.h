@@ -451,6 +451,13 @@ int launch_search8_topk(const unsigned char* lib, const float* scale, long long 
 int launch_search_rescore(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, const long long* cand, int R, int k,
                           float alpha, float* out_score, long long* out_row, hipStream_t s);
 int search8_slices(long long N, int Q, int k);   // host only: the default S
+// product-quantised search (pq.hip, include/coati_pq.h): rows as E / 8 code bytes under codebook [E / 8][256][8] bf16; the encoder, and
+// the streaming stage over the codes with the code book in LDS (launch_search_topk's partial lists, merged by launch_search_merge)
+int launch_pq_encode(const bf16_t* x, long long n, int E, const bf16_t* codebook, unsigned char* codes, hipStream_t s);
+int launch_pq_topk(const unsigned char* codes, long long N, int E, const bf16_t* codebook, const float* bias, const bf16_t* q, int Q, int k,
+                   float alpha, int S, float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s);
+int pq_k_max(int E);                                   // host only: the largest k at this E
+int pq_slices(long long N, int E, int Q, int k);       // host only: the default S
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

@@ -13,7 +13,7 @@ lists the result IS EmbeddingIndex.search's.  Nothing depends on the launch geom
 "dot" has no nearest centre and raises.  There is no CPU fallback.  Lists of e4m3 bytes with an exact bf16 re-scoring are
 coati_amd.ivf8.Ivf8Index (index.ivf(nlist, fp8=True), ivf.fp8(index)): the same lists, probe tables and merge, built on the helpers
 below (make_lists, ListIndex).  Radius search over the lists -- IVFIndex.radius_search / radius_count / near_duplicates / dedup -- is
-coati_amd.ivf_radius (include/coati_ivf_radius.h).  Out of scope: add() after build (rebuild instead), more than 4096 lists, storage below fp8, fp8 centres,
+coati_amd.ivf_radius (include/coati_ivf_radius.h).  Out of scope: add() after build (rebuild instead), more than 4096 lists, storage below fp8 inside the lists (coati_amd.pq.PQIndex is exhaustive, and has add()), fp8 centres,
 several GPUs.  The reference has no counterpart."""
 import torch
 

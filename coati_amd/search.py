@@ -330,6 +330,15 @@ class EmbeddingIndex:
         from .fp8_index import Fp8Index
         return Fp8Index.build(self, keep_rows=keep_rows)
 
+    def pq(self, keep_rows=True, seed=0, iters=20, sample=65536, codebooks=None):
+        """A coati_amd.pq.PQIndex over the rows present now: every row as one code byte per 8 dimensions (16 times fewer bytes) under code
+        books fitted on these rows (seeded k-means per sub-space over at most `sample` of them) or given as `codebooks`, searched in two
+        stages -- a stream over the codes keeps oversample * k candidates, their exact scores from the bf16 rows decide.  keep_rows=True
+        holds a view of these bf16 rows; keep_rows=False nothing but codes and bias (stage 1 alone).  Rows added or removed afterwards
+        are not seen by it.  dim_padded <= 256."""
+        from .pq import PQIndex
+        return PQIndex.build(self, keep_rows=keep_rows, seed=seed, iters=iters, sample=sample, codebooks=codebooks)
+
     def radius_count(self, queries, threshold, row_below=None):
         """int64 [Q]: how many live rows score >= threshold for each query (threshold, row_below: as in radius_search) -- the count pass
         of coati_amd.radius alone; nothing is allocated per hit."""
