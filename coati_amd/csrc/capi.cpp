@@ -17,6 +17,7 @@
 #include "../../include/coati_ivf8.h"
 #include "../../include/coati_ivf_radius.h"
 #include "../../include/coati_pq.h"
+#include "../../include/coati_ivfpq.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -448,6 +449,15 @@ int coati_pq_topk(const uint8_t* codes, int64_t N, int E, const uint16_t* codebo
 }
 int coati_pq_k_max(int E) { return pq_k_max(E); }
 int coati_pq_slices(int64_t N, int E, int Q, int k) { return pq_slices(N, E, Q, k); }
+// IVF-PQ search (include/coati_ivfpq.h)
+int coati_ivfpq_scan(const uint8_t* codes, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                     const uint16_t* centres, const uint16_t* codebook, const uint16_t* q, int Q, const int32_t* pair_q,
+                     const int32_t* pair_off, const int32_t* item_off, int64_t P, int k, float alpha, int seg_rows, int segs,
+                     float* part_score, int32_t* part_row, int blocks, void* stream) {
+  return launch_ivfpq_scan(codes, ids, bias, list_off, M, E, L, centres, codebook, q, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs,
+                           part_score, part_row, blocks, S_(stream));
+}
+int coati_ivfpq_k_max(int E) { return ivfpq_k_max(E); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

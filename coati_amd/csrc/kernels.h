@@ -458,6 +458,13 @@ int launch_pq_topk(const unsigned char* codes, long long N, int E, const bf16_t*
                    float alpha, int S, float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s);
 int pq_k_max(int E);                                   // host only: the largest k at this E
 int pq_slices(long long N, int E, int Q, int k);       // host only: the default S
+// IVF-PQ search (ivfpq.hip, include/coati_ivfpq.h): launch_ivf_scan's tables, partial lists and limits over positions stored as codes
+// of the residual against centres [L, E] under one codebook; the score is launch_ivf_scan's at width 2 E on [centre | entry] and [q | q]
+int launch_ivfpq_scan(const unsigned char* codes, const int* ids, const float* bias, const int* list_off, long long M, int E, int L,
+                      const bf16_t* centres, const bf16_t* codebook, const bf16_t* q, int Q, const int* pair_q, const int* pair_off,
+                      const int* item_off, long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks,
+                      hipStream_t s);
+int ivfpq_k_max(int E);                                // host only: the largest k at this E
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

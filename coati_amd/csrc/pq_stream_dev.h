@@ -16,17 +16,21 @@
 // it is the lane's -- so the four lane groups of a row read the same dwords.  A row >= N is read at row N - 1 (inside the allocation)
 // and masked by a -inf bias after the MFMA; a slab past the last iteration is never loaded, its registers keep code 0 (entry 0 of the
 // sub-space: inside the code book) and its fragments are never multiplied.
+//
+// START (ivfpq.hip: residual codes inside inverted lists): every slab's accumulator starts from start[p] -- the caller's MFMA chain over
+// a part of the row that all rows of the range share, left in all four registers of the lane -- instead of zero, and the k-steps of
+// the entries continue that chain.  Without it (pq.hip) every slab starts from zero and `start` is not read.
 #pragma once
 #include "topk_stream_dev.h"
 
 // Rows [r_begin, r_end) of codes [N, E / 8] (both bounds workgroup-uniform; an empty range leaves empty lists) under the code book cb
 // (LDS, [E / 8][256] entries of 16 bytes, complete and behind a barrier when this is called or, as here, behind this function's first
-// barrier) against the B fragments bq of panels p < np: topk_stream's arguments and topk_stream's result otherwise.
-template <int KSMAX, int NP>
+// barrier) against the B fragments bq of panels p < np: topk_stream's arguments and topk_stream's result otherwise.  start [NP]: see START.
+template <int KSMAX, int NP, bool START = false>
 __device__ __forceinline__ void pq_stream(const unsigned char* __restrict__ codes, long long N, int E, const uint4* cb,
                                           const float* __restrict__ bias, const bf16x8 (&bq)[NP][KSMAX], int np, const bool (&stored)[NP],
                                           long long r_begin, long long r_end, float alpha, int k, int cap, topk_key_t* sbuf, int* s_cnt,
-                                          float* s_thr, int* s_flag) {
+                                          float* s_thr, int* s_flag, const topk_f32x4* start = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, g = lane >> 4;
   const int ks = E >> 5, M = E >> 3, nq = 16 * np;
   const int iters = r_end > r_begin ? (int)((r_end - r_begin + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT) : 0;
@@ -91,7 +95,12 @@ __device__ __forceinline__ void pq_stream(const unsigned char* __restrict__ code
 
     topk_f32x4 acc[NP];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = topk_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int p = 0; p < NP; ++p) {
+      if constexpr (START)
+        acc[p] = start[p];
+      else
+        acc[p] = topk_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int s = 0; s < KSMAX; ++s) {
       if (s < ks) {

@@ -30,14 +30,15 @@ def build_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 102
     that many inverted lists over the rows (k-means with `iters`, `seed`) instead of the exact EmbeddingIndex; fp8: return a
     coati_amd.fp8_index.Fp8Index over the rows (e4m3 bytes searched first, the bf16 rows kept for the exact re-ranking); nlist with
     list_dtype="fp8": a coati_amd.ivf8.Ivf8Index, the inverted lists stored as e4m3 bytes and the bf16 rows kept for the re-ranking;
-    nearest_smiles takes any of them."""
-    if list_dtype not in ("bf16", "fp8"):
-        raise ValueError(f'build_index: list_dtype={list_dtype!r} is not "bf16" or "fp8"')
+    nlist with list_dtype="pq": a coati_amd.ivfpq.IvfPqIndex, the lists stored as PQ codes of the rows' residuals (code books fitted with
+    `seed`, `iters`), the bf16 rows kept likewise; nearest_smiles takes any of them."""
+    if list_dtype not in ("bf16", "fp8", "pq"):
+        raise ValueError(f'build_index: list_dtype={list_dtype!r} is not "bf16", "fp8" or "pq"')
     if fp8 and nlist is not None:
         raise ValueError('build_index: fp8=True is the exhaustive Fp8Index and nlist= an inverted file; for inverted lists of fp8 rows '
                          'pass nlist= with list_dtype="fp8"')
-    if list_dtype == "fp8" and nlist is None:
-        raise ValueError('build_index: list_dtype="fp8" needs nlist=')
+    if list_dtype != "bf16" and nlist is None:
+        raise ValueError(f'build_index: list_dtype="{list_dtype}" needs nlist=')
     index = EmbeddingIndex(encoder.embed_dim, metric=metric, device=encoder.device, keep_f32=keep_f32)
     kept: List[str] = []
     for batch in batch_indexable(smiles, batch_size):
@@ -49,6 +50,8 @@ def build_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 102
             raise RuntimeError(f"build_index: {len(usable)} usable strings gave {emb.shape[0]} embeddings")
         index.add(emb)
         kept += usable
+    if nlist is not None and list_dtype == "pq":
+        return index.ivfpq(nlist, iters=iters, seed=seed, pq_seed=seed, pq_iters=iters), kept
     if nlist is not None:
         return index.ivf(nlist, iters=iters, seed=seed, fp8=list_dtype == "fp8"), kept
     if fp8:
@@ -81,7 +84,7 @@ def nearest_smiles(queries: Union[List[str], torch.Tensor], index, kept: List[st
                    canon_smiles=None) -> List[List[Tuple[str, float]]]:
     """Per query its k nearest library strings as (string, score), best first (fewer when the index has fewer rows left).  queries: a
     list of SMILES (one that does not canonicalise or tokenize gets an empty list) or embeddings [Q, E], e.g. encode_points'.  index: an
-    EmbeddingIndex, an IVFIndex (then over its default nprobe lists), an Fp8Index or a PQIndex (then at its default oversample) or an Ivf8Index (both defaults)."""
+    EmbeddingIndex, an IVFIndex (then over its default nprobe lists), an Fp8Index or a PQIndex (then at its default oversample) or an Ivf8Index or IvfPqIndex (both defaults)."""
     where, emb = _query_embeddings("nearest_smiles", queries, index, kept, encoder, tokenizer, canon_smiles)
     out: List[List[Tuple[str, float]]] = [[] for _ in where]
     if emb is None:

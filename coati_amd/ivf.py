@@ -13,8 +13,9 @@ lists the result IS EmbeddingIndex.search's.  Nothing depends on the launch geom
 "dot" has no nearest centre and raises.  There is no CPU fallback.  Lists of e4m3 bytes with an exact bf16 re-scoring are
 coati_amd.ivf8.Ivf8Index (index.ivf(nlist, fp8=True), ivf.fp8(index)): the same lists, probe tables and merge, built on the helpers
 below (make_lists, ListIndex).  Radius search over the lists -- IVFIndex.radius_search / radius_count / near_duplicates / dedup -- is
-coati_amd.ivf_radius (include/coati_ivf_radius.h).  Out of scope: add() after build (rebuild instead), more than 4096 lists, storage below fp8 inside the lists (coati_amd.pq.PQIndex is exhaustive, and has add()), fp8 centres,
-several GPUs.  The reference has no counterpart."""
+coati_amd.ivf_radius (include/coati_ivf_radius.h).  Lists of PQ codes of the rows' residuals are
+coati_amd.ivfpq.IvfPqIndex (index.ivfpq(nlist), ivf.pq(index)), on the same helpers.  Out of scope: add() after build (rebuild instead),
+more than 4096 lists, fp8 centres, several GPUs.  The reference has no counterpart."""
 import torch
 
 from . import _lib, cluster
@@ -92,7 +93,7 @@ def make_lists(what, index, nlist, iters=20, seed=0, centres=None, assign=None):
 
 
 class ListIndex:
-    """What IVFIndex and coati_amd.ivf8.Ivf8Index share: the lists (centres, ids, sizes, offsets), the coarse step, the checks of a
+    """What IVFIndex, coati_amd.ivf8.Ivf8Index and coati_amd.ivfpq.IvfPqIndex share: the lists (centres, ids, sizes, offsets), the coarse step, the checks of a
     search's arguments and the scan + merge loop over chunks of queries.  A subclass stores the rows and supplies the scan call."""
 
     def _init_lists(self, dim, dim_padded, metric, n, centres, ids, sizes, device):
@@ -281,6 +282,13 @@ class IVFIndex(ListIndex):
         the second stage then re-scores the candidates from (a view); without it the result is stage 1's."""
         from .ivf8 import Ivf8Index
         return Ivf8Index.from_ivf(self, index)
+
+    def pq(self, index=None, pq_seed=0, pq_iters=20, sample=65536, codebooks=None):
+        """A coati_amd.ivfpq.IvfPqIndex of these lists: the stored rows as PQ codes of their residuals against the lists' centres, under
+        code books fitted on a seeded sample of the residuals or given.  index: the source EmbeddingIndex, whose bf16 rows the second stage
+        then re-scores the candidates from (a view); without it the result is stage 1's."""
+        from .ivfpq import IvfPqIndex
+        return IvfPqIndex.from_ivf(self, index, pq_seed=pq_seed, pq_iters=pq_iters, sample=sample, codebooks=codebooks)
 
     @property
     def vectors(self):

@@ -16,7 +16,7 @@ index's for "cosine"; for "l2" it is -|x_hat|^2 of the dequantised row (summed i
 
 "dot" has no nearest centre and raises.  There is no CPU fallback for search().  Out of scope: fp8 centres or an fp8 coarse step,
 re-scoring from bf16 rows in list order or in host memory, add() after build, R > 128, radius search, clustering or property heads over
-fp8 lists, per-block scales, fp6 / fp4, product quantisation inside the lists (coati_amd.pq.PQIndex is exhaustive), more than 4096 lists, several GPUs.  The reference has no counterpart."""
+fp8 lists, per-block scales, fp6 / fp4, more than 4096 lists, several GPUs.  Product quantisation inside the lists is coati_amd.ivfpq.IvfPqIndex.  The reference has no counterpart."""
 import torch
 
 from . import _lib

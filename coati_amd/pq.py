@@ -20,7 +20,8 @@ every operation rounded on its own, ascending dimension order, the lowest index 
 and "cosine"; for "l2" it is -|x_hat|^2 of the reconstructed row (summed in float64, stored as f32), so that its score is the negated
 squared distance to the reconstructed row; -inf once removed.
 
-There is no CPU fallback for search().  Out of scope: PQ inside inverted lists (IVF-PQ), residual or rotated PQ, sub-vectors other than 8
+There is no CPU fallback for search().  Codes of the rows' residuals inside inverted lists (IVF-PQ) are coati_amd.ivfpq.IvfPqIndex, built
+on encode_rows / encode_device, fit_codebooks and reconstruct below.  Out of scope: rotated PQ, sub-vectors other than 8
 dimensions or code counts other than 256, dim_padded > 256, radius search, clustering or property heads over codes, several GPUs,
 re-scoring from rows in host memory, add() on a snapshot that holds a view of another index's rows.  The reference has no counterpart."""
 import torch

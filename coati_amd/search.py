@@ -322,6 +322,15 @@ class EmbeddingIndex:
         from .ivf import IVFIndex
         return IVFIndex.build(self, nlist, iters=iters, seed=seed, centres=centres)
 
+    def ivfpq(self, nlist, iters=20, seed=0, centres=None, keep_rows=True, pq_seed=0, pq_iters=20, sample=65536, codebooks=None):
+        """A coati_amd.ivfpq.IvfPqIndex over the live rows: ivf(nlist, iters, seed, centres)'s lists, every row stored as one code byte
+        per 8 dimensions of its RESIDUAL (row minus its list's centre) under one set of code books fitted on the residuals of at most
+        `sample` rows (pq_seed, pq_iters) or given as `codebooks`; the candidates re-scored from these bf16 rows (keep_rows=True: a view of
+        them) or stage 1 alone (keep_rows=False).  Rows added or removed afterwards are not seen by it.  dim_padded <= 256."""
+        from .ivfpq import IvfPqIndex
+        return IvfPqIndex.build(self, nlist, iters=iters, seed=seed, centres=centres, keep_rows=keep_rows, pq_seed=pq_seed, pq_iters=pq_iters,
+                                sample=sample, codebooks=codebooks)
+
     def fp8(self, keep_rows=True):
         """A coati_amd.fp8_index.Fp8Index over the rows present now: every row as e4m3 bytes plus one scale (half the bytes), searched in
         two stages -- a stream over the bytes keeps oversample * k candidates, their exact scores from the bf16 rows decide.
