@@ -18,6 +18,7 @@
 #include "../../include/coati_ivf_radius.h"
 #include "../../include/coati_pq.h"
 #include "../../include/coati_ivfpq.h"
+#include "../../include/coati_search4.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -458,6 +459,17 @@ int coati_ivfpq_scan(const uint8_t* codes, const int32_t* ids, const float* bias
                            part_score, part_row, blocks, S_(stream));
 }
 int coati_ivfpq_k_max(int E) { return ivfpq_k_max(E); }
+// four-bit search (include/coati_search4.h)
+int coati_quant_rows_fp4(const uint16_t* x, int64_t n, int E, uint8_t* codes, uint8_t* scales, void* stream) {
+  return launch_quant_rows_fp4(x, n, E, codes, scales, S_(stream));
+}
+int coati_search4_topk(const uint8_t* codes, const uint8_t* scales, int64_t N, int E4, const float* bias, const uint8_t* q8,
+                       const float* qscale, int Q, int k, float alpha, int S, float* part_score, int32_t* part_row, float* out_score,
+                       int64_t* out_row, void* stream) {
+  return launch_search4_topk(codes, scales, N, E4, bias, q8, qscale, Q, k, alpha, S, part_score, part_row, out_score,
+                             reinterpret_cast<long long*>(out_row), S_(stream));
+}
+int coati_search4_slices(int64_t N, int Q, int k) { return search4_slices(N, Q, k); }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

@@ -465,6 +465,13 @@ int launch_ivfpq_scan(const unsigned char* codes, const int* ids, const float* b
                       const int* item_off, long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks,
                       hipStream_t s);
 int ivfpq_k_max(int E);                                // host only: the largest k at this E
+// four-bit search (search4.hip, include/coati_search4.h): rows as e2m1 nibbles [N, E4 / 2] + E8M0 block scales [N, E4 / 32]; the
+// quantiser, and the streaming stage over them (launch_search_topk's partial lists, merged by launch_search_merge)
+int launch_quant_rows_fp4(const bf16_t* x, long long n, int E, unsigned char* codes, unsigned char* scales, hipStream_t s);
+int launch_search4_topk(const unsigned char* codes, const unsigned char* scales, long long N, int E4, const float* bias, const unsigned char* q,
+                        const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
+                        long long* out_row, hipStream_t s);
+int search4_slices(long long N, int Q, int k);   // host only: the default S
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

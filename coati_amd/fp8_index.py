@@ -17,9 +17,10 @@ quantised the same way.  Stage 1's bias is the index's for "dot" and "cosine"; f
 in float64, stored as f32), so that its score is the negated squared distance between the dequantised operands.
 
 There is no CPU fallback for search().  The same storage inside inverted lists -- the rows of the probed lists only, the same second
-stage -- is coati_amd.ivf8.Ivf8Index, which uses this module's quantiser and rescore_candidates.  Storage below fp8 is coati_amd.pq.PQIndex
-(product quantisation, one byte per 8 dimensions), which also has add() after build.  Out of scope here: add() after build (rebuild
-instead), radius search, clustering or property heads over fp8 rows, fp6 / fp4, per-block scales, bf16 rows kept in host memory, R > 128.  The reference has no counterpart."""
+stage -- is coati_amd.ivf8.Ivf8Index, which uses this module's quantiser and rescore_candidates.  Storage below fp8 is
+coati_amd.fp4_index.Fp4Index (e2m1 nibbles with one scale byte per block of 32, the same second stage) and coati_amd.pq.PQIndex (product
+quantisation, one byte per 8 dimensions), which also has add() after build.  Out of scope here: add() after build (rebuild instead),
+radius search, clustering or property heads over fp8 rows, fp6, bf16 rows kept in host memory, R > 128.  The reference has no counterpart."""
 import torch
 
 from . import _lib

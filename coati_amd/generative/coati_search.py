@@ -68,6 +68,15 @@ def build_pq_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 
     return index.pq(keep_rows=keep_rows, seed=seed, iters=iters), kept
 
 
+def build_fp4_index(smiles: Iterable[str], encoder, tokenizer, batch_size: int = 1024, metric: str = "cosine", canon_smiles=None,
+                    keep_rows: bool = True):
+    """build_index's rows as a coati_amd.fp4_index.Fp4Index and kept, the strings of its rows: e2m1 nibbles with one scale byte per 32
+    elements; keep_rows=True keeps the bf16 rows for the exact re-ranking, keep_rows=False the codes and scales alone.  nearest_smiles
+    takes it."""
+    index, kept = build_index(smiles, encoder, tokenizer, batch_size=batch_size, metric=metric, canon_smiles=canon_smiles)
+    return index.fp4(keep_rows=keep_rows), kept
+
+
 def _query_embeddings(what, queries, index, kept, encoder, tokenizer, canon_smiles):
     """(where, emb): per query its row of emb (None: a string that does not canonicalise or tokenize), emb None when no query is usable"""
     if len(kept) != len(index):
@@ -84,7 +93,7 @@ def nearest_smiles(queries: Union[List[str], torch.Tensor], index, kept: List[st
                    canon_smiles=None) -> List[List[Tuple[str, float]]]:
     """Per query its k nearest library strings as (string, score), best first (fewer when the index has fewer rows left).  queries: a
     list of SMILES (one that does not canonicalise or tokenize gets an empty list) or embeddings [Q, E], e.g. encode_points'.  index: an
-    EmbeddingIndex, an IVFIndex (then over its default nprobe lists), an Fp8Index or a PQIndex (then at its default oversample) or an Ivf8Index or IvfPqIndex (both defaults)."""
+    EmbeddingIndex, an IVFIndex (then over its default nprobe lists), an Fp8Index, an Fp4Index or a PQIndex (then at its default oversample) or an Ivf8Index or IvfPqIndex (both defaults)."""
     where, emb = _query_embeddings("nearest_smiles", queries, index, kept, encoder, tokenizer, canon_smiles)
     out: List[List[Tuple[str, float]]] = [[] for _ in where]
     if emb is None:

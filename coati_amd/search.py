@@ -339,6 +339,15 @@ class EmbeddingIndex:
         from .fp8_index import Fp8Index
         return Fp8Index.build(self, keep_rows=keep_rows)
 
+    def fp4(self, keep_rows=True):
+        """A coati_amd.fp4_index.Fp4Index over the rows present now: every row as e2m1 nibbles plus one scale byte per 32 elements (a
+        quarter of the bytes and one in 32; dim_padded <= 512, stored in multiples of 128), searched in two stages -- a stream over
+        the nibbles keeps oversample * k candidates, their exact scores from the bf16 rows decide.  keep_rows=True holds a view of these
+        bf16 rows; keep_rows=False nothing but codes, scales and bias (stage 1 alone).  Rows added or removed afterwards are not seen
+        by it."""
+        from .fp4_index import Fp4Index
+        return Fp4Index.build(self, keep_rows=keep_rows)
+
     def pq(self, keep_rows=True, seed=0, iters=20, sample=65536, codebooks=None):
         """A coati_amd.pq.PQIndex over the rows present now: every row as one code byte per 8 dimensions (16 times fewer bytes) under code
         books fitted on these rows (seeded k-means per sub-space over at most `sample` of them) or given as `codebooks`, searched in two
