@@ -21,13 +21,12 @@
 // list_off -- a slot no item wrote is never read) become 64-bit keys (score key << 32 | ~row) in LDS, unique over the query since a row
 // lives in one list.  An 8-pass radix select finds the k-th largest key, the <= k survivors are ranked by counting.  Key descending is
 // score descending, original row ascending among equal scores.
-#include "topk_stream_dev.h"
+#include "search_host.h"
 
 #define IVF_E_MAX 512
 #define IVF_L_MAX 4096
 #define IVF_NPROBE_MAX 128
 #define IVF_MERGE_MAX 16384    // nprobe * segs * k: the merge's row of 64-bit keys in 128 KiB of LDS
-#define IVF_DEVICE_SLOTS 512   // work items that fill the device: 256 CUs, two workgroups each
 #define IVF_SEG_MIN 128        // rows of the shortest segment ivf_plan proposes
 #define IVF_GRID_MAX 2048
 
@@ -231,16 +230,7 @@ int launch_ivf_merge(const float* part_score, const int* part_row, const int* pr
   COATI_CHECK_SHAPE(nprobe >= 1 && nprobe <= IVF_NPROBE_MAX, "ivf_merge: nprobe=%d outside 1 .. %d", nprobe, IVF_NPROBE_MAX);
   COATI_CHECK_SHAPE((long long)nprobe * segs * k <= IVF_MERGE_MAX, "ivf_merge: nprobe=%d lists of segs=%d segments of k=%d exceed nprobe * segs * k <= %d",
                     nprobe, segs, k, IVF_MERGE_MAX);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       IVF_MERGE_MAX * (int)sizeof(topk_key_t));
-    if (e != hipSuccess) {
-      coati_set_error("ivf_merge: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
+  COATI_TRY(max_dynamic_lds<ivf_merge_kernel>("ivf_merge", IVF_MERGE_MAX * (int)sizeof(topk_key_t)));
   hipLaunchKernelGGL(ivf_merge_kernel, dim3(Q), dim3(256), (size_t)nprobe * segs * k * sizeof(topk_key_t), s, part_score, part_row, probes,
                      pair_slot, P, list_off, L, nprobe, k, seg_rows, segs, out_score, out_row);
   COATI_LAUNCH_CHECK("ivf_merge");
@@ -257,7 +247,7 @@ long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k) {
   const long long by_merge = IVF_MERGE_MAX / ((long long)nprobe * k);
   COATI_CHECK_SHAPE(by_merge >= 1, "ivf_plan: nprobe=%d times k=%d exceeds nprobe * segs * k <= %d", nprobe, k, IVF_MERGE_MAX);
   const long long pairs = (long long)Q * nprobe;
-  long long segs = (IVF_DEVICE_SLOTS + pairs - 1) / pairs;
+  long long segs = (TOPK_DEVICE_SLOTS + pairs - 1) / pairs;
   segs = segs < by_merge ? segs : by_merge;
   long long seg_rows = ((max_list_rows + segs - 1) / segs + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT * TOPK_ROWS_IT;
   seg_rows = seg_rows > IVF_SEG_MIN ? seg_rows : IVF_SEG_MIN;

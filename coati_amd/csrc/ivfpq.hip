@@ -31,6 +31,7 @@
 // from one LDS word behind a barrier.  A column without a query only has a zero fragment and stored = false.  The barrier after the
 // write-out puts the next item's reset of the counts behind this item's reads of them.
 #include "pq_stream_dev.h"
+#include "search_host.h"
 
 #define IVFPQ_E_MAX 256
 #define IVFPQ_LDS_BYTES (160 * 1024)   // a CU's LDS, which one workgroup may take whole
@@ -115,16 +116,7 @@ static int ivfpq_launch(const unsigned char* codes, const int* ids, const float*
                         hipStream_t s) {
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
   const size_t lds = ivfpq_lds(E, k);     // <= IVFPQ_LDS_BYTES: k <= ivfpq_k_max(E)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivfpq_scan_kernel<KSMAX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       IVFPQ_LDS_BYTES);
-    if (e != hipSuccess) {
-      coati_set_error("ivfpq_scan: hipFuncSetAttribute(%d bytes of LDS) failed: %s", IVFPQ_LDS_BYTES, hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
+  COATI_TRY(max_dynamic_lds<ivfpq_scan_kernel<KSMAX>>("ivfpq_scan", IVFPQ_LDS_BYTES));
   hipLaunchKernelGGL((ivfpq_scan_kernel<KSMAX>), dim3(grid), dim3(256), lds, s, codes, ids, bias, list_off, M, E, L, centres, codebook, q, Q, pair_q,
                      pair_off, item_off, P, k, alpha, seg_rows, segs, cap, part_score, part_row);
   COATI_LAUNCH_CHECK("ivfpq_scan");

@@ -15,9 +15,9 @@
 // (512 E bytes), the lists [16 NP][cap] of 8-byte keys, then counts, thresholds and the two flags (PQ_WORDS_BYTES).  NP = 2 up to
 // E = 128 (a fragment read from LDS then feeds two MFMAs), NP = 1 above, where the code book leaves room for 16 lists only.
 #include "pq_stream_dev.h"
+#include "search_host.h"
 
 #define PQ_E_MAX 256
-#define PQ_MERGE_MAX 30720          // S * k: search_merge_kernel's row of keys
 #define PQ_LDS_BYTES (160 * 1024)   // a CU's LDS, which one workgroup may take whole
 #define PQ_WORDS_BYTES(NP) (16 * (NP) * 8 + 8)   // counts and thresholds [16 NP], flags [2]
 #define PQ_SLICE_ROWS_MIN 16384     // a slice's code bytes (E / 8 a row) are at least 4 times the 512 E bytes of code book its workgroup loads
@@ -79,15 +79,7 @@ int launch_pq_encode(const bf16_t* x, long long n, int E, const bf16_t* codebook
   COATI_CHECK_ARG(x && codebook && codes, "pq_encode: null operand");
   COATI_TRY(pq_check_E("pq_encode", E));
   COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "pq_encode: n=%lld outside 1 .. 2^31 - 1", n);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pq_encode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 512 * PQ_E_MAX);
-    if (e != hipSuccess) {
-      coati_set_error("pq_encode: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
+  COATI_TRY(max_dynamic_lds<pq_encode_kernel>("pq_encode", 512 * PQ_E_MAX));
   const long long blocks = (n + PQ_ENCODE_ROWS - 1) / PQ_ENCODE_ROWS;
   hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), (size_t)512 * E, s, x, n, E, codebook, codes);
   COATI_LAUNCH_CHECK("pq_encode");
@@ -156,20 +148,9 @@ static int pq_launch(const unsigned char* codes, long long N, int E, const bf16_
                      float alpha, int S, float* part_score, int* part_row, hipStream_t s) {
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
   const size_t lds = pq_lds(E, k);        // <= PQ_LDS_BYTES: k <= pq_k_max(E)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pq_topk_kernel<KSMAX, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       PQ_LDS_BYTES);
-    if (e != hipSuccess) {
-      coati_set_error("pq_topk: hipFuncSetAttribute(%d bytes of LDS) failed: %s", PQ_LDS_BYTES, hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
-  // slices of whole iterations; a slice past the end of the library (S > N / TOPK_ROWS_IT) writes padding only
-  const long long slice_rows = (N + (long long)S * TOPK_ROWS_IT - 1) / ((long long)S * TOPK_ROWS_IT) * TOPK_ROWS_IT;
+  COATI_TRY((max_dynamic_lds<pq_topk_kernel<KSMAX, NP>>("pq_topk", PQ_LDS_BYTES)));
   hipLaunchKernelGGL((pq_topk_kernel<KSMAX, NP>), dim3(cdiv(Q, 16 * NP), S), dim3(256), lds, s, codes, N, E, codebook, bias, q, Q, k, alpha, S,
-                     slice_rows, cap, part_score, part_row);
+                     topk_slice_rows(N, S), cap, part_score, part_row);
   COATI_LAUNCH_CHECK("pq_topk");
   return COATI_OK;
 }
@@ -178,7 +159,7 @@ int launch_pq_topk(const unsigned char* codes, long long N, int E, const bf16_t*
                    float alpha, int S, float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s) {
   COATI_CHECK_ARG(codes && codebook && q && part_score && part_row && out_score && out_row, "pq_topk: null operand");
   COATI_TRY(pq_check("pq_topk", N, E, Q, k));
-  COATI_CHECK_SHAPE(S >= 1 && (long long)S * k <= PQ_MERGE_MAX, "pq_topk: S=%d slices of k=%d exceed S * k <= %d", S, k, PQ_MERGE_MAX);
+  COATI_CHECK_SHAPE(S >= 1 && (long long)S * k <= TOPK_MERGE_MAX, "pq_topk: S=%d slices of k=%d exceed S * k <= %d", S, k, TOPK_MERGE_MAX);
   if (pq_np(E) == 2)
     COATI_TRY((pq_launch<4, 2>(codes, N, E, codebook, bias, q, Q, k, alpha, S, part_score, part_row, s)));
   else
@@ -192,7 +173,7 @@ int pq_slices(long long N, int E, int Q, int k) {
   COATI_TRY(pq_check("pq_slices", N, E, Q, k));
   const long long tiles = ((long long)Q + 16 * pq_np(E) - 1) / (16 * pq_np(E));
   const long long slots = 256 * (long long)(PQ_LDS_BYTES / pq_lds(E, k));
-  const long long by_rows = (N + PQ_SLICE_ROWS_MIN - 1) / PQ_SLICE_ROWS_MIN, by_merge = PQ_MERGE_MAX / k;
+  const long long by_rows = (N + PQ_SLICE_ROWS_MIN - 1) / PQ_SLICE_ROWS_MIN, by_merge = TOPK_MERGE_MAX / k;
   long long S = (slots + tiles - 1) / tiles;
   S = S < by_rows ? S : by_rows;
   S = S < by_merge ? S : by_merge;

@@ -27,10 +27,9 @@
 #include <climits>
 #include <type_traits>
 
-#include "topk_stream_dev.h"
+#include "search_host.h"
 
 #define RADIUS_E_MAX 512
-#define RADIUS_DEVICE_SLOTS 512   // workgroups that fill the device: 256 CUs, two workgroups each
 #define RADIUS_S_MAX 65535        // gridDim.y
 
 __device__ __forceinline__ int radius_bytesum(unsigned x) { return (int)((x * 0x01010101u) >> 24); }   // (of four bytes that sum to < 256)
@@ -226,10 +225,8 @@ static int radius_launch(const char* what, const bf16_t* lib, long long N, int E
                          const float* sub, int clamp0, const float* thr, const int* row_hi, int S,
                          std::conditional_t<FILL, const int*, int*> counts, const long long* offsets, float* out_score, long long* out_row,
                          hipStream_t s) {
-  // slices of whole iterations; a slice past the end of the library (S > N / TOPK_ROWS_IT) has no hits
-  const long long slice_rows = (N + (long long)S * TOPK_ROWS_IT - 1) / ((long long)S * TOPK_ROWS_IT) * TOPK_ROWS_IT;
   hipLaunchKernelGGL((radius_kernel<KSMAX, NP, FILL>), dim3(cdiv(Q, 16 * NP), S), dim3(256), 0, s, lib, N, E, bias, q, Q, alpha, sub, clamp0, thr,
-                     row_hi, S, slice_rows, counts, offsets, out_score, out_row);
+                     row_hi, S, topk_slice_rows(N, S), counts, offsets, out_score, out_row);
   COATI_LAUNCH_CHECK(what);
   return COATI_OK;
 }
@@ -267,7 +264,7 @@ int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias,
 int radius_slices(long long N, int Q) {
   COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31) && Q >= 1, "radius_slices: N=%lld Q=%d out of range", N, Q);
   const long long tiles = ((long long)Q + 63) / 64, by_rows = (N + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT;
-  long long S = (RADIUS_DEVICE_SLOTS + tiles - 1) / tiles;
+  long long S = (TOPK_DEVICE_SLOTS + tiles - 1) / tiles;
   S = S < by_rows ? S : by_rows;
   S = S < RADIUS_S_MAX ? S : RADIUS_S_MAX;
   return (int)(S > 1 ? S : 1);

@@ -11,11 +11,9 @@
 //
 // search_merge_kernel, one workgroup per query: the samplers' radix select (decode_dev.h) over the query's S * k partial scores.
 // Candidate position order is (slice, rank) = ascending row index among equal scores, so the select's "index ascending" is the tie rule.
-#include "topk_stream_dev.h"
+#include "search_host.h"
 
 #define SEARCH_E_MAX 512
-#define SEARCH_MERGE_MAX 30720   // S * k: the merge's row of keys in 120 KiB of LDS
-#define SEARCH_DEVICE_SLOTS 512  // workgroups that fill the device: 256 CUs, two workgroups each where the LDS allows
 
 template <int KSMAX, int NP>
 __global__ __launch_bounds__(256) void search_topk_kernel(const bf16_t* __restrict__ lib, long long N, int E, const float* __restrict__ bias,
@@ -65,11 +63,8 @@ __global__ __launch_bounds__(256) void search_merge_kernel(const float* __restri
 }
 
 static int search_check(long long N, int E, int Q, int k, int S) {
-  COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX, "search_topk: k=%d outside 1 .. %d", k, TOPK_MAX);
+  COATI_TRY(topk_check("search_topk", N, Q, k, S));
   COATI_CHECK_SHAPE(E >= 32 && E <= SEARCH_E_MAX && E % 32 == 0, "search_topk: E=%d is not a multiple of 32 in 32 .. %d", E, SEARCH_E_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "search_topk: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(Q >= 1, "search_topk: Q=%d < 1", Q);
-  COATI_CHECK_SHAPE(S >= 1 && (long long)S * k <= SEARCH_MERGE_MAX, "search_topk: S=%d slices of k=%d exceed S * k <= %d", S, k, SEARCH_MERGE_MAX);
   return COATI_OK;
 }
 
@@ -78,20 +73,9 @@ static int search_launch(const bf16_t* lib, long long N, int E, const float* bia
                          float* part_score, int* part_row, hipStream_t s) {
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
   const size_t lds = (size_t)16 * NP * cap * sizeof(topk_key_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_topk_kernel<KSMAX, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       16 * NP * (TOPK_MAX + 2 * TOPK_ROWS_IT) * (int)sizeof(topk_key_t));
-    if (e != hipSuccess) {
-      coati_set_error("search_topk: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
-  // slices of whole iterations; a slice past the end of the library (S > N / TOPK_ROWS_IT) writes padding only
-  const long long slice_rows = (N + (long long)S * TOPK_ROWS_IT - 1) / ((long long)S * TOPK_ROWS_IT) * TOPK_ROWS_IT;
+  COATI_TRY((max_dynamic_lds<search_topk_kernel<KSMAX, NP>>("search_topk", 16 * NP * (TOPK_MAX + 2 * TOPK_ROWS_IT) * (int)sizeof(topk_key_t))));
   hipLaunchKernelGGL((search_topk_kernel<KSMAX, NP>), dim3(cdiv(Q, 16 * NP), S), dim3(256), lds, s, lib, N, E, bias, q, Q, k, alpha, S,
-                     slice_rows, cap, part_score, part_row);
+                     topk_slice_rows(N, S), cap, part_score, part_row);
   COATI_LAUNCH_CHECK("search_topk");
   return COATI_OK;
 }
@@ -104,48 +88,19 @@ int launch_search_topk(const bf16_t* lib, long long N, int E, const float* bias,
     COATI_TRY((search_launch<8, 4>(lib, N, E, bias, q, Q, k, alpha, S, part_score, part_row, s)));
   else
     COATI_TRY((search_launch<16, 2>(lib, N, E, bias, q, Q, k, alpha, S, part_score, part_row, s)));
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SEARCH_MERGE_MAX * 4);
-    if (e != hipSuccess) {
-      coati_set_error("search_topk: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(256), (size_t)S * k * 4, s, part_score, part_row, S * k, k, out_score, out_row);
-  COATI_LAUNCH_CHECK("search_merge");
-  return COATI_OK;
+  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, out_row, s);
 }
 
-// The merge alone, for a stream kernel of another file that writes the same partial lists (search8.hip): out [Q, k] from part [Q, V].
+// The merge alone, also for the stream kernels of other files that write the same partial lists (search8.hip, search4.hip, pq.hip):
+// out [Q, k] from part [Q, V].
 int launch_search_merge(const float* part_score, const int* part_row, int Q, int V, int k, float* out_score, long long* out_row, hipStream_t s) {
   COATI_CHECK_ARG(part_score && part_row && out_score && out_row, "search_merge: null operand");
-  COATI_CHECK_SHAPE(Q >= 1 && k >= 1 && k <= TOPK_MAX && V >= k && V <= SEARCH_MERGE_MAX, "search_merge: Q=%d V=%d k=%d out of range", Q, V, k);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(search_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SEARCH_MERGE_MAX * 4);
-    if (e != hipSuccess) {
-      coati_set_error("search_merge: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
+  COATI_CHECK_SHAPE(Q >= 1 && k >= 1 && k <= TOPK_MAX && V >= k && V <= TOPK_MERGE_MAX, "search_merge: Q=%d V=%d k=%d out of range", Q, V, k);
+  COATI_TRY(max_dynamic_lds<search_merge_kernel>("search_merge", TOPK_MERGE_MAX * 4));
   hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(256), (size_t)V * 4, s, part_score, part_row, V, k, out_score, out_row);
   COATI_LAUNCH_CHECK("search_merge");
   return COATI_OK;
 }
 
-// The number of slices launch_search_topk is given by default: enough workgroups to fill the device at this Q (tiles of 64 queries),
-// no slice shorter than one workgroup iteration, S * k within the merge's row.  Host arithmetic only.
-int search_slices(long long N, int Q, int k) {
-  COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX && N >= 1 && N < (1ll << 31) && Q >= 1, "search_slices: N=%lld Q=%d k=%d out of range", N, Q, k);
-  const long long tiles = ((long long)Q + 63) / 64;
-  const long long by_rows = (N + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT, by_merge = SEARCH_MERGE_MAX / k;
-  long long S = (SEARCH_DEVICE_SLOTS + tiles - 1) / tiles;
-  S = S < by_rows ? S : by_rows;
-  S = S < by_merge ? S : by_merge;
-  return (int)(S > 1 ? S : 1);
-}
+// The number of slices launch_search_topk is given by default (topk_default_slices).  Host arithmetic only.
+int search_slices(long long N, int Q, int k) { return topk_default_slices("search_slices", N, Q, k); }

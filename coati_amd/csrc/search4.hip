@@ -38,11 +38,9 @@
 // past the slice's end are read at row N - 1 and dropped by the filter.
 #include <type_traits>
 
-#include "topk_stream_dev.h"
+#include "search_host.h"
 
 #define SEARCH4_E_MAX 512
-#define SEARCH4_MERGE_MAX 30720   // S * k: search_merge_kernel's row of keys
-#define SEARCH4_DEVICE_SLOTS 512  // workgroups that fill the device
 #ifndef SEARCH4_NB
 #define SEARCH4_NB 4              // register buffers of the stream: SEARCH4_NB - 1 slabs in flight
 #endif
@@ -264,11 +262,8 @@ __global__ __launch_bounds__(256) void search4_topk_kernel(const unsigned char* 
 }
 
 static int search4_check(long long N, int E4, int Q, int k, int S) {
-  COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX, "search4_topk: k=%d outside 1 .. %d", k, TOPK_MAX);
+  COATI_TRY(topk_check("search4_topk", N, Q, k, S));
   COATI_CHECK_SHAPE(E4 >= 128 && E4 <= SEARCH4_E_MAX && E4 % 128 == 0, "search4_topk: E4=%d is not a multiple of 128 in 128 .. %d", E4, SEARCH4_E_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "search4_topk: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(Q >= 1, "search4_topk: Q=%d < 1", Q);
-  COATI_CHECK_SHAPE(S >= 1 && (long long)S * k <= SEARCH4_MERGE_MAX, "search4_topk: S=%d slices of k=%d exceed S * k <= %d", S, k, SEARCH4_MERGE_MAX);
   return COATI_OK;
 }
 
@@ -278,20 +273,9 @@ static int search4_launch(const unsigned char* codes, const unsigned char* scale
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
   // the lists of the panels this launch has: a launch of <= 16 queries takes half the tile's LDS
   const size_t lds = (size_t)16 * min(NP, cdiv(Q, 16)) * cap * sizeof(topk_key_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(search4_topk_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       16 * NP * (TOPK_MAX + 2 * TOPK_ROWS_IT) * (int)sizeof(topk_key_t));
-    if (e != hipSuccess) {
-      coati_set_error("search4_topk: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
-  // slices of whole iterations; a slice past the end of the library (S > N / TOPK_ROWS_IT) writes padding only
-  const long long slice_rows = (N + (long long)S * TOPK_ROWS_IT - 1) / ((long long)S * TOPK_ROWS_IT) * TOPK_ROWS_IT;
+  COATI_TRY((max_dynamic_lds<search4_topk_kernel<T, NP>>("search4_topk", 16 * NP * (TOPK_MAX + 2 * TOPK_ROWS_IT) * (int)sizeof(topk_key_t))));
   hipLaunchKernelGGL((search4_topk_kernel<T, NP>), dim3(cdiv(Q, 16 * NP), S), dim3(256), lds, s, codes, scales, N, bias, q, qscale, Q, k, alpha, S,
-                     slice_rows, cap, part_score, part_row);
+                     topk_slice_rows(N, S), cap, part_score, part_row);
   COATI_LAUNCH_CHECK("search4_topk");
   return COATI_OK;
 }
@@ -310,14 +294,5 @@ int launch_search4_topk(const unsigned char* codes, const unsigned char* scales,
   return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, out_row, s);
 }
 
-// The number of slices launch_search4_topk is given by default: search8_slices' arithmetic (enough workgroups to fill the device at this
-// Q, no slice shorter than one workgroup iteration, S * k within the merge's row).  Host arithmetic only.
-int search4_slices(long long N, int Q, int k) {
-  COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX && N >= 1 && N < (1ll << 31) && Q >= 1, "search4_slices: N=%lld Q=%d k=%d out of range", N, Q, k);
-  const long long tiles = ((long long)Q + 63) / 64;
-  const long long by_rows = (N + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT, by_merge = SEARCH4_MERGE_MAX / k;
-  long long S = (SEARCH4_DEVICE_SLOTS + tiles - 1) / tiles;
-  S = S < by_rows ? S : by_rows;
-  S = S < by_merge ? S : by_merge;
-  return (int)(S > 1 ? S : 1);
-}
+// The number of slices launch_search4_topk is given by default: search_slices' (topk_default_slices).  Host arithmetic only.
+int search4_slices(long long N, int Q, int k) { return topk_default_slices("search4_slices", N, Q, k); }

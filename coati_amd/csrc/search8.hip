@@ -34,11 +34,9 @@
 // in LDS by topk_compact<true>: score descending, row ascending.
 #include <type_traits>
 
-#include "topk_stream_dev.h"
+#include "search_host.h"
 
 #define SEARCH8_E_MAX 512
-#define SEARCH8_MERGE_MAX 30720   // S * k: search_merge_kernel's row of keys
-#define SEARCH8_DEVICE_SLOTS 512  // workgroups that fill the device
 #define RESCORE_R_MAX 128
 
 // ---- quantiser ---------------------------------------------------------------------------------------------------------------------
@@ -252,11 +250,8 @@ __global__ __launch_bounds__(256) void search8_topk_kernel(const unsigned char* 
 }
 
 static int search8_check(long long N, int E, int Q, int k, int S) {
-  COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX, "search8_topk: k=%d outside 1 .. %d", k, TOPK_MAX);
+  COATI_TRY(topk_check("search8_topk", N, Q, k, S));
   COATI_CHECK_SHAPE(E >= 32 && E <= SEARCH8_E_MAX && E % 32 == 0, "search8_topk: E=%d is not a multiple of 32 in 32 .. %d", E, SEARCH8_E_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "search8_topk: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(Q >= 1, "search8_topk: Q=%d < 1", Q);
-  COATI_CHECK_SHAPE(S >= 1 && (long long)S * k <= SEARCH8_MERGE_MAX, "search8_topk: S=%d slices of k=%d exceed S * k <= %d", S, k, SEARCH8_MERGE_MAX);
   return COATI_OK;
 }
 
@@ -266,20 +261,9 @@ static int search8_launch(const unsigned char* lib, const float* scale, long lon
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
   // the lists of the panels this launch has: a launch of <= 16 queries takes half the tile's LDS
   const size_t lds = (size_t)16 * min(NP, cdiv(Q, 16)) * cap * sizeof(topk_key_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(search8_topk_kernel<TMAX, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       16 * NP * (TOPK_MAX + 2 * TOPK_ROWS_IT) * (int)sizeof(topk_key_t));
-    if (e != hipSuccess) {
-      coati_set_error("search8_topk: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return COATI_EHIP;
-    }
-    attr_set = true;
-  }
-  // slices of whole iterations; a slice past the end of the library (S > N / TOPK_ROWS_IT) writes padding only
-  const long long slice_rows = (N + (long long)S * TOPK_ROWS_IT - 1) / ((long long)S * TOPK_ROWS_IT) * TOPK_ROWS_IT;
+  COATI_TRY((max_dynamic_lds<search8_topk_kernel<TMAX, NP>>("search8_topk", 16 * NP * (TOPK_MAX + 2 * TOPK_ROWS_IT) * (int)sizeof(topk_key_t))));
   hipLaunchKernelGGL((search8_topk_kernel<TMAX, NP>), dim3(cdiv(Q, 16 * NP), S), dim3(256), lds, s, lib, scale, N, E, bias, q, qscale, Q, k, alpha,
-                     S, slice_rows, cap, part_score, part_row);
+                     S, topk_slice_rows(N, S), cap, part_score, part_row);
   COATI_LAUNCH_CHECK("search8_topk");
   return COATI_OK;
 }
@@ -371,14 +355,5 @@ int launch_search_rescore(const bf16_t* lib, long long N, int E, const float* bi
   return COATI_OK;
 }
 
-// The number of slices launch_search8_topk is given by default: search_slices' arithmetic (enough workgroups to fill the device at this
-// Q, no slice shorter than one workgroup iteration, S * k within the merge's row).  Host arithmetic only.
-int search8_slices(long long N, int Q, int k) {
-  COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX && N >= 1 && N < (1ll << 31) && Q >= 1, "search8_slices: N=%lld Q=%d k=%d out of range", N, Q, k);
-  const long long tiles = ((long long)Q + 63) / 64;
-  const long long by_rows = (N + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT, by_merge = SEARCH8_MERGE_MAX / k;
-  long long S = (SEARCH8_DEVICE_SLOTS + tiles - 1) / tiles;
-  S = S < by_rows ? S : by_rows;
-  S = S < by_merge ? S : by_merge;
-  return (int)(S > 1 ? S : 1);
-}
+// The number of slices launch_search8_topk is given by default: search_slices' (topk_default_slices).  Host arithmetic only.
+int search8_slices(long long N, int Q, int k) { return topk_default_slices("search8_slices", N, Q, k); }

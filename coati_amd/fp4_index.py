@@ -29,9 +29,9 @@ import torch
 
 from . import _lib
 from . import fp8_index as _F8
-from .fp8_index import R_MAX, rescore_candidates
 from .ops import ptr, stream
-from .search import K_MAX, MERGE_MAX, SCRATCH_BYTES, finish_scores, metric_alpha, prepare_queries, scratch_pair, _check_metric
+from .search import _check_metric
+from .two_stage import FlatTwoStage
 
 E4_MAX = 512
 BLOCK = 32                       # elements per scale byte
@@ -105,9 +105,12 @@ def quantise_device(x16):
     return codes, scales
 
 
-class Fp4Index:
+class Fp4Index(FlatTwoStage):
     """The rows of an EmbeddingIndex at the time of build() as e2m1 nibbles and block scales; len() and the rows returned are the
     source's.  Attributes: dim, dim_padded, dim_stored (E4), metric, device, keep_rows."""
+    _slices_entry = "coati_search4_slices"
+    _payload = {"codes": "_codes", "scales": "_scales"}
+    _quantise_rows = staticmethod(quantise_rows)
 
     def __init__(self, dim, dim_padded, metric, codes, scales, bias, rows16=None, bias16=None, device="cuda:0"):
         _check_metric(metric)
@@ -120,15 +123,7 @@ class Fp4Index:
         if self._codes.dtype != torch.uint8 or self._codes.shape != (self._n, self.dim_stored // 2) or self._scales.dtype != torch.uint8 \
                 or self._scales.shape != (self._n, self.dim_stored // BLOCK) or self._bias.shape != (self._n,):
             raise ValueError("Fp4Index: codes, scales and bias do not match")
-        self.keep_rows = rows16 is not None
-        self._rows16 = self._bias16 = None
-        if self.keep_rows:
-            self._rows16 = rows16 if rows16.device == self.device else rows16.to(self.device)      # (a view of the source's rows stays one)
-            self._bias16 = self._bias if bias16 is None else bias16.to(self.device, torch.float32).contiguous()
-            if self._rows16.dtype != torch.bfloat16 or self._rows16.shape != (self._n, self.dim_padded) or self._bias16.shape != (self._n,) \
-                    or not self._rows16.is_contiguous():
-                raise ValueError("Fp4Index: the bf16 rows do not match the codes")
-        self._scratch = None         # the partial lists, kept between searches
+        self._adopt_rows(rows16, self._bias if bias16 is None else bias16)
 
     # ---- building ----------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -146,9 +141,6 @@ class Fp4Index:
         bias = stage1_bias(index.metric, codes, scales, bias16)
         return cls(index.dim, index.dim_padded, index.metric, codes, scales, bias, x16 if keep_rows else None, bias16 if keep_rows else None,
                    index.device)
-
-    def __len__(self):
-        return self._n
 
     @property
     def codes(self):
@@ -173,29 +165,19 @@ class Fp4Index:
         """what stage 1 holds per row: E4 / 2 code bytes, E4 / 32 scale bytes and the f32 bias"""
         return self.dim_stored // 2 + self.dim_stored // BLOCK + 4
 
-    def remove(self, rows):
-        """the rows are never returned again; len() and the other rows' indices do not change"""
-        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
-        if rows.numel() == 0:
-            return
-        if int(rows.min()) < 0 or int(rows.max()) >= self._n:
-            raise IndexError(f"Fp4Index.remove: rows outside 0 .. {self._n - 1}")
-        self._bias[rows.to(self.device)] = float("-inf")
-        if self.keep_rows:
-            self._bias16[rows.to(self.device)] = float("-inf")
+    # ---- searching (FlatTwoStage) ----------------------------------------------------------------------------------------------------
+    def _default_slices(self, qc, kk):
+        return _lib.lib().coati_search4_slices(self._n, qc, kk)
 
-    # ---- searching -----------------------------------------------------------------------------------------------------------------
-    def _plan(self, Q, kk, slices):
-        """(queries per call, slices): the [Q, S, kk] partial lists of a call stay within SCRATCH_BYTES"""
-        lib = _lib.lib()
-        qc = Q
-        while True:
-            S = int(slices) if slices is not None else lib.coati_search4_slices(self._n, qc, kk)
-            if S < 1:
-                raise RuntimeError(f"coati_search4_slices({self._n}, {qc}, {kk}) = {S}: {lib.coati_last_error().decode('utf-8', 'replace')}")
-            if qc * S * kk * 8 <= SCRATCH_BYTES or qc == 1:
-                return qc, S
-            qc = max(1, min(qc // 2, SCRATCH_BYTES // (S * kk * 8)))
+    def _stage1_queries(self, q16, rescore):
+        E4 = self.dim_stored
+        q16w = q16 if E4 == self.dim_padded else torch.nn.functional.pad(q16, (0, E4 - self.dim_padded)).contiguous()
+        q8, qscale = _F8.quantise_device(q16w)
+        return (q8, qscale), None if rescore else _F8.dequantise(q8, qscale)
+
+    def _stage1_call(self, qs, bias1, lo, n, kk, alpha, S, part_score, part_row, scores, rows, s):
+        _lib.call("coati_search4_topk", ptr(self._codes), ptr(self._scales), self._n, self.dim_stored, ptr(bias1), ptr(qs[0][lo:lo + n]),
+                  ptr(qs[1][lo:lo + n]), n, kk, alpha, S, ptr(part_score), ptr(part_row), ptr(scores), ptr(rows), s)
 
     def search(self, queries, k, oversample=8, rescore=None, slices=None, bias=None):
         """(scores [Q, k] f32, rows [Q, k] int64): EmbeddingIndex.search's contract -- the metric's score, descending, row ascending among
@@ -205,63 +187,5 @@ class Fp4Index:
         coati_search4_slices); the result does not depend on it.  bias: f32 [N], added to every row's score in both stages, -inf
         excluding a row.  oversample=8 is twice Fp8Index's default: four-bit rows rank the exact top k deeper (DESIGN.md section 6,
         "Four-bit search")."""
-        k, oversample = int(k), int(oversample)
-        if k < 1 or k > K_MAX:
-            raise ValueError(f"Fp4Index.search: k={k} outside 1 .. {K_MAX}")
-        if oversample < 1:
-            raise ValueError(f"Fp4Index.search: oversample={oversample} < 1")
-        rescore = self.keep_rows if rescore is None else bool(rescore)
-        if rescore and not self.keep_rows:
-            raise ValueError("Fp4Index.search: rescore=True needs the bf16 rows (keep_rows=True)")
-        kk = min(oversample * k, R_MAX) if rescore else k
-        if slices is not None and (int(slices) < 1 or int(slices) * kk > MERGE_MAX):
-            raise ValueError(f"Fp4Index.search: slices={slices} outside 1 .. {MERGE_MAX // kk} at {kk} candidates")
-        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,)):
-            raise ValueError(f"Fp4Index.search: bias must be an f32 tensor [{self._n}]")
-        _, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
-        Q = q16.shape[0]
-        if Q == 0 or self._n == 0:
-            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device),
-                    torch.full((Q, k), -1, dtype=torch.int64, device=self.device))
-        if self.device.type != "cuda":
-            raise RuntimeError("Fp4Index.search: the index is not on a GPU; there is no CPU fallback")
-        extra = None if bias is None else bias.to(self.device)
-        E4 = self.dim_stored
-        q16w = q16 if E4 == self.dim_padded else torch.nn.functional.pad(q16, (0, E4 - self.dim_padded)).contiguous()
-        q8, qscale = _F8.quantise_device(q16w)
-        scores = torch.empty(Q, kk, dtype=torch.float32, device=self.device)          # (the merge writes every entry, padding included)
-        rows = torch.empty(Q, kk, dtype=torch.int64, device=self.device)
-        qc, S = self._plan(Q, kk, slices)
-        self._scratch = scratch_pair(self._scratch, qc * S * kk, self.device)
-        bias1 = self._bias if extra is None else self._bias + extra
-        alpha = metric_alpha(self.metric)
-        with torch.cuda.device(self.device):
-            s = stream()
-            for lo in range(0, Q, qc):
-                n = min(qc, Q - lo)
-                _lib.call("coati_search4_topk", ptr(self._codes), ptr(self._scales), self._n, E4, ptr(bias1), ptr(q8[lo:lo + n]),
-                          ptr(qscale[lo:lo + n]), n, kk, alpha, S, ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(scores[lo:lo + n]),
-                          ptr(rows[lo:lo + n]), s)
-        if not rescore:
-            return finish_scores(scores, self.metric, _F8.dequantise(q8, qscale)), rows
-        bias2 = self._bias16 if extra is None else self._bias16 + extra
-        scores, rows = rescore_candidates(self._rows16, bias2, q16, rows, k, alpha)
-        return finish_scores(scores, self.metric, q16), rows
+        return self._search(queries, k, oversample, rescore, slices, bias)
 
-    # ---- persistence ---------------------------------------------------------------------------------------------------------------
-    def save(self, path):
-        """With the bf16 rows kept they are what is saved (load() quantises them again: the same bytes), else codes and scales."""
-        d = {"dim": self.dim, "dim_padded": self.dim_padded, "metric": self.metric, "bias": self._bias.cpu()}
-        if self.keep_rows:
-            d.update(rows16=self._rows16.cpu(), bias16=self._bias16.cpu())
-        else:
-            d.update(codes=self._codes.cpu(), scales=self._scales.cpu())
-        torch.save(d, path)
-
-    @classmethod
-    def load(cls, path, device="cuda:0"):
-        d = torch.load(path, map_location="cpu")
-        if "rows16" in d:
-            codes, scales = quantise_rows(d["rows16"])
-            return cls(d["dim"], d["dim_padded"], d["metric"], codes, scales, d["bias"], d["rows16"].to(device), d["bias16"], device)
-        return cls(d["dim"], d["dim_padded"], d["metric"], d["codes"], d["scales"], d["bias"], None, None, device)

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib, cluster
 from .ops import ptr, stream
-from .search import K_MAX, SCRATCH_BYTES, finish_scores, metric_alpha, prepare_queries, scratch_pair
+from .search import K_MAX, SCRATCH_BYTES, check_bias, check_rows, finish_scores, metric_alpha, prepare_queries, scratch_pair
 
 NLIST_MAX = 4096
 NPROBE_MAX = 128
@@ -149,12 +149,7 @@ class ListIndex:
 
     def _positions(self, rows):
         """the stored positions of original rows (those that have one), for remove()"""
-        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
-        if rows.numel() == 0:
-            return rows.to(self.device), rows.to(self.device)
-        if int(rows.min()) < 0 or int(rows.max()) >= self._n:
-            raise IndexError(f"{self._name}.remove: rows outside 0 .. {self._n - 1}")
-        rows = rows.to(self.device)
+        rows = check_rows(f"{self._name}.remove", rows, self._n).to(self.device)
         pos = self._inverse[rows]
         return rows, pos[pos >= 0]
 
@@ -208,10 +203,8 @@ class ListIndex:
             raise ValueError(f"{self._name}.{what}: probes must be an integer table [{Q}, 1 .. {NPROBE_MAX}]")
         return table, table.shape[1]
 
-    def _search_args(self, queries, kk, nprobe, probes, seg_rows, bias):
+    def _search_args(self, queries, kk, nprobe, probes, seg_rows):
         """The checks of a search that keeps kk entries per partial list: (q16, table [Q, nprobe] on the device, nprobe, seg_rows, segs)"""
-        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,)):
-            raise ValueError(f"{self._name}.search: bias must be an f32 tensor [{self._n}]")
         _, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
         Q = q16.shape[0]
         table, nprobe = self._given_probes(probes, nprobe, Q, "search")
@@ -315,7 +308,8 @@ class IVFIndex(ListIndex):
         k = int(k)
         if k < 1 or k > K_MAX:
             raise ValueError(f"IVFIndex.search: k={k} outside 1 .. {K_MAX}")
-        q16, table, nprobe, seg_rows, segs = self._search_args(queries, k, nprobe, probes, seg_rows, bias)
+        check_bias("IVFIndex.search", bias, self._n)
+        q16, table, nprobe, seg_rows, segs = self._search_args(queries, k, nprobe, probes, seg_rows)
         pos_bias = self._bias if bias is None else (self._bias + bias.to(self.device)[self._ids.long()]).contiguous()
 
         def scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, s):

@@ -20,10 +20,10 @@ fp8 lists, per-block scales, fp6 / fp4, more than 4096 lists, several GPUs.  Pro
 import torch
 
 from . import _lib
-from .fp8_index import R_MAX, dequantise, quantise_device, quantise_rows, rescore_candidates, stage1_bias
-from .ivf import ListIndex, make_lists
+from .fp8_index import dequantise, quantise_device, quantise_rows, stage1_bias
+from .ivf import make_lists
 from .ops import ptr
-from .search import K_MAX, finish_scores, metric_alpha
+from .two_stage import ListTwoStage
 
 BUILD_CHUNK = 1 << 20            # rows gathered and quantised at a time by build()
 
@@ -32,7 +32,7 @@ def _quantise(x16):
     return quantise_device(x16) if x16.device.type == "cuda" else quantise_rows(x16)
 
 
-class Ivf8Index(ListIndex):
+class Ivf8Index(ListTwoStage):
     """An inverted-file index over the live rows of an EmbeddingIndex at the time of build(), the rows stored as e4m3 bytes and scales
     in list order.  len() is the source's; rows returned by search are the source's rows.  Attributes: centres [L, dim] f32, nlist, metric,
     dim, dim_padded, device, keep_rows."""
@@ -45,16 +45,7 @@ class Ivf8Index(ListIndex):
         if self._vec8.dtype != torch.uint8 or self._vec8.shape != (self._m, self.dim_padded) or self._scale.shape != (self._m,) \
                 or self._bias.shape != (self._m,):
             raise ValueError("Ivf8Index: bytes, scales, ids and bias do not match the list sizes")
-        self.keep_rows = rows16 is not None
-        self._rows16 = self._bias16 = None
-        if self.keep_rows:
-            if bias16 is None:
-                raise ValueError("Ivf8Index: the bf16 rows need their bias")
-            self._rows16 = rows16 if rows16.device == self.device else rows16.to(self.device)      # (a view of the source's rows stays one)
-            self._bias16 = bias16.to(self.device, torch.float32).contiguous()
-            if self._rows16.dtype != torch.bfloat16 or self._rows16.shape != (self._n, self.dim_padded) or self._bias16.shape != (self._n,) \
-                    or not self._rows16.is_contiguous():
-                raise ValueError("Ivf8Index: the bf16 rows do not match the index")
+        self._adopt_rows(rows16, bias16)
 
     # ---- building ----------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -113,14 +104,18 @@ class Ivf8Index(ListIndex):
         """f32 [M, dim_padded]: the rows the bytes and scales stand for, in list order"""
         return dequantise(self._vec8, self._scale)
 
-    def remove(self, rows):
-        """the rows (original indices) are never returned again by either stage; len() and the other rows' indices do not change"""
-        rows, pos = self._positions(rows)
-        self._bias[pos] = float("-inf")
-        if self.keep_rows:
-            self._bias16[rows] = float("-inf")
+    # ---- searching (ListTwoStage) ----------------------------------------------------------------------------------------------------
+    def _stage1_queries(self, q16, rescore):
+        q8, qscale = quantise_device(q16)
+        return (q8, qscale), None if rescore else dequantise(q8, qscale)
 
-    # ---- searching -----------------------------------------------------------------------------------------------------------------
+    def _scan(self, qs, pos_bias, kk, alpha, blocks):
+        def scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, s):
+            _lib.call("coati_ivf8_scan", ptr(self._vec8), ptr(self._scale), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m,
+                      self.dim_padded, self.nlist, ptr(qs[0][lo:lo + n]), ptr(qs[1][lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off),
+                      P, kk, alpha, seg_rows, segs, ptr(part_score), ptr(part_row), int(blocks), s)
+        return scan
+
     def search(self, queries, k, nprobe=8, oversample=4, rescore=None, probes=None, seg_rows=None, bias=None, return_probes=False, blocks=0):
         """(scores [Q, k] f32, rows [Q, k] int64): EmbeddingIndex.search's contract over every query's probed lists -- the metric's score,
         descending, original row ascending among equal scores, (-inf, -1) where fewer rows qualify.  Stage 1 keeps
@@ -128,41 +123,7 @@ class Ivf8Index(ListIndex):
         keep_rows; False: stage 1's k best with stage 1's scores (of the dequantised operands); True without the bf16 rows raises.
         nprobe, probes, seg_rows, blocks, return_probes: IVFIndex.search's (seg_rows defaults to coati_ivf_plan at R).  bias: f32 [N]
         over ORIGINAL rows, added to every row's score in both stages, -inf excluding a row."""
-        k, oversample = int(k), int(oversample)
-        if k < 1 or k > K_MAX:
-            raise ValueError(f"Ivf8Index.search: k={k} outside 1 .. {K_MAX}")
-        if oversample < 1:
-            raise ValueError(f"Ivf8Index.search: oversample={oversample} < 1")
-        rescore = self.keep_rows if rescore is None else bool(rescore)
-        if rescore and not self.keep_rows:
-            raise ValueError("Ivf8Index.search: rescore=True needs the bf16 rows (keep_rows=True)")
-        kk = min(oversample * k, R_MAX) if rescore else k
-        q16, table, nprobe, seg_rows, segs = self._search_args(queries, kk, nprobe, probes, seg_rows, bias)
-        Q = q16.shape[0]
-        extra = None if bias is None else bias.to(self.device)
-        pos_bias = self._bias if extra is None else (self._bias + extra[self._ids.long()]).contiguous()
-        alpha = metric_alpha(self.metric)
-        q8 = qscale = None
-        if Q and self._m:
-            if self.device.type != "cuda":
-                raise RuntimeError("Ivf8Index.search: the index is not on a GPU; there is no CPU fallback")
-            q8, qscale = quantise_device(q16)
-
-        def scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, s):
-            _lib.call("coati_ivf8_scan", ptr(self._vec8), ptr(self._scale), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m,
-                      self.dim_padded, self.nlist, ptr(q8[lo:lo + n]), ptr(qscale[lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off),
-                      P, kk, alpha, seg_rows, segs, ptr(part_score), ptr(part_row), int(blocks), s)
-
-        scores, rows = self._scan_merge(scan, Q, table, nprobe, kk, seg_rows, segs)
-        if q8 is None:
-            scores, rows = scores[:, :k], rows[:, :k]
-        elif not rescore:
-            scores = finish_scores(scores, self.metric, dequantise(q8, qscale))
-        else:
-            bias2 = self._bias16 if extra is None else self._bias16 + extra
-            scores, rows = rescore_candidates(self._rows16, bias2, q16, rows, k, alpha)
-            scores = finish_scores(scores, self.metric, q16)
-        return (scores, rows, table.long()) if return_probes else (scores, rows)
+        return self._search(queries, k, nprobe, oversample, rescore, probes, seg_rows, bias, return_probes, blocks)
 
     # ---- persistence ---------------------------------------------------------------------------------------------------------------
     def save(self, path):

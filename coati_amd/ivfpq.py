@@ -35,10 +35,9 @@ over codes, several GPUs, re-scoring from rows in host memory.  The reference ha
 import torch
 
 from . import _lib, cluster, pq
-from .fp8_index import R_MAX, rescore_candidates
-from .ivf import ListIndex, make_lists
+from .ivf import make_lists
 from .ops import ptr
-from .search import finish_scores, metric_alpha
+from .two_stage import ListTwoStage
 
 BUILD_CHUNK = 1 << 20            # rows gathered, subtracted and encoded at a time by build()
 DIM_MAX = pq.DIM_MAX             # the code books of a wider row do not fit a CU's LDS
@@ -113,7 +112,7 @@ def encode_lists(metric, rows_at, bias_at, M, sizes, c16, codebooks):
     return codes, bias
 
 
-class IvfPqIndex(ListIndex):
+class IvfPqIndex(ListTwoStage):
     """An inverted-file index over the live rows of an EmbeddingIndex at the time of build(), the rows stored as PQ codes of their
     residuals in list order.  len() is the source's; rows returned by search are the source's rows.  Attributes: centres [L, dim] f32,
     nlist, metric, dim, dim_padded, device, keep_rows."""
@@ -128,16 +127,7 @@ class IvfPqIndex(ListIndex):
         self._bias = bias.to(self.device, torch.float32).contiguous()
         if self._codes.dtype != torch.uint8 or self._codes.shape != (self._m, self.dim_padded // pq.SUB) or self._bias.shape != (self._m,):
             raise ValueError("IvfPqIndex: codes, ids and bias do not match the list sizes")
-        self.keep_rows = rows16 is not None
-        self._rows16 = self._bias16 = None
-        if self.keep_rows:
-            if bias16 is None:
-                raise ValueError("IvfPqIndex: the bf16 rows need their bias")
-            self._rows16 = rows16 if rows16.device == self.device else rows16.to(self.device)      # (a view of the source's rows stays one)
-            self._bias16 = bias16.to(self.device, torch.float32).contiguous()
-            if self._rows16.dtype != torch.bfloat16 or self._rows16.shape != (self._n, self.dim_padded) or self._bias16.shape != (self._n,) \
-                    or not self._rows16.is_contiguous():
-                raise ValueError("IvfPqIndex: the bf16 rows do not match the index")
+        self._adopt_rows(rows16, bias16)
 
     # ---- building ----------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -212,14 +202,17 @@ class IvfPqIndex(ListIndex):
         """what stage 1 holds per row: the code bytes, the int32 id and the f32 bias"""
         return self.dim_padded // pq.SUB + 8
 
-    def remove(self, rows):
-        """the rows (original indices) are never returned again by either stage; len() and the other rows' indices do not change"""
-        rows, pos = self._positions(rows)
-        self._bias[pos] = float("-inf")
-        if self.keep_rows:
-            self._bias16[rows] = float("-inf")
+    # ---- searching (ListTwoStage) ----------------------------------------------------------------------------------------------------
+    def _stage1_queries(self, q16, rescore):
+        return q16, q16
 
-    # ---- searching -----------------------------------------------------------------------------------------------------------------
+    def _scan(self, q16, pos_bias, kk, alpha, blocks):
+        def scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, s):
+            _lib.call("coati_ivfpq_scan", ptr(self._codes), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m, self.dim_padded,
+                      self.nlist, ptr(self._c16), ptr(self._cb), ptr(q16[lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off), P, kk,
+                      alpha, seg_rows, segs, ptr(part_score), ptr(part_row), int(blocks), s)
+        return scan
+
     def search(self, queries, k, nprobe=8, oversample=4, rescore=None, probes=None, seg_rows=None, bias=None, return_probes=False, blocks=0):
         """(scores [Q, k] f32, rows [Q, k] int64): EmbeddingIndex.search's contract over every query's probed lists -- the metric's score,
         descending, original row ascending among equal scores, (-inf, -1) where fewer rows qualify.  Stage 1 keeps
@@ -228,37 +221,8 @@ class IvfPqIndex(ListIndex):
         raises.  nprobe, probes, seg_rows, blocks, return_probes: IVFIndex.search's (seg_rows defaults to coati_ivf_plan at R).  bias:
         f32 [N] over ORIGINAL rows, added to every row's score in both stages, -inf excluding a row.  oversample=4 is Ivf8Index's
         default, kept: see DESIGN.md section 6 for what was and was not measured."""
-        k, oversample = int(k), int(oversample)
-        km = k_max(self.dim_padded)
-        if k < 1 or k > km:
-            raise ValueError(f"IvfPqIndex.search: k={k} outside 1 .. {km}, the limit of coati_ivfpq_k_max({self.dim_padded})")
-        if oversample < 1:
-            raise ValueError(f"IvfPqIndex.search: oversample={oversample} < 1")
-        rescore = self.keep_rows if rescore is None else bool(rescore)
-        if rescore and not self.keep_rows:
-            raise ValueError("IvfPqIndex.search: rescore=True needs the bf16 rows (keep_rows=True)")
-        kk = min(oversample * k, km, R_MAX) if rescore else k
-        q16, table, nprobe, seg_rows, segs = self._search_args(queries, kk, nprobe, probes, seg_rows, bias)
-        Q = q16.shape[0]
-        extra = None if bias is None else bias.to(self.device)
-        pos_bias = self._bias if extra is None else (self._bias + extra[self._ids.long()]).contiguous()
-        alpha = metric_alpha(self.metric)
-
-        def scan(lo, n, pair_q, pair_off, item_off, P, seg_rows, segs, part_score, part_row, s):
-            _lib.call("coati_ivfpq_scan", ptr(self._codes), ptr(self._ids), ptr(pos_bias), ptr(self._list_off), self._m, self.dim_padded,
-                      self.nlist, ptr(self._c16), ptr(self._cb), ptr(q16[lo:lo + n]), n, ptr(pair_q), ptr(pair_off), ptr(item_off), P, kk,
-                      alpha, seg_rows, segs, ptr(part_score), ptr(part_row), int(blocks), s)
-
-        scores, rows = self._scan_merge(scan, Q, table, nprobe, kk, seg_rows, segs)
-        if Q == 0 or self._m == 0:
-            scores, rows = scores[:, :k], rows[:, :k]
-        elif not rescore:
-            scores = finish_scores(scores, self.metric, q16)
-        else:
-            bias2 = self._bias16 if extra is None else self._bias16 + extra
-            scores, rows = rescore_candidates(self._rows16, bias2, q16, rows, k, alpha)
-            scores = finish_scores(scores, self.metric, q16)
-        return (scores, rows, table.long()) if return_probes else (scores, rows)
+        return self._search(queries, k, nprobe, oversample, rescore, probes, seg_rows, bias, return_probes, blocks, k_max(self.dim_padded),
+                            f", the limit of coati_ivfpq_k_max({self.dim_padded})")
 
     # ---- persistence ---------------------------------------------------------------------------------------------------------------
     def save(self, path):

@@ -27,10 +27,9 @@ re-scoring from rows in host memory, add() on a snapshot that holds a view of an
 import torch
 
 from . import _lib
-from .fp8_index import R_MAX, rescore_candidates
 from .ops import ptr, stream
-from .search import MERGE_MAX, MIN_CAPACITY, SCRATCH_BYTES, finish_scores, metric_alpha, padded_dim, prepare_queries, prepare_rows, scratch_pair, \
-    _check_metric
+from .search import MIN_CAPACITY, padded_dim, prepare_rows, _check_metric
+from .two_stage import FlatTwoStage
 
 SUB = 8                          # dimensions per sub-space
 CODES = 256                      # entries per code book
@@ -163,9 +162,11 @@ def stage1_bias(metric, codes, codebooks, bias16):
     return out
 
 
-class PQIndex:
+class PQIndex(FlatTwoStage):
     """Rows as PQ codes under fixed code books.  Starts empty; add() encodes and appends.  Attributes: dim, dim_padded, metric, device,
     keep_rows (bf16 rows for stage 2 are held: only a snapshot made by build(..., keep_rows=True), or loaded from the file of one, has them)."""
+    _slices_entry = "coati_pq_slices"
+    _rows_hint = "a snapshot built with keep_rows=True"
 
     def __init__(self, dim, metric="cosine", codebooks=None, device="cuda:0"):
         _check_metric(metric)
@@ -178,9 +179,7 @@ class PQIndex:
         self._m = self.dim_padded // SUB
         self._n = 0
         self._codes = self._bias = None                # [capacity, M] uint8, [capacity] f32
-        self.keep_rows = False
-        self._rows16 = self._bias16 = None             # a snapshot's view of the source's bf16 rows, and its own copy of their bias
-        self._scratch = None                           # the partial lists, kept between searches
+        self._adopt_rows(None, None)                   # (a snapshot adopts a view of the source's bf16 rows, and its own copy of their bias)
 
     # ---- building ----------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -204,7 +203,7 @@ class PQIndex:
         gone = bias16 == float("-inf")
         pq._append(x16, torch.where(gone, bias16, torch.zeros_like(bias16)))
         if keep_rows:
-            pq.keep_rows, pq._rows16, pq._bias16 = True, x16, bias16
+            pq._adopt_rows(x16, bias16)
         return pq
 
     def _reserve(self, n):
@@ -247,9 +246,6 @@ class PQIndex:
         _, x16, _ = prepare_rows(vectors, self.metric, self.dim, self.device)
         return self._append(x16.contiguous(), torch.zeros(x16.shape[0], dtype=torch.float32, device=self.device))
 
-    def __len__(self):
-        return self._n
-
     @property
     def codes(self):
         """the stored code bytes [N, dim_padded / 8] uint8 (a view)"""
@@ -273,30 +269,16 @@ class PQIndex:
         """what stage 1 holds per row: the code bytes and the f32 bias"""
         return self._m + 4
 
-    def remove(self, rows):
-        """the rows are never returned again; len() and the other rows' indices do not change"""
-        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
-        if rows.numel() == 0:
-            return
-        if int(rows.min()) < 0 or int(rows.max()) >= self._n:
-            raise IndexError(f"PQIndex.remove: rows outside 0 .. {self._n - 1}")
-        self._bias[rows.to(self.device)] = float("-inf")
-        if self.keep_rows:
-            self._bias16[rows.to(self.device)] = float("-inf")
+    # ---- searching (FlatTwoStage) ----------------------------------------------------------------------------------------------------
+    def _default_slices(self, qc, kk):
+        return _lib.lib().coati_pq_slices(self._n, self.dim_padded, qc, kk)
 
-    # ---- searching -----------------------------------------------------------------------------------------------------------------
-    def _plan(self, Q, kk, slices):
-        """(queries per call, slices): the [Q, S, kk] partial lists of a call stay within SCRATCH_BYTES"""
-        lib = _lib.lib()
-        qc = Q
-        while True:
-            S = int(slices) if slices is not None else lib.coati_pq_slices(self._n, self.dim_padded, qc, kk)
-            if S < 1:
-                raise RuntimeError(f"coati_pq_slices({self._n}, {self.dim_padded}, {qc}, {kk}) = {S}: "
-                                   f"{lib.coati_last_error().decode('utf-8', 'replace')}")
-            if qc * S * kk * 8 <= SCRATCH_BYTES or qc == 1:
-                return qc, S
-            qc = max(1, min(qc // 2, SCRATCH_BYTES // (S * kk * 8)))
+    def _stage1_queries(self, q16, rescore):
+        return q16, q16
+
+    def _stage1_call(self, q16, bias1, lo, n, kk, alpha, S, part_score, part_row, scores, rows, s):
+        _lib.call("coati_pq_topk", ptr(self._codes), self._n, self.dim_padded, ptr(self._cb), ptr(bias1), ptr(q16[lo:lo + n]), n, kk, alpha, S,
+                  ptr(part_score), ptr(part_row), ptr(scores), ptr(rows), s)
 
     def search(self, queries, k, oversample=4, rescore=None, slices=None, bias=None):
         """(scores [Q, k] f32, rows [Q, k] int64): EmbeddingIndex.search's contract -- the metric's score, descending, row ascending among
@@ -305,45 +287,8 @@ class PQIndex:
         stage 1's scores (of the reconstructed rows); True without the bf16 rows raises.  slices: the library slices of stage 1's grid
         (default: coati_pq_slices); the result does not depend on it.  bias: f32 [N], added to every row's score in both stages, -inf
         excluding a row.  oversample=4 is Fp8Index's default, kept: see DESIGN.md section 6 for what was and was not measured."""
-        k, oversample = int(k), int(oversample)
-        km = k_max(self.dim_padded)
-        if k < 1 or k > km:
-            raise ValueError(f"PQIndex.search: k={k} outside 1 .. {km}, the limit of coati_pq_k_max({self.dim_padded})")
-        if oversample < 1:
-            raise ValueError(f"PQIndex.search: oversample={oversample} < 1")
-        rescore = self.keep_rows if rescore is None else bool(rescore)
-        if rescore and not self.keep_rows:
-            raise ValueError("PQIndex.search: rescore=True needs the bf16 rows (a snapshot built with keep_rows=True)")
-        kk = min(oversample * k, km, R_MAX) if rescore else k
-        if slices is not None and (int(slices) < 1 or int(slices) * kk > MERGE_MAX):
-            raise ValueError(f"PQIndex.search: slices={slices} outside 1 .. {MERGE_MAX // kk} at {kk} candidates")
-        if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,)):
-            raise ValueError(f"PQIndex.search: bias must be an f32 tensor [{self._n}]")
-        _, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
-        Q = q16.shape[0]
-        if Q == 0 or self._n == 0:
-            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device),
-                    torch.full((Q, k), -1, dtype=torch.int64, device=self.device))
-        if self.device.type != "cuda":
-            raise RuntimeError("PQIndex.search: the index is not on a GPU; there is no CPU fallback")
-        extra = None if bias is None else bias.to(self.device)
-        scores = torch.empty(Q, kk, dtype=torch.float32, device=self.device)          # (the merge writes every entry, padding included)
-        rows = torch.empty(Q, kk, dtype=torch.int64, device=self.device)
-        qc, S = self._plan(Q, kk, slices)
-        self._scratch = scratch_pair(self._scratch, qc * S * kk, self.device)
-        bias1 = (self.bias if extra is None else self.bias + extra).contiguous()
-        alpha = metric_alpha(self.metric)
-        with torch.cuda.device(self.device):
-            s = stream()
-            for lo in range(0, Q, qc):
-                n = min(qc, Q - lo)
-                _lib.call("coati_pq_topk", ptr(self._codes), self._n, self.dim_padded, ptr(self._cb), ptr(bias1), ptr(q16[lo:lo + n]), n, kk,
-                          alpha, S, ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(scores[lo:lo + n]), ptr(rows[lo:lo + n]), s)
-        if not rescore:
-            return finish_scores(scores, self.metric, q16), rows
-        bias2 = self._bias16 if extra is None else self._bias16 + extra
-        scores, rows = rescore_candidates(self._rows16, bias2, q16, rows, k, alpha)
-        return finish_scores(scores, self.metric, q16), rows
+        return self._search(queries, k, oversample, rescore, slices, bias, k_max(self.dim_padded),
+                            f", the limit of coati_pq_k_max({self.dim_padded})")
 
     # ---- persistence ---------------------------------------------------------------------------------------------------------------
     def save(self, path):
@@ -365,7 +310,5 @@ class PQIndex:
             pq._codes[:n], pq._bias[:n] = d["codes"].to(pq.device), d["bias"].to(pq.device, torch.float32)
         pq._n = n
         if "rows16" in d:
-            pq.keep_rows, pq._rows16, pq._bias16 = True, d["rows16"].to(pq.device).contiguous(), d["bias16"].to(pq.device, torch.float32)
-            if pq._rows16.dtype != torch.bfloat16 or tuple(pq._rows16.shape) != (n, pq.dim_padded) or tuple(pq._bias16.shape) != (n,):
-                raise ValueError("PQIndex.load: the bf16 rows do not match the codes")
+            pq._adopt_rows(d["rows16"].to(pq.device), d["bias16"])
         return pq

@@ -91,6 +91,54 @@ def scratch_pair(pair, need, device):
     return pair
 
 
+def check_rows(what, rows, n):
+    """`rows` as a flat int64 tensor; an IndexError naming `what` unless every one is a row of 0 .. n - 1"""
+    rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
+        raise IndexError(f"{what}: rows outside 0 .. {n - 1}")
+    return rows
+
+
+def check_bias(what, bias, n):
+    """a search's extra bias: None, or an f32 tensor [n]"""
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (n,)):
+        raise ValueError(f"{what}: bias must be an f32 tensor [{n}]")
+
+
+def plan_chunks(entry, default_slices, Q, kk, slices):
+    """(queries per call, slices): the [Q, S, kk] partial lists of a call stay within SCRATCH_BYTES.  S is `slices`, or else
+    default_slices(qc, kk), the C entry `entry`'s answer for a call of qc queries."""
+    qc = Q
+    while True:
+        S = int(slices) if slices is not None else default_slices(qc, kk)
+        if S < 1:
+            raise RuntimeError(f"{entry} at Q={qc}, k={kk} = {S}: {_lib.lib().coati_last_error().decode('utf-8', 'replace')}")
+        if qc * S * kk * 8 <= SCRATCH_BYTES or qc == 1:
+            return qc, S
+        qc = max(1, min(qc // 2, SCRATCH_BYTES // (S * kk * 8)))
+
+
+def sliced_topk(index, what, Q, kk, slices, call):
+    """The flat indices' stage over all N rows: (scores [Q, kk] f32, rows [Q, kk] int64) of Q prepared queries, written chunk by chunk
+    (index._plan) by call(lo, n, S, part_score, part_row, scores, rows, stream) -- one C entry on queries lo .. lo + n - 1 and their
+    slices of the outputs.  No queries or no rows: the padding (-inf, -1).  index keeps the partial lists between calls (_scratch)."""
+    if Q == 0 or len(index) == 0:
+        return (torch.full((Q, kk), float("-inf"), dtype=torch.float32, device=index.device),
+                torch.full((Q, kk), -1, dtype=torch.int64, device=index.device))
+    if index.device.type != "cuda":
+        raise RuntimeError(f"{what}: the index is not on a GPU; there is no CPU fallback")
+    scores = torch.empty(Q, kk, dtype=torch.float32, device=index.device)          # (the merge writes every entry, padding included)
+    rows = torch.empty(Q, kk, dtype=torch.int64, device=index.device)
+    qc, S = index._plan(Q, kk, slices)
+    index._scratch = scratch_pair(index._scratch, qc * S * kk, index.device)
+    with torch.cuda.device(index.device):
+        s = stream()
+        for lo in range(0, Q, qc):
+            n = min(qc, Q - lo)
+            call(lo, n, S, index._scratch[0], index._scratch[1], scores[lo:lo + n], rows[lo:lo + n], s)
+    return scores, rows
+
+
 class EmbeddingIndex:
     def __init__(self, dim, metric="cosine", device="cuda:0", keep_f32=False):
         _check_metric(metric)
@@ -150,24 +198,13 @@ class EmbeddingIndex:
 
     def remove(self, rows):
         """the rows are never returned again; len() and the other rows' indices do not change"""
-        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
-        if rows.numel() == 0:
-            return
-        if int(rows.min()) < 0 or int(rows.max()) >= self._n:
-            raise IndexError(f"EmbeddingIndex.remove: rows outside 0 .. {self._n - 1}")
-        self._bias[rows.to(self.device)] = float("-inf")
+        rows = check_rows("EmbeddingIndex.remove", rows, self._n)
+        if rows.numel():
+            self._bias[rows.to(self.device)] = float("-inf")
 
     def _plan(self, Q, k, slices):
-        """(queries per call, slices): the [Q, S, k] partial lists of a call stay within SCRATCH_BYTES"""
-        lib = _lib.lib()
-        qc = Q
-        while True:
-            S = int(slices) if slices is not None else lib.coati_search_slices(self._n, qc, k)
-            if S < 1:
-                raise RuntimeError(f"coati_search_slices({self._n}, {qc}, {k}) = {S}: {lib.coati_last_error().decode('utf-8', 'replace')}")
-            if qc * S * k * 8 <= SCRATCH_BYTES or qc == 1:
-                return qc, S
-            qc = max(1, min(qc // 2, SCRATCH_BYTES // (S * k * 8)))
+        """(queries per call, slices) of a search: plan_chunks with coati_search_slices' default"""
+        return plan_chunks("coati_search_slices", lambda qc, k: _lib.lib().coati_search_slices(self._n, qc, k), Q, k, slices)
 
     def search(self, queries, k, rescore=1, slices=None, bias=None):
         """(scores [Q, k] f32, rows [Q, k] int64) of the k nearest rows per query, score descending, row ascending among equal scores;
@@ -189,8 +226,7 @@ class EmbeddingIndex:
         if bias is not None:
             if rescore > 1:
                 raise ValueError("EmbeddingIndex.search: bias is not compatible with rescore > 1")
-            if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (self._n,):
-                raise ValueError(f"EmbeddingIndex.search: bias must be an f32 tensor [{self._n}]")
+            check_bias("EmbeddingIndex.search", bias, self._n)
         q32, q16 = prepare_queries(queries, self.metric, self.dim, self.device)
         scores, rows = self._topk(q16, kk, slices, self._bias if bias is None else self.bias + bias.to(self.device))
         if rescore > 1:
@@ -199,22 +235,11 @@ class EmbeddingIndex:
 
     def _topk(self, q16, kk, slices, bias):
         """the kernel on prepared queries: (alpha * dot + bias[row] [Q, kk], rows [Q, kk]); bias f32, at least N entries on the device"""
-        Q = q16.shape[0]
-        scores = torch.full((Q, kk), float("-inf"), dtype=torch.float32, device=self.device)
-        rows = torch.full((Q, kk), -1, dtype=torch.int64, device=self.device)
-        if Q > 0 and self._n > 0:
-            if self.device.type != "cuda":
-                raise RuntimeError("EmbeddingIndex.search: the index is not on a GPU; there is no CPU fallback")
-            qc, S = self._plan(Q, kk, slices)
-            self._scratch = scratch_pair(self._scratch, qc * S * kk, self.device)
-            with torch.cuda.device(self.device):
-                s = stream()
-                for lo in range(0, Q, qc):
-                    n = min(qc, Q - lo)
-                    _lib.call("coati_search_topk", ptr(self._vec), self._n, self.dim_padded, ptr(bias), ptr(q16[lo:lo + n]), n, kk,
-                              metric_alpha(self.metric), S, ptr(self._scratch[0]), ptr(self._scratch[1]), ptr(scores[lo:lo + n]),
-                              ptr(rows[lo:lo + n]), s)
-        return scores, rows
+        def call(lo, n, S, part_score, part_row, scores, rows, s):
+            _lib.call("coati_search_topk", ptr(self._vec), self._n, self.dim_padded, ptr(bias), ptr(q16[lo:lo + n]), n, kk,
+                      metric_alpha(self.metric), S, ptr(part_score), ptr(part_row), ptr(scores), ptr(rows), s)
+
+        return sliced_topk(self, "EmbeddingIndex.search", q16.shape[0], kk, slices, call)
 
     def _check_head(self, head, what):
         if head.input_dim != self.dim:
@@ -283,9 +308,7 @@ class EmbeddingIndex:
             raise RuntimeError(f"EmbeddingIndex.{what}: the index is not on a GPU; there is no CPU fallback")
         if rows is None:
             return self.vectors, self.bias, None
-        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1).to(self.device)
-        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= self._n):
-            raise IndexError(f"EmbeddingIndex.{what}: rows outside 0 .. {self._n - 1}")
+        rows = check_rows(f"EmbeddingIndex.{what}", rows, self._n).to(self.device)
         return self.vectors[rows].contiguous(), self.bias[rows].contiguous(), rows
 
     def assign(self, centres):

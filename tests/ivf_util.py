@@ -4,6 +4,7 @@ probed lists, score descending, ORIGINAL row ascending among equal scores, rows 
 import torch
 
 from tests import search_util
+from tests.search_util import recall  # noqa: F401  (the tests reach it through this module)
 
 NEG_INF = float("-inf")
 
@@ -34,11 +35,3 @@ def scan(lib16, ids, bias, list_off, q16, probes, k, alpha=1.0):
     order = torch.argsort(ids, stable=True)                                                             # positions in original-row order
     val, idx = search_util.topk(s[:, order], k)
     return val, torch.where(idx >= 0, ids[order][idx.clamp_min(0)], idx)
-
-
-def recall(rows, exact_rows):
-    """the fraction of the exact result's rows (>= 0) that `rows` holds, over all queries"""
-    rows, exact_rows = rows.cpu(), exact_rows.cpu()
-    want = exact_rows >= 0
-    hit = (exact_rows[:, :, None] == rows[:, None, :]).any(dim=2) & want
-    return float(hit.sum()) / max(int(want.sum()), 1)

@@ -4,7 +4,7 @@ lossless."""
 import torch
 
 from tests import search_util
-from tests.search8_util import clustered  # noqa: F401  (the clustered generator the fp8 tests and tools/search8_bench.py use)
+from tests.search_util import clustered, recall  # noqa: F401  (the tests reach both through this module)
 
 NEG_INF = float("-inf")
 
@@ -44,35 +44,19 @@ def composed_rows(codebooks, N, seed, distinct=256):
 
 
 def stage1_scores(pq, queries, extra=None):
-    """[Q, N] float64: stage 1's score under the metric, from the RECONSTRUCTED rows and the bf16 queries -- alpha q . x_hat + bias
-    (+ extra), for l2 minus |q|^2 and at most 0; a removed row is -inf.  On the CPU."""
+    """([Q, N] float64, q16): stage 1's score under the metric, from the RECONSTRUCTED rows and the bf16 queries
+    (search_util.stage1_scores)"""
     from coati_amd import search as S
     _, q16 = S.prepare_queries(queries, pq.metric, pq.dim, "cpu")
-    bias = pq.bias.cpu() if extra is None else pq.bias.cpu() + extra.cpu()
-    s = search_util.score_matrix(pq.dequantised().cpu(), bias, q16, S.metric_alpha(pq.metric))
-    if pq.metric == "l2":
-        s = (s - (q16.double() ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
-    return s, q16
+    return search_util.stage1_scores(pq, q16, extra), q16
 
 
 def stage1_search(pq, queries, k, extra=None):
     """the oracle of PQIndex.search(queries, k, rescore=False): (scores [Q, k] float64, rows [Q, k] int64, the score matrix)"""
-    s, _ = stage1_scores(pq, queries, extra)
-    val, idx = search_util.topk(s, k)
-    return val, idx, s
+    from coati_amd import search as S
+    return search_util.stage1_search(pq, S.prepare_queries(queries, pq.metric, pq.dim, "cpu")[1], k, extra)
 
 
 def two_stage_search(pq, index, queries, k, R):
     """the oracle of the two stages: the best k by index's exact float64 score among stage 1's best R rows"""
-    _, cand, _ = stage1_search(pq, queries, R)
-    exact = search_util.index_scores(index, queries)
-    picked = torch.full_like(exact, NEG_INF)
-    ok = cand >= 0
-    picked.scatter_(1, cand.clamp_min(0), torch.where(ok, exact.gather(1, cand.clamp_min(0)), torch.full_like(exact[:, :1], NEG_INF).expand_as(cand)))
-    return search_util.topk(picked, k)
-
-
-def recall(rows, want):
-    """the fraction of want's rows [Q, k] (>= 0) found in the same query's `rows`"""
-    hit = (rows[:, :, None] == want[:, None, :]).any(dim=1) & (want >= 0)
-    return float(hit.sum()) / float((want >= 0).sum())
+    return search_util.two_stage_search(stage1_search(pq, queries, R)[1], index, queries, k)

@@ -22,22 +22,15 @@ def query_hat(fp4, queries):
 
 
 def stage1_scores(fp4, queries, extra=None):
-    """[Q, N] float64: stage 1's score under the metric, from the DEQUANTISED rows and the dequantised queries -- alpha q_hat . x_hat +
-    bias (+ extra), for l2 minus |q_hat|^2 and at most 0; a removed row is -inf.  Computed on the CPU."""
-    from coati_amd import search as S
+    """([Q, N] float64, q_hat): stage 1's score under the metric, from the DEQUANTISED rows and the dequantised queries
+    (search_util.stage1_scores)"""
     q_hat = query_hat(fp4, queries)
-    bias = fp4.bias.cpu() if extra is None else fp4.bias.cpu() + extra.cpu()
-    s = search_util.score_matrix(fp4.dequantised().cpu(), bias, q_hat, S.metric_alpha(fp4.metric))
-    if fp4.metric == "l2":
-        s = (s - (q_hat.double() ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
-    return s, q_hat
+    return search_util.stage1_scores(fp4, q_hat, extra), q_hat
 
 
 def stage1_search(fp4, queries, k, extra=None):
     """the oracle of Fp4Index.search(queries, k, rescore=False): (scores [Q, k] float64, rows [Q, k] int64, the score matrix)"""
-    s, _ = stage1_scores(fp4, queries, extra)
-    val, idx = search_util.topk(s, k)
-    return val, idx, s
+    return search_util.stage1_search(fp4, query_hat(fp4, queries), k, extra)
 
 
 def stage1_ranks(full, rows):

@@ -3,28 +3,28 @@ top of tests/search_util.py (whose oracle, data and tie rule they reuse), and th
 import torch
 
 from tests import search_util
+from tests.search_util import clustered  # noqa: F401  (the tests reach the clustered generator through this module)
 
 NEG_INF = float("-inf")
 
 
-def stage1_scores(fp8, queries, extra=None):
-    """[Q, N] float64: stage 1's score under the metric, from the DEQUANTISED rows and the dequantised queries -- alpha q_hat . x_hat +
-    bias (+ extra), for l2 minus |q_hat|^2 and at most 0; a removed row is -inf.  Computed on the CPU with torch's float8_e4m3fn."""
+def query_hat(fp8, queries):
+    """f32 [Q, E]: the dequantised e4m3 queries of Fp8Index.search, computed on the CPU with torch's float8_e4m3fn"""
     from coati_amd import fp8_index as F, search as S
     _, q16 = S.prepare_queries(queries, fp8.metric, fp8.dim, "cpu")
-    q_hat = F.dequantise(*F.quantise_rows(q16))
-    bias = fp8.bias.cpu() if extra is None else fp8.bias.cpu() + extra.cpu()
-    s = search_util.score_matrix(fp8.dequantised().cpu(), bias, q_hat, S.metric_alpha(fp8.metric))
-    if fp8.metric == "l2":
-        s = (s - (q_hat.double() ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
-    return s, q_hat
+    return F.dequantise(*F.quantise_rows(q16))
+
+
+def stage1_scores(fp8, queries, extra=None):
+    """([Q, N] float64, q_hat): stage 1's score under the metric, from the DEQUANTISED rows and the dequantised queries
+    (search_util.stage1_scores)"""
+    q_hat = query_hat(fp8, queries)
+    return search_util.stage1_scores(fp8, q_hat, extra), q_hat
 
 
 def stage1_search(fp8, queries, k, extra=None):
     """the oracle of Fp8Index.search(queries, k, rescore=False): (scores [Q, k] float64, rows [Q, k] int64, the score matrix)"""
-    s, _ = stage1_scores(fp8, queries, extra)
-    val, idx = search_util.topk(s, k)
-    return val, idx, s
+    return search_util.stage1_search(fp8, query_hat(fp8, queries), k, extra)
 
 
 def quantiser_rows(n, E, seed):
@@ -75,10 +75,3 @@ def hex_library(kind, N=4096):
     q = torch.zeros(1, 32)
     q[0, 0], q[0, 1], q[0, 2] = 256, 16, 1
     return x, q
-
-
-def clustered(N, E, seed, centres=200, noise=0.5):
-    """rows [N, E] and queries from the same law: `centres` Gaussian centres plus noise-sigma Gaussian noise"""
-    g = torch.Generator().manual_seed(seed)
-    c = torch.randn(centres, E, generator=g)
-    return lambda n: c[torch.randint(0, centres, (n,), generator=g)] + noise * torch.randn(n, E, generator=g)

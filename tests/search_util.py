@@ -49,6 +49,49 @@ def index_search(index, queries, k):
     return val, idx, s
 
 
+def stage1_scores(index, q_hat, extra=None):
+    """[Q, N] float64: stage 1's score of a two-stage index (Fp8Index, Fp4Index, PQIndex) under its metric for the queries q_hat as its
+    stage 1 sees them -- alpha q_hat . x_hat + bias (+ extra) from index.dequantised(), for l2 minus |q_hat|^2 and at most 0; a removed
+    row is -inf.  On the CPU."""
+    from coati_amd import search as S
+    bias = index.bias.cpu() if extra is None else index.bias.cpu() + extra.cpu()
+    s = score_matrix(index.dequantised().cpu(), bias, q_hat, S.metric_alpha(index.metric))
+    if index.metric == "l2":
+        s = (s - (q_hat.double() ** 2).sum(dim=1, keepdim=True)).clamp_max(0.0)
+    return s
+
+
+def stage1_search(index, q_hat, k, extra=None):
+    """the oracle of index.search(queries, k, rescore=False): (scores [Q, k] float64, rows [Q, k] int64, the score matrix)"""
+    s = stage1_scores(index, q_hat, extra)
+    val, idx = topk(s, k)
+    return val, idx, s
+
+
+def two_stage_search(cand, index, queries, k):
+    """the oracle of the two stages: the best k by index's exact float64 score among stage 1's candidates cand [Q, R] (-1 = none)"""
+    exact = index_scores(index, queries)
+    picked = torch.full_like(exact, NEG_INF)
+    ok = cand >= 0
+    picked.scatter_(1, cand.clamp_min(0), torch.where(ok, exact.gather(1, cand.clamp_min(0)), torch.full_like(exact[:, :1], NEG_INF).expand_as(cand)))
+    return topk(picked, k)
+
+
+def recall(rows, exact_rows):
+    """the fraction of the exact result's rows (>= 0) that `rows` holds, over all queries"""
+    rows, exact_rows = rows.cpu(), exact_rows.cpu()
+    want = exact_rows >= 0
+    hit = (exact_rows[:, :, None] == rows[:, None, :]).any(dim=2) & want
+    return float(hit.sum()) / max(int(want.sum()), 1)
+
+
+def clustered(N, E, seed, centres=200, noise=0.5):
+    """rows [N, E] and queries from the same law: `centres` Gaussian centres plus noise-sigma Gaussian noise"""
+    g = torch.Generator().manual_seed(seed)
+    c = torch.randn(centres, E, generator=g)
+    return lambda n: c[torch.randint(0, centres, (n,), generator=g)] + noise * torch.randn(n, E, generator=g)
+
+
 def ints(shape, seed, lo=-4, hi=4):
     """integer-valued f32 in lo .. hi: every score is exact, and ties abound"""
     return torch.randint(lo, hi + 1, shape, generator=torch.Generator().manual_seed(seed)).to(torch.float32)

@@ -2,6 +2,7 @@
 float64 restatement of tests/search_util.py.  Integer data is exact in bf16 and in f32 in any summation order, so those cases must
 EQUAL the oracle element for element, ties and padding included; real-valued data is held to a bound derived from f32 accumulation."""
 import contextlib
+import inspect
 import io
 import json
 import os
@@ -104,6 +105,27 @@ def test_result_does_not_depend_on_the_slices():
         assert torch.equal(s, s2) and torch.equal(r, r2), slices
     with pytest.raises(ValueError):
         index.search(q, k, slices=30720 // k + 1)
+
+
+@pytest.mark.parametrize("kind,rescore", [("exact", None), ("fp8", True), ("fp8", False), ("fp4", True), ("fp4", False), ("pq", True),
+                                          ("pq", False)])
+def test_flat_query_chunks_give_the_same_result(monkeypatch, kind, rescore):
+    """the partial lists of a call stay within a scratch budget (coati_amd.search.sliced_topk, the loop of EmbeddingIndex, Fp8Index,
+    Fp4Index and PQIndex): with the budget cut to 7 queries' worth, 40 queries go in six calls and the result is the whole search's,
+    bit for bit.  Integer rows: ties abound, so the tie rule is under test."""
+    from coati_amd import search as search_mod
+    N, dim, Q, k = 1000, 64, 40, 5
+    index, q, kw, kk = _index(_ints((N, dim), 4100)), _ints((Q, dim), 4101), {}, k
+    if kind != "exact":
+        index, kw = getattr(index, kind)(), dict(rescore=rescore)
+        kk = k * inspect.signature(index.search).parameters["oversample"].default if rescore else k
+    s, r = index.search(q, k, **kw)
+    S = index._plan(Q, kk, None)[1]                                                 # what the whole search used
+    monkeypatch.setattr(search_mod, "SCRATCH_BYTES", 7 * S * kk * 8)
+    index._scratch = None
+    s2, r2 = index.search(q, k, slices=S, **kw)
+    assert index._scratch[0].numel() == 7 * S * kk
+    assert torch.equal(s2, s) and torch.equal(r2, r)
 
 
 # ---- 4. bias, removal, growth ------------------------------------------------------------------------------------------------

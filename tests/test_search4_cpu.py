@@ -225,6 +225,7 @@ def test_save_and_load_on_the_cpu(tmp_path, keep_rows):
     fp4.remove([3])
     path = str(tmp_path / "fp4.pt")
     fp4.save(path)
+    assert set(torch.load(path)) == {"dim", "dim_padded", "metric", "bias"} | ({"rows16", "bias16"} if keep_rows else {"codes", "scales"})
     again = F.Fp4Index.load(path, device="cpu")
     assert len(again) == 300 and again.keep_rows == keep_rows and again.metric == "l2" and again.dim == 40 and again.dim_padded == 64
     assert torch.equal(again.codes, fp4.codes) and torch.equal(again.scales, fp4.scales) and torch.equal(again.bias, fp4.bias)

@@ -189,6 +189,7 @@ def test_save_and_load_on_the_cpu(tmp_path, keep_rows):
     fp8.remove([3])
     path = str(tmp_path / "fp8.pt")
     fp8.save(path)
+    assert set(torch.load(path)) == {"dim", "dim_padded", "metric", "bias"} | ({"rows16", "bias16"} if keep_rows else {"vectors8", "scales"})
     again = F.Fp8Index.load(path, device="cpu")
     assert len(again) == 300 and again.keep_rows == keep_rows and again.metric == "l2" and again.dim == 40 and again.dim_padded == 64
     assert torch.equal(again.vectors8, fp8.vectors8) and torch.equal(again.scales, fp8.scales) and torch.equal(again.bias, fp8.bias)
