@@ -1,6 +1,6 @@
 """ctypes binding of libcoati_hip.so.  Every signature, the config struct and the ABI version are read from the C ABI's own header
 (include/coati_hip.h, _abi.py), the beam-search entries from include/coati_beam.h, the library-search entries from include/coati_search.h,
-the constrained-decoding entry from include/coati_grammar.h, the property-head entry from include/coati_screen.h, its input gradient from include/coati_guide.h, the GP head from include/coati_gp.h, the gradient of its acquisition from include/coati_acq.h, library clustering from include/coati_cluster.h, IVF approximate search from include/coati_ivf.h, radius search from include/coati_radius.h, the point encoder's kernels one by one from include/coati_gnn_ops.h, quantised search from include/coati_search8.h, IVF search over fp8 lists from include/coati_ivf8.h, radius search over inverted lists from include/coati_ivf_radius.h, product-quantised search from include/coati_pq.h, IVF search over lists of residual PQ codes from include/coati_ivfpq.h, four-bit search from include/coati_search4.h: nothing of it is restated here.  There is no CPU fallback: if the library is missing or a call fails, a
+the constrained-decoding entry from include/coati_grammar.h, the property-head entry from include/coati_screen.h, its input gradient from include/coati_guide.h, the GP head from include/coati_gp.h, the gradient of its acquisition from include/coati_acq.h, library clustering from include/coati_cluster.h, IVF approximate search from include/coati_ivf.h, radius search from include/coati_radius.h, the point encoder's kernels one by one from include/coati_gnn_ops.h, quantised search from include/coati_search8.h, IVF search over fp8 lists from include/coati_ivf8.h, radius search over inverted lists from include/coati_ivf_radius.h, product-quantised search from include/coati_pq.h, IVF search over lists of residual PQ codes from include/coati_ivfpq.h, four-bit search from include/coati_search4.h, embedding maps from include/coati_tsne.h: nothing of it is restated here.  There is no CPU fallback: if the library is missing or a call fails, a
 RuntimeError is raised."""
 import ctypes
 import os
@@ -103,6 +103,11 @@ try:
         _SEARCH4_ABI = _abi.parse(_f.read(), guard="COATI_SEARCH4_H", name="coati_search4.h", base=_ABI)
 except OSError as e:
     raise RuntimeError(f"coati_amd: cannot read {_build.SEARCH4_HEADER}, which the binding of the four-bit search is derived from: {e}") from e
+try:
+    with open(_build.TSNE_HEADER) as _f:
+        _TSNE_ABI = _abi.parse(_f.read(), guard="COATI_TSNE_H", name="coati_tsne.h", base=_ABI)
+except OSError as e:
+    raise RuntimeError(f"coati_amd: cannot read {_build.TSNE_HEADER}, which the binding of the embedding maps is derived from: {e}") from e
 
 PROTOTYPES = _ABI.prototypes        # name -> (restype, argtypes), the operators of csrc/experimental/ included
 CoatiConfig = _ABI.CoatiConfig
@@ -125,6 +130,7 @@ IVF_RADIUS_PROTOTYPES = _IVF_RADIUS_ABI.prototypes   # the entries of include/co
 PQ_PROTOTYPES = _PQ_ABI.prototypes   # the entries of include/coati_pq.h, likewise
 IVFPQ_PROTOTYPES = _IVFPQ_ABI.prototypes   # the entries of include/coati_ivfpq.h, likewise
 SEARCH4_PROTOTYPES = _SEARCH4_ABI.prototypes   # the entries of include/coati_search4.h, likewise
+TSNE_PROTOTYPES = _TSNE_ABI.prototypes   # the entries of include/coati_tsne.h, likewise
 
 _lib = None
 
@@ -153,14 +159,14 @@ def lib():
     import torch  # noqa: F401
     l = ctypes.CDLL(path)
     # operators of csrc/experimental/ are only in libcoati_hip_x.so (COATI_AMD_EXPERIMENTAL=1, build.py): bound when the loaded library has them
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BEAM_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items()) + list(GRAMMAR_PROTOTYPES.items()) + list(SCREEN_PROTOTYPES.items()) + list(GUIDE_PROTOTYPES.items()) + list(LN_XHAT_PROTOTYPES.items()) + list(GP_PROTOTYPES.items()) + list(ACQ_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(IVF_PROTOTYPES.items()) + list(RADIUS_PROTOTYPES.items()) + list(GNN_OPS_PROTOTYPES.items()) + list(SEARCH8_PROTOTYPES.items()) + list(IVF8_PROTOTYPES.items()) + list(IVF_RADIUS_PROTOTYPES.items()) + list(PQ_PROTOTYPES.items()) + list(IVFPQ_PROTOTYPES.items()) + list(SEARCH4_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BEAM_PROTOTYPES.items()) + list(SEARCH_PROTOTYPES.items()) + list(GRAMMAR_PROTOTYPES.items()) + list(SCREEN_PROTOTYPES.items()) + list(GUIDE_PROTOTYPES.items()) + list(LN_XHAT_PROTOTYPES.items()) + list(GP_PROTOTYPES.items()) + list(ACQ_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(IVF_PROTOTYPES.items()) + list(RADIUS_PROTOTYPES.items()) + list(GNN_OPS_PROTOTYPES.items()) + list(SEARCH8_PROTOTYPES.items()) + list(IVF8_PROTOTYPES.items()) + list(IVF_RADIUS_PROTOTYPES.items()) + list(PQ_PROTOTYPES.items()) + list(IVFPQ_PROTOTYPES.items()) + list(SEARCH4_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()):
         if hasattr(l, name):
             getattr(l, name).restype = restype
             getattr(l, name).argtypes = argtypes
     if l.coati_abi_version() != ABI_VERSION:
         raise RuntimeError(f"coati_amd: {path} has ABI version {l.coati_abi_version()}, this package expects {ABI_VERSION}; "
                            "rebuild with `python -m coati_amd.build --force`")
-    missing = [n for n in exported_symbols() + sorted(BEAM_PROTOTYPES) + sorted(SEARCH_PROTOTYPES) + sorted(GRAMMAR_PROTOTYPES) + sorted(SCREEN_PROTOTYPES) + sorted(GUIDE_PROTOTYPES) + sorted(LN_XHAT_PROTOTYPES) + sorted(GP_PROTOTYPES) + sorted(ACQ_PROTOTYPES) + sorted(CLUSTER_PROTOTYPES) + sorted(IVF_PROTOTYPES) + sorted(RADIUS_PROTOTYPES) + sorted(GNN_OPS_PROTOTYPES) + sorted(SEARCH8_PROTOTYPES) + sorted(IVF8_PROTOTYPES) + sorted(IVF_RADIUS_PROTOTYPES) + sorted(PQ_PROTOTYPES) + sorted(IVFPQ_PROTOTYPES) + sorted(SEARCH4_PROTOTYPES) if not hasattr(l, n)]
+    missing = [n for n in exported_symbols() + sorted(BEAM_PROTOTYPES) + sorted(SEARCH_PROTOTYPES) + sorted(GRAMMAR_PROTOTYPES) + sorted(SCREEN_PROTOTYPES) + sorted(GUIDE_PROTOTYPES) + sorted(LN_XHAT_PROTOTYPES) + sorted(GP_PROTOTYPES) + sorted(ACQ_PROTOTYPES) + sorted(CLUSTER_PROTOTYPES) + sorted(IVF_PROTOTYPES) + sorted(RADIUS_PROTOTYPES) + sorted(GNN_OPS_PROTOTYPES) + sorted(SEARCH8_PROTOTYPES) + sorted(IVF8_PROTOTYPES) + sorted(IVF_RADIUS_PROTOTYPES) + sorted(PQ_PROTOTYPES) + sorted(IVFPQ_PROTOTYPES) + sorted(SEARCH4_PROTOTYPES) + sorted(TSNE_PROTOTYPES) if not hasattr(l, n)]
     if missing:
         raise RuntimeError(f"coati_amd: {path} lacks symbols {missing[:6]}; rebuild with `python -m coati_amd.build --force`")
     _lib = l

@@ -29,7 +29,8 @@ IVF_RADIUS_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ivf_ra
 PQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_pq.h")   # product-quantised search: a seventeenth
 IVFPQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ivfpq.h")   # IVF search over lists of residual PQ codes: an eighteenth
 SEARCH4_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_search4.h")   # four-bit (MX fp4) search: a nineteenth
-HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip", "guide.hip", "gp.hip", "gp_grad.hip", "cluster.hip", "ivf.hip", "radius.hip", "search8.hip", "ivf8.hip", "ivf_radius.hip", "pq.hip", "ivfpq.hip", "search4.hip"]
+TSNE_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_tsne.h")   # embedding maps (exact t-SNE): a twentieth
+HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip", "guide.hip", "gp.hip", "gp_grad.hip", "cluster.hip", "ivf.hip", "radius.hip", "search8.hip", "ivf8.hip", "ivf_radius.hip", "pq.hip", "ivfpq.hip", "search4.hip", "tsne.hip"]
 CPP_UNITS = ["engine.cpp", "capi.cpp", "tokenizer.cpp", "comm.cpp"]
 # -amdgpu-mfma-vgpr-form: MFMA results in VGPRs (gfx950 has one unified register file).  Where the compiler picked the AGPR form
 # (the attention forward kernels) 13 % of the instructions were v_accvgpr_read / write moves in a VALU-bound kernel
@@ -60,7 +61,7 @@ def _sources():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if not os.path.isdir(os.path.join(CSRC, f))]
     if EXPERIMENTAL:
         deps += [os.path.join(CSRC, "experimental", f) for f in os.listdir(os.path.join(CSRC, "experimental"))]
-    deps += [HEADER, BEAM_HEADER, SEARCH_HEADER, GRAMMAR_HEADER, SCREEN_HEADER, GUIDE_HEADER, LN_XHAT_HEADER, GP_HEADER, ACQ_HEADER, CLUSTER_HEADER, IVF_HEADER, RADIUS_HEADER, GNN_OPS_HEADER, SEARCH8_HEADER, IVF8_HEADER, IVF_RADIUS_HEADER, PQ_HEADER, IVFPQ_HEADER, SEARCH4_HEADER]
+    deps += [HEADER, BEAM_HEADER, SEARCH_HEADER, GRAMMAR_HEADER, SCREEN_HEADER, GUIDE_HEADER, LN_XHAT_HEADER, GP_HEADER, ACQ_HEADER, CLUSTER_HEADER, IVF_HEADER, RADIUS_HEADER, GNN_OPS_HEADER, SEARCH8_HEADER, IVF8_HEADER, IVF_RADIUS_HEADER, PQ_HEADER, IVFPQ_HEADER, SEARCH4_HEADER, TSNE_HEADER]
     return deps
 
 

@@ -19,6 +19,7 @@
 #include "../../include/coati_pq.h"
 #include "../../include/coati_ivfpq.h"
 #include "../../include/coati_search4.h"
+#include "../../include/coati_tsne.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
@@ -470,6 +471,22 @@ int coati_search4_topk(const uint8_t* codes, const uint8_t* scales, int64_t N, i
                              reinterpret_cast<long long*>(out_row), S_(stream));
 }
 int coati_search4_slices(int64_t N, int Q, int k) { return search4_slices(N, Q, k); }
+// embedding maps (include/coati_tsne.h)
+int coati_tsne_affinities(const float* d2, const int32_t* nbr, int64_t N, int k, float perplexity, int steps, float* p, float* beta,
+                          void* stream) {
+  return launch_tsne_affinities(d2, nbr, N, k, perplexity, steps, p, beta, S_(stream));
+}
+int coati_tsne_repulsion(const float* y, int64_t N, float* rep, float* z, float* part, int64_t part_floats, int blocks, void* stream) {
+  return launch_tsne_repulsion(y, N, rep, z, part, part_floats, blocks, S_(stream));
+}
+int coati_tsne_chunk(void) { return tsne_chunk(); }
+int64_t coati_tsne_part_floats(int64_t N) { return tsne_part_floats(N); }
+int coati_tsne_step(const float* y, const float* rep, const float* zsum, const int64_t* offsets, const int32_t* cols, const float* vals,
+                    int64_t N, float exaggeration, float momentum, float lr, float min_gain, float* update, float* gains, float* y_out,
+                    float* kl_rows, float* att, void* stream) {
+  return launch_tsne_step(y, rep, zsum, LL(offsets), cols, vals, N, exaggeration, momentum, lr, min_gain, update, gains, y_out, kl_rows, att,
+                          S_(stream));
+}
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,
                            int64_t* tok_next, int32_t* done, int Tmax, int stop_token, void* stream) {

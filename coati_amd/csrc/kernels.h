@@ -472,6 +472,16 @@ int launch_search4_topk(const unsigned char* codes, const unsigned char* scales,
                         const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
                         long long* out_row, hipStream_t s);
 int search4_slices(long long N, int Q, int k);   // host only: the default S
+// embedding maps (tsne.hip, include/coati_tsne.h): the conditional probabilities over a kNN graph by a fixed-length bisection; the all-pairs
+// repulsive sums in chunks of tsne_chunk() points (through part [chunks][3][N] when given and the tiles are few; no result depends on it or
+// on blocks); one iteration's attraction over the CSR joint P, gradient and gains / momentum update
+int launch_tsne_affinities(const float* d2, const int* nbr, long long N, int k, float perplexity, int steps, float* p, float* beta, hipStream_t s);
+int launch_tsne_repulsion(const float* y, long long N, float* rep, float* z, float* part, long long part_floats, int blocks, hipStream_t s);
+int launch_tsne_step(const float* y, const float* rep, const float* zsum, const long long* offsets, const int* cols, const float* vals, long long N,
+                     float exaggeration, float momentum, float lr, float min_gain, float* update, float* gains, float* y_out, float* kl_rows,
+                     float* att, hipStream_t s);
+int tsne_chunk(void);                        // host only
+long long tsne_part_floats(long long N);     // host only
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

@@ -413,6 +413,19 @@ class EmbeddingIndex:
         from . import radius
         return radius.dedup(self, threshold)
 
+    def knn_graph(self, k, chunk=4096):
+        """(rows int64 [n], nbr int32 [n, k], d2 f32 [n, k]): every live row's k nearest other live rows as positions in `rows`, and the
+        squared distances to them (coati_amd.tsne.knn_graph); "cosine" or "l2", 1 <= k <= 127."""
+        from . import tsne
+        return tsne.knn_graph(self, k, chunk)
+
+    def tsne(self, perplexity=30.0, iters=1000, seed=0, k=None, **layout):
+        """A coati_amd.tsne.TSNEResult: the exact t-SNE map of the live rows in two dimensions, reproducible bit for bit from `seed`.
+        y [len(index), 2] f32 by row, NaN for removed rows.  k: the neighbours P is held on, default min(n - 1, int(3 perplexity), 127);
+        **layout: coati_amd.tsne.layout's arguments (lr, exaggeration, momentum, init, kl_every, ...)."""
+        from . import tsne
+        return tsne.tsne_index(self, perplexity, iters, seed, k, **layout)
+
     def _rescore(self, q32, scores, rows, k):
         """the candidates' scores from the f32 copies (a gather and a bmm over [Q, m k, E]), re-sorted: score descending, row ascending"""
         pad = rows < 0
