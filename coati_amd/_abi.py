@@ -1,6 +1,6 @@
 """Reads include/coati_hip.h into ctypes signatures, so that the Python binding cannot disagree with the C ABI.  No C parser: the header
 is one extern "C" block of prototypes over a handful of scalar types, one struct, one anonymous enum and opaque typedefs, and anything
-else at file scope is an error here, never skipped.  A further header of the same library (include/coati_beam.h, include/coati_search.h, include/coati_grammar.h, include/coati_radius.h, include/coati_gnn_ops.h, include/coati_search8.h, include/coati_pq.h) is read the same way,
+else at file scope is an error here, never skipped.  A feature header of the same library (the table build.FEATURE_HEADERS lists them) is read the same way,
 against the first one's coati_config and scalar types (parse(..., base=)).  Imports neither torch nor the library."""
 import ctypes
 import re

@@ -11,25 +11,31 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libcoati_hip_x.so" if os.environ.get("COATI_AMD_EXPERIMENTAL") == "1" else "libcoati_hip.so")
 OBJDIR = os.path.join(HERE, "build")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_hip.h")   # the C ABI; _lib.py derives the ctypes binding from it
-BEAM_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_beam.h")   # beam search: a second header of the same library
-SEARCH_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_search.h")   # embedding-library search: a third one
-GRAMMAR_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_grammar.h")   # syntax-constrained decoding: a fourth
-SCREEN_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_screen.h")   # property heads on library rows: a fifth
-GUIDE_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_guide.h")   # the head's input gradient: a sixth
-LN_XHAT_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ln_xhat.h")   # the operators of "a fused LayerNorm saves xhat": a seventh
-GP_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_gp.h")   # the GP head on the property head's features: an eighth
-ACQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_acq.h")   # the gradient of a GP acquisition w.r.t. the input rows: a ninth
-CLUSTER_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_cluster.h")   # library clustering: a tenth
-IVF_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ivf.h")   # IVF approximate search: an eleventh
-RADIUS_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_radius.h")   # radius search: a twelfth
-GNN_OPS_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_gnn_ops.h")   # the point encoder's kernels one by one: a thirteenth
-SEARCH8_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_search8.h")   # quantised (fp8) search: a fourteenth
-IVF8_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ivf8.h")   # IVF search over fp8 lists: a fifteenth
-IVF_RADIUS_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ivf_radius.h")   # radius search over inverted lists: a sixteenth
-PQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_pq.h")   # product-quantised search: a seventeenth
-IVFPQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_ivfpq.h")   # IVF search over lists of residual PQ codes: an eighteenth
-SEARCH4_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_search4.h")   # four-bit (MX fp4) search: a nineteenth
-TSNE_HEADER = os.path.join(os.path.dirname(HERE), "include", "coati_tsne.h")   # embedding maps (exact t-SNE): a twentieth
+# The feature headers of the same library, one line each: (stem, what its entries are).  include/coati_<stem>.h is read by _lib.py into
+# <STEM>_PROTOTYPES and watched by needs_build(); adding a header is one line here, the header, and the unit that defines its entries
+FEATURE_HEADERS = [
+    ("beam", "beam search"),
+    ("search", "embedding-library search"),
+    ("grammar", "syntax-constrained decoding"),
+    ("screen", "property heads on library rows"),
+    ("guide", "the head's input gradient"),
+    ("ln_xhat", "the operators of \"a fused LayerNorm saves xhat\""),
+    ("gp", "the GP head on the property head's features"),
+    ("acq", "the gradient of a GP acquisition w.r.t. the input rows"),
+    ("cluster", "library clustering"),
+    ("ivf", "IVF approximate search"),
+    ("radius", "radius search"),
+    ("gnn_ops", "the point encoder's kernels one by one"),
+    ("search8", "quantised (fp8) search"),
+    ("ivf8", "IVF search over fp8 lists"),
+    ("ivf_radius", "radius search over inverted lists"),
+    ("pq", "product-quantised search"),
+    ("ivfpq", "IVF search over lists of residual PQ codes"),
+    ("search4", "four-bit (MX fp4) search"),
+    ("tsne", "embedding maps (exact t-SNE)"),
+]
+for _stem, _ in FEATURE_HEADERS:   # BEAM_HEADER ... TSNE_HEADER: the paths, as module attributes (_lib.py reads each through its attribute)
+    globals()[f"{_stem.upper()}_HEADER"] = os.path.join(os.path.dirname(HERE), "include", f"coati_{_stem}.h")
 HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip", "guide.hip", "gp.hip", "gp_grad.hip", "cluster.hip", "ivf.hip", "radius.hip", "search8.hip", "ivf8.hip", "ivf_radius.hip", "pq.hip", "ivfpq.hip", "search4.hip", "tsne.hip"]
 CPP_UNITS = ["engine.cpp", "capi.cpp", "tokenizer.cpp", "comm.cpp"]
 # -amdgpu-mfma-vgpr-form: MFMA results in VGPRs (gfx950 has one unified register file).  Where the compiler picked the AGPR form
@@ -61,7 +67,7 @@ def _sources():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if not os.path.isdir(os.path.join(CSRC, f))]
     if EXPERIMENTAL:
         deps += [os.path.join(CSRC, "experimental", f) for f in os.listdir(os.path.join(CSRC, "experimental"))]
-    deps += [HEADER, BEAM_HEADER, SEARCH_HEADER, GRAMMAR_HEADER, SCREEN_HEADER, GUIDE_HEADER, LN_XHAT_HEADER, GP_HEADER, ACQ_HEADER, CLUSTER_HEADER, IVF_HEADER, RADIUS_HEADER, GNN_OPS_HEADER, SEARCH8_HEADER, IVF8_HEADER, IVF_RADIUS_HEADER, PQ_HEADER, IVFPQ_HEADER, SEARCH4_HEADER, TSNE_HEADER]
+    deps += [HEADER] + [globals()[f"{stem.upper()}_HEADER"] for stem, _ in FEATURE_HEADERS]
     return deps
 
 

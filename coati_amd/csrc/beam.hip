@@ -4,6 +4,7 @@
 // A session of B = G * W rows serves G embeddings with W beams each (row g * W + r).  After every step the surviving beams are a
 // permutation-with-repeats of the previous ones.  A cache record (row, t) is written once and never changes, so the rows do not move:
 // anc[b][t] names the cache row that holds position t of beam b's history, at 4 extra bytes per 64 / 128-B record read.
+#include "../../include/coati_beam.h"
 #include "decode_dev.h"
 
 // The cached (row, head) sequence that holds position t of beam b: row anc[b * Tmax + t] (an entry outside 0 .. B - 1 reads row b).  A
@@ -85,12 +86,13 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restr
   }
 }
 
-int launch_beam_row_topk(const float* logits, long long ldl, int G, int W, int V, const float* cum, const int* fin, int pad_token,
-                         float* cand_score, int* cand_tok, hipStream_t s) {
+int coati_beam_row_topk(const float* logits, int64_t ldl, int G, int W, int V, const float* cum, const int32_t* fin, int pad_token,
+                        float* cand_score, int32_t* cand_tok, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(logits && cum && fin && cand_score && cand_tok, "beam_row_topk: null operand");
   COATI_CHECK_SHAPE(G > 0 && W >= 1 && W <= BEAM_MAX && V > 0 && W <= V && (size_t)V * 4 <= 120 * 1024 && ldl >= V &&
                         (long long)G * W <= 0x7fffffffLL,
-                    "beam_row_topk: unsupported shape G=%d W=%d V=%d ldl=%lld (1 <= W <= %d, W <= V)", G, W, V, ldl, BEAM_MAX);
+                    "beam_row_topk: unsupported shape G=%d W=%d V=%d ldl=%lld (1 <= W <= %d, W <= V)", G, W, V, (long long)ldl, BEAM_MAX);
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(beam_row_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
@@ -177,9 +179,11 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
   }
 }
 
-int launch_beam_merge(const float* cand_score, const int* cand_tok, int G, int W, const float* cum_in, const int* fin_in, const int* len_in,
-                      const int* anc_in, const long long* hist_in, long long ldh, int Tmax, int pos, int n, int stop_token, float* cum_out,
-                      int* fin_out, int* len_out, int* anc_out, long long* hist_out, long long* tok_next, int* nfin, hipStream_t s) {
+int coati_beam_merge(const float* cand_score, const int32_t* cand_tok, int G, int W, const float* cum_in, const int32_t* fin_in,
+                     const int32_t* len_in, const int32_t* anc_in, const int64_t* hist_in, int64_t ldh, int Tmax, int pos, int n,
+                     int stop_token, float* cum_out, int32_t* fin_out, int32_t* len_out, int32_t* anc_out, int64_t* hist_out,
+                     int64_t* tok_next, int32_t* nfin, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(cand_score && cand_tok && cum_in && fin_in && len_in && anc_in && hist_in && cum_out && fin_out && len_out && anc_out &&
                       hist_out && tok_next && nfin,
                   "beam_merge: null operand");
@@ -188,9 +192,9 @@ int launch_beam_merge(const float* cand_score, const int* cand_tok, int G, int W
   COATI_CHECK_SHAPE(G > 0 && W >= 1 && W <= BEAM_MAX && (long long)G * W <= 0x7fffffffLL && Tmax > 0 && pos >= 0 && pos < Tmax && n >= 0 &&
                         n < ldh,
                     "beam_merge: unsupported shape G=%d W=%d Tmax=%d pos=%d n=%d ldh=%lld (1 <= W <= %d, pos < Tmax, n < ldh)", G, W, Tmax,
-                    pos, n, ldh, BEAM_MAX);
-  hipLaunchKernelGGL(beam_merge_kernel, dim3(G), dim3(256), 0, s, cand_score, cand_tok, W, cum_in, fin_in, len_in, anc_in, hist_in, ldh, Tmax,
-                     pos, n, stop_token, cum_out, fin_out, len_out, anc_out, hist_out, tok_next, nfin);
+                    pos, n, (long long)ldh, BEAM_MAX);
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(G), dim3(256), 0, s, cand_score, cand_tok, W, cum_in, fin_in, len_in, anc_in, LL(hist_in), ldh, Tmax,
+                     pos, n, stop_token, cum_out, fin_out, len_out, anc_out, LL(hist_out), LL(tok_next), nfin);
   COATI_LAUNCH_CHECK("beam_merge");
   return COATI_OK;
 }

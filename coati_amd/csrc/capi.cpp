@@ -1,31 +1,13 @@
-// C ABI wrappers of the fine-grained operators (declared in include/coati_hip.h).
+// C ABI wrappers of the fine-grained operators (declared in include/coati_hip.h).  The entries of a feature header (include/coati_<x>.h)
+// are defined by the unit that implements them, compiled against that header; what is here are the ones whose launcher the engine calls too.
 #include <string.h>
 
 #include "../../include/coati_hip.h"
 #include "../../include/coati_beam.h"
-#include "../../include/coati_search.h"
-#include "../../include/coati_grammar.h"
-#include "../../include/coati_screen.h"
-#include "../../include/coati_guide.h"
 #include "../../include/coati_ln_xhat.h"
-#include "../../include/coati_gp.h"
-#include "../../include/coati_acq.h"
-#include "../../include/coati_cluster.h"
-#include "../../include/coati_ivf.h"
-#include "../../include/coati_radius.h"
-#include "../../include/coati_search8.h"
-#include "../../include/coati_ivf8.h"
-#include "../../include/coati_ivf_radius.h"
-#include "../../include/coati_pq.h"
-#include "../../include/coati_ivfpq.h"
-#include "../../include/coati_search4.h"
-#include "../../include/coati_tsne.h"
 #include "../../include/coati_gnn_ops.h"
 #include <vector>
 #include "kernels.h"
-
-#define S_(x) ((hipStream_t)(x))
-#define LL(x) (reinterpret_cast<const long long*>(x))
 
 extern "C" {
 
@@ -306,186 +288,10 @@ int coati_attn_decode_rows(const uint16_t* qkv, uint16_t* cache, uint16_t* y, in
                            void* stream) {
   return launch_attn_decode_rows(qkv, cache, y, B, n_head, head_size, Tmax, pos, S_(stream));
 }
-// beam search (include/coati_beam.h)
+// beam search (include/coati_beam.h): its other entries are defined in beam.hip, as every other feature header's are in their unit
 int coati_attn_decode_anc(const uint16_t* qkv, uint16_t* cache, uint16_t* y, int B, int n_head, int head_size, int Tmax, int pos,
                           const int32_t* anc, void* stream) {
   return launch_attn_decode_anc(qkv, cache, y, B, n_head, head_size, Tmax, pos, anc, S_(stream));
-}
-int coati_beam_row_topk(const float* logits, int64_t ldl, int G, int W, int V, const float* cum, const int32_t* fin, int pad_token,
-                        float* cand_score, int32_t* cand_tok, void* stream) {
-  return launch_beam_row_topk(logits, ldl, G, W, V, cum, fin, pad_token, cand_score, cand_tok, S_(stream));
-}
-int coati_beam_merge(const float* cand_score, const int32_t* cand_tok, int G, int W, const float* cum_in, const int32_t* fin_in,
-                     const int32_t* len_in, const int32_t* anc_in, const int64_t* hist_in, int64_t ldh, int Tmax, int pos, int n,
-                     int stop_token, float* cum_out, int32_t* fin_out, int32_t* len_out, int32_t* anc_out, int64_t* hist_out,
-                     int64_t* tok_next, int32_t* nfin, void* stream) {
-  return launch_beam_merge(cand_score, cand_tok, G, W, cum_in, fin_in, len_in, anc_in, LL(hist_in), ldh, Tmax, pos, n, stop_token, cum_out,
-                           fin_out, len_out, anc_out, reinterpret_cast<long long*>(hist_out), reinterpret_cast<long long*>(tok_next), nfin,
-                           S_(stream));
-}
-// embedding-library search (include/coati_search.h)
-int coati_search_topk(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, int k, float alpha, int S,
-                      float* part_score, int32_t* part_row, float* out_score, int64_t* out_row, void* stream) {
-  return launch_search_topk(lib, N, E, bias, q, Q, k, alpha, S, part_score, part_row, out_score, reinterpret_cast<long long*>(out_row),
-                            S_(stream));
-}
-int coati_search_slices(int64_t N, int Q, int k) { return search_slices(N, Q, k); }
-// syntax-constrained decoding (include/coati_grammar.h)
-int coati_grammar_step(float* logits, int64_t ldl, int B, int V, const uint64_t* table, const int32_t* state_in, int32_t* state_out,
-                       const int64_t* tok_prev, const int32_t* parent, int remaining, int stop_token, void* stream) {
-  return launch_grammar_step(logits, ldl, B, V, reinterpret_cast<const unsigned long long*>(table), state_in, state_out, LL(tok_prev), parent,
-                             remaining, stop_token, S_(stream));
-}
-// property heads (include/coati_screen.h)
-int coati_head_eval(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
-                    int D, const float* wl, const float* bl, int P, int F, float* out, int64_t ldo, void* stream) {
-  return launch_head_eval(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, F, out, ldo, S_(stream));
-}
-
-// the head's input gradient (include/coati_guide.h)
-int coati_head_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
-                    int D, const float* wl, const float* bl, int P, int F, const uint16_t* w0t, const uint16_t* wrt, const float* cot,
-                    int64_t ldc, float* out, int64_t ldo, float* g, int64_t ldg, void* stream) {
-  return launch_head_grad(x, ldx, N, E, w0, b0, wr, br, D, wl, bl, P, F, w0t, wrt, cot, ldc, out, ldo, g, ldg, S_(stream));
-}
-// the GP head on the property head's features (include/coati_gp.h)
-int coati_head_gp(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
-                  int D, int F, const float* wl, const float* bl, int P_lin, float* out, int64_t ldo, const uint16_t* z, const float* zn,
-                  const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, int64_t ldm,
-                  float* var, void* stream) {
-  return launch_head_gp(x, ldx, N, E, w0, b0, wr, br, D, F, wl, bl, P_lin, out, ldo, z, zn, alpha, q, c, inv2l2, s2, P, Mp, mean, ldm, var,
-                        S_(stream));
-}
-// the gradient of a GP acquisition with respect to the input rows (include/coati_acq.h)
-int coati_head_gp_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr,
-                       const float* br, int D, int F, const uint16_t* w0t, const uint16_t* wrt, const uint16_t* z, const uint16_t* zt,
-                       const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
-                       const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, int64_t ldm,
-                       float* var, float* acq, float* g, int64_t ldg, void* stream) {
-  return launch_head_gp_grad(x, ldx, N, E, w0, b0, wr, br, D, F, w0t, wrt, z, zt, zn, alpha, qs, c, inv2l2, s2, P, Mp, wm, kappa, var_add, mode,
-                             best, rs, mean, ldm, var, acq, g, ldg, S_(stream));
-}
-// library clustering (include/coati_cluster.h)
-int coati_cluster_assign(const uint16_t* lib, int64_t N, int E, const float* row_bias, const uint16_t* c, int K, const float* cbias,
-                         int32_t* assign, float* best, int blocks, void* stream) {
-  return launch_cluster_assign(lib, N, E, row_bias, c, K, cbias, assign, best, blocks, S_(stream));
-}
-int coati_cluster_sums(const uint16_t* lib, int64_t N, int E, const int32_t* order, int64_t M, const int32_t* offsets,
-                       const int32_t* item_off, int K, float* part, int64_t items_max, float* sums, int blocks, void* stream) {
-  return launch_cluster_sums(lib, N, E, order, M, offsets, item_off, K, part, items_max, sums, blocks, S_(stream));
-}
-int coati_cluster_chunk(void) { return cluster_chunk(); }
-int64_t coati_cluster_items_max(int64_t M, int K) { return cluster_items_max(M, K); }
-// IVF approximate search (include/coati_ivf.h)
-int coati_ivf_scan(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
-                   const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P, int k,
-                   float alpha, int seg_rows, int segs, float* part_score, int32_t* part_row, int blocks, void* stream) {
-  return launch_ivf_scan(lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs, part_score, part_row,
-                         blocks, S_(stream));
-}
-int coati_ivf_merge(const float* part_score, const int32_t* part_row, const int32_t* probes, const int32_t* pair_slot, int64_t P,
-                    const int32_t* list_off, int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, int64_t* out_row,
-                    void* stream) {
-  return launch_ivf_merge(part_score, part_row, probes, pair_slot, P, list_off, L, Q, nprobe, k, seg_rows, segs, out_score,
-                          reinterpret_cast<long long*>(out_row), S_(stream));
-}
-int64_t coati_ivf_plan(int64_t max_list_rows, int Q, int nprobe, int k) { return ivf_plan(max_list_rows, Q, nprobe, k); }
-// IVF search over fp8 lists (include/coati_ivf8.h)
-int coati_ivf8_scan(const uint8_t* lib8, const float* scale, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E,
-                    int L, const uint8_t* q8, const float* qscale, int Q, const int32_t* pair_q, const int32_t* pair_off,
-                    const int32_t* item_off, int64_t P, int k, float alpha, int seg_rows, int segs, float* part_score, int32_t* part_row,
-                    int blocks, void* stream) {
-  return launch_ivf8_scan(lib8, scale, ids, bias, list_off, M, E, L, q8, qscale, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs,
-                          part_score, part_row, blocks, S_(stream));
-}
-// radius search (include/coati_radius.h)
-int coati_radius_count(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
-                       int clamp0, const float* thr, const int32_t* row_hi, int S, int32_t* counts, void* stream) {
-  return launch_radius_count(lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, S_(stream));
-}
-int coati_radius_fill(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
-                      int clamp0, const float* thr, const int32_t* row_hi, int S, const int32_t* counts, const int64_t* offsets,
-                      float* out_score, int64_t* out_row, void* stream) {
-  return launch_radius_fill(lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, LL(offsets), out_score,
-                            reinterpret_cast<long long*>(out_row), S_(stream));
-}
-int coati_radius_slices(int64_t N, int Q) { return radius_slices(N, Q); }
-// radius search over inverted lists (include/coati_ivf_radius.h)
-int coati_ivf_radius_count(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
-                           const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P,
-                           float alpha, const float* sub, int clamp0, const float* thr, const int32_t* row_hi, int seg_rows, int segs,
-                           int32_t* counts, int blocks, void* stream) {
-  return launch_ivf_radius_count(lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, alpha, sub, clamp0, thr, row_hi, seg_rows,
-                                 segs, counts, blocks, S_(stream));
-}
-int coati_ivf_radius_fill(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
-                          const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P,
-                          float alpha, const float* sub, int clamp0, const float* thr, const int32_t* row_hi, int seg_rows, int segs,
-                          const int32_t* counts, const int64_t* offsets, float* out_score, int64_t* out_row, int blocks, void* stream) {
-  return launch_ivf_radius_fill(lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, alpha, sub, clamp0, thr, row_hi, seg_rows,
-                                segs, counts, LL(offsets), out_score, reinterpret_cast<long long*>(out_row), blocks, S_(stream));
-}
-// quantised search (include/coati_search8.h)
-int coati_quant_rows_fp8(const uint16_t* x, int64_t n, int E, uint8_t* out, float* scale, void* stream) {
-  return launch_quant_rows_fp8(x, n, E, out, scale, S_(stream));
-}
-int coati_search8_topk(const uint8_t* lib8, const float* scale, int64_t N, int E, const float* bias, const uint8_t* q8, const float* qscale,
-                       int Q, int k, float alpha, int S, float* part_score, int32_t* part_row, float* out_score, int64_t* out_row,
-                       void* stream) {
-  return launch_search8_topk(lib8, scale, N, E, bias, q8, qscale, Q, k, alpha, S, part_score, part_row, out_score,
-                             reinterpret_cast<long long*>(out_row), S_(stream));
-}
-int coati_search_rescore(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, const int64_t* cand, int R, int k,
-                         float alpha, float* out_score, int64_t* out_row, void* stream) {
-  return launch_search_rescore(lib, N, E, bias, q, Q, LL(cand), R, k, alpha, out_score, reinterpret_cast<long long*>(out_row), S_(stream));
-}
-int coati_search8_slices(int64_t N, int Q, int k) { return search8_slices(N, Q, k); }
-// product-quantised search (include/coati_pq.h)
-int coati_pq_encode(const uint16_t* x, int64_t n, int E, const uint16_t* codebook, uint8_t* codes, void* stream) {
-  return launch_pq_encode(x, n, E, codebook, codes, S_(stream));
-}
-int coati_pq_topk(const uint8_t* codes, int64_t N, int E, const uint16_t* codebook, const float* bias, const uint16_t* q, int Q, int k,
-                  float alpha, int S, float* part_score, int32_t* part_row, float* out_score, int64_t* out_row, void* stream) {
-  return launch_pq_topk(codes, N, E, codebook, bias, q, Q, k, alpha, S, part_score, part_row, out_score, reinterpret_cast<long long*>(out_row),
-                        S_(stream));
-}
-int coati_pq_k_max(int E) { return pq_k_max(E); }
-int coati_pq_slices(int64_t N, int E, int Q, int k) { return pq_slices(N, E, Q, k); }
-// IVF-PQ search (include/coati_ivfpq.h)
-int coati_ivfpq_scan(const uint8_t* codes, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
-                     const uint16_t* centres, const uint16_t* codebook, const uint16_t* q, int Q, const int32_t* pair_q,
-                     const int32_t* pair_off, const int32_t* item_off, int64_t P, int k, float alpha, int seg_rows, int segs,
-                     float* part_score, int32_t* part_row, int blocks, void* stream) {
-  return launch_ivfpq_scan(codes, ids, bias, list_off, M, E, L, centres, codebook, q, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs,
-                           part_score, part_row, blocks, S_(stream));
-}
-int coati_ivfpq_k_max(int E) { return ivfpq_k_max(E); }
-// four-bit search (include/coati_search4.h)
-int coati_quant_rows_fp4(const uint16_t* x, int64_t n, int E, uint8_t* codes, uint8_t* scales, void* stream) {
-  return launch_quant_rows_fp4(x, n, E, codes, scales, S_(stream));
-}
-int coati_search4_topk(const uint8_t* codes, const uint8_t* scales, int64_t N, int E4, const float* bias, const uint8_t* q8,
-                       const float* qscale, int Q, int k, float alpha, int S, float* part_score, int32_t* part_row, float* out_score,
-                       int64_t* out_row, void* stream) {
-  return launch_search4_topk(codes, scales, N, E4, bias, q8, qscale, Q, k, alpha, S, part_score, part_row, out_score,
-                             reinterpret_cast<long long*>(out_row), S_(stream));
-}
-int coati_search4_slices(int64_t N, int Q, int k) { return search4_slices(N, Q, k); }
-// embedding maps (include/coati_tsne.h)
-int coati_tsne_affinities(const float* d2, const int32_t* nbr, int64_t N, int k, float perplexity, int steps, float* p, float* beta,
-                          void* stream) {
-  return launch_tsne_affinities(d2, nbr, N, k, perplexity, steps, p, beta, S_(stream));
-}
-int coati_tsne_repulsion(const float* y, int64_t N, float* rep, float* z, float* part, int64_t part_floats, int blocks, void* stream) {
-  return launch_tsne_repulsion(y, N, rep, z, part, part_floats, blocks, S_(stream));
-}
-int coati_tsne_chunk(void) { return tsne_chunk(); }
-int64_t coati_tsne_part_floats(int64_t N) { return tsne_part_floats(N); }
-int coati_tsne_step(const float* y, const float* rep, const float* zsum, const int64_t* offsets, const int32_t* cols, const float* vals,
-                    int64_t N, float exaggeration, float momentum, float lr, float min_gain, float* update, float* gains, float* y_out,
-                    float* kl_rows, float* att, void* stream) {
-  return launch_tsne_step(y, rep, zsum, LL(offsets), cols, vals, N, exaggeration, momentum, lr, min_gain, update, gains, y_out, kl_rows, att,
-                          S_(stream));
 }
 int coati_topk_sample_rows(const float* logits, int64_t ldl, int B, int V, int k, float inv_temp, const float* u, int64_t ldu,
                            const int64_t* prompt, int64_t ldp, const int32_t* plen, const int32_t* req, int32_t* pos, int64_t* out, int64_t ldo,

@@ -23,6 +23,7 @@
 // offsets) are cut into chunks of CL_CH; work item i = chunk i - item_off[k] of the cluster k found by bisection in item_off.  A workgroup
 // takes items in turn; E / 8 threads span a row (16-B loads), the 256 / (E / 8) groups of them take the chunk's rows p, p + R, ... in order,
 // and the groups' f32 sums are added in group order through LDS into part[item].  The finish adds a cluster's partial rows in chunk order.
+#include "../../include/coati_cluster.h"
 #include "kernels.h"
 
 #define CL_E_MAX 512
@@ -228,8 +229,9 @@ static int cluster_assign_launch(const bf16_t* lib, long long N, const float* ro
   return COATI_OK;
 }
 
-int launch_cluster_assign(const bf16_t* lib, long long N, int E, const float* row_bias, const bf16_t* c, int K, const float* cbias, int* assign,
-                          float* best, int blocks, hipStream_t s) {
+int coati_cluster_assign(const uint16_t* lib, int64_t N, int E, const float* row_bias, const uint16_t* c, int K, const float* cbias,
+                         int32_t* assign, float* best, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "cluster_assign: lib is null");
   COATI_CHECK_ARG(c, "cluster_assign: c is null");
   COATI_CHECK_ARG(assign, "cluster_assign: assign is null");
@@ -246,18 +248,19 @@ int launch_cluster_assign(const bf16_t* lib, long long N, int E, const float* ro
   return COATI_ESHAPE;
 }
 
-int cluster_chunk(void) { return CL_CH; }
+int coati_cluster_chunk(void) { return CL_CH; }
 
-long long cluster_items_max(long long M, int K) {
+int64_t coati_cluster_items_max(int64_t M, int K) {
   if (!(M >= 0 && M < (1ll << 31) && K >= 1 && K <= CL_K_MAX)) {
-    coati_set_error("cluster_items_max: M=%lld K=%d out of range", M, K);
+    coati_set_error("cluster_items_max: M=%lld K=%d out of range", (long long)M, K);
     return COATI_ESHAPE;
   }
   return M / CL_CH + K;
 }
 
-int launch_cluster_sums(const bf16_t* lib, long long N, int E, const int* order, long long M, const int* offsets, const int* item_off, int K,
-                        float* part, long long items_max, float* sums, int blocks, hipStream_t s) {
+int coati_cluster_sums(const uint16_t* lib, int64_t N, int E, const int32_t* order, int64_t M, const int32_t* offsets,
+                       const int32_t* item_off, int K, float* part, int64_t items_max, float* sums, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "cluster_sums: lib is null");
   COATI_CHECK_ARG(order, "cluster_sums: order is null");
   COATI_CHECK_ARG(offsets, "cluster_sums: offsets is null");
@@ -265,8 +268,8 @@ int launch_cluster_sums(const bf16_t* lib, long long N, int E, const int* order,
   COATI_CHECK_ARG(part, "cluster_sums: part is null");
   COATI_CHECK_ARG(sums, "cluster_sums: sums is null");
   COATI_TRY(cluster_check("cluster_sums", N, E, K, blocks));
-  COATI_CHECK_SHAPE(M >= 1 && M <= N, "cluster_sums: M=%lld outside 1 .. N=%lld", M, N);
-  COATI_CHECK_SHAPE(items_max >= M / CL_CH + K, "cluster_sums: items_max=%lld < M / %d + K = %lld", items_max, CL_CH, M / CL_CH + K);
+  COATI_CHECK_SHAPE(M >= 1 && M <= N, "cluster_sums: M=%lld outside 1 .. N=%lld", (long long)M, (long long)N);
+  COATI_CHECK_SHAPE(items_max >= M / CL_CH + K, "cluster_sums: items_max=%lld < M / %d + K = %lld", (long long)items_max, CL_CH, (long long)M / CL_CH + K);
   const long long most = M / CL_CH + K;
   const int grid = (int)(blocks > 0 && blocks < most ? blocks : (most < 4096 ? most : 4096));
   hipLaunchKernelGGL(cluster_partial_kernel, dim3(grid), dim3(256), 0, s, lib, N, E, order, M, offsets, item_off, K, part, items_max);

@@ -46,6 +46,12 @@ void coati_set_error(const char* fmt, ...);
     if (_rc != COATI_OK) return _rc; \
   } while (0)
 
+// What a C entry does with the two types of the public headers that the kernels spell differently: the stream arrives as void*, and
+// int64_t (long) and long long are both 64-bit here but distinct types to the compiler
+inline hipStream_t S_(void* stream) { return (hipStream_t)stream; }
+inline const long long* LL(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+inline long long* LL(int64_t* p) { return reinterpret_cast<long long*>(p); }
+
 // ---- bf16 <-> f32: hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32 on gfx950), the same rounding
 // as torch's .bfloat16() -------------------------------------------------------------------------------
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));

@@ -3,6 +3,7 @@
 // forward, instruction for instruction (with wl given it also writes coati_head_eval's out), then the GP tail on the stream the forward
 // leaves in registers: one more chained bf16 product against the inducing points, Mp exponentials per row, a dot product per output and a
 // quadratic form on the f32 matrix cores.  The library is read once, no [N, F] feature matrix exists in memory; no atomics, no workspace.
+#include "../../include/coati_gp.h"
 #include "head_dev.h"
 
 template <int F, int WAVES, int NP>
@@ -29,10 +30,11 @@ static void head_gp_launch(const bf16_t* x, long long ldx, long long N, int E, c
 
 static bool gp_aligned16(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; }
 
-int launch_head_gp(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
-                   int D, int F, const float* wl, const float* bl, int P_lin, float* out, long long ldo, const bf16_t* z, const float* zn,
-                   const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, long long ldm,
-                   float* var, hipStream_t s) {
+int coati_head_gp(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
+                  int D, int F, const float* wl, const float* bl, int P_lin, float* out, int64_t ldo, const uint16_t* z, const float* zn,
+                  const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, int64_t ldm,
+                  float* var, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x, "head_gp: x is null");
   COATI_CHECK_ARG(w0, "head_gp: w0 is null");
   COATI_CHECK_ARG(b0, "head_gp: b0 is null");
@@ -49,14 +51,14 @@ int launch_head_gp(const bf16_t* x, long long ldx, long long N, int E, const bf1
   COATI_CHECK_SHAPE(F == 64 || F == 128 || F == 256, "head_gp: F=%d is not 64, 128 or 256", F);
   COATI_CHECK_SHAPE(P >= 1 && P <= HEAD_P_MAX, "head_gp: P=%d outside 1 .. %d", P, HEAD_P_MAX);
   COATI_CHECK_SHAPE(Mp == 32 || Mp == HEAD_GP_M_MAX, "head_gp: Mp=%d is not 32 or %d", Mp, HEAD_GP_M_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_gp: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_gp: ldx=%lld must be a multiple of 8 and >= E=%d", ldx, E);
-  COATI_CHECK_SHAPE(ldm >= P, "head_gp: ldm=%lld < P=%d", ldm, P);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_gp: N=%lld outside 1 .. 2^31 - 1", (long long)N);
+  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_gp: ldx=%lld must be a multiple of 8 and >= E=%d", (long long)ldx, E);
+  COATI_CHECK_SHAPE(ldm >= P, "head_gp: ldm=%lld < P=%d", (long long)ldm, P);
   if (wl) {   // the linear last layer of coati_head_eval, in the same pass
     COATI_CHECK_ARG(bl, "head_gp: wl given with bl null");
     COATI_CHECK_ARG(out, "head_gp: wl given with out null");
     COATI_CHECK_SHAPE(P_lin >= 1 && P_lin <= HEAD_P_MAX, "head_gp: P_lin=%d outside 1 .. %d", P_lin, HEAD_P_MAX);
-    COATI_CHECK_SHAPE(ldo >= P_lin, "head_gp: ldo=%lld < P_lin=%d", ldo, P_lin);
+    COATI_CHECK_SHAPE(ldo >= P_lin, "head_gp: ldo=%lld < P_lin=%d", (long long)ldo, P_lin);
   }
   COATI_CHECK_ARG(gp_aligned16(x) && gp_aligned16(w0) && gp_aligned16(b0) && gp_aligned16(wr) && gp_aligned16(br) && gp_aligned16(wl),
                   "head_gp: x, w0, b0, wr, br and wl must start at 16-byte boundaries");

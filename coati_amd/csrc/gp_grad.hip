@@ -5,8 +5,9 @@
 // the transposed weights.  No activation, mask, k or d ever exists in memory; no atomics, no workspace.
 //
 // LDS is dynamic: the two weight buffers, qs (17 KiB), then D layers of mask words: up to 153 KiB at F = 256, D = 16.  The tile is
-// launch_head_grad's choice: at F = 64 and F = 128 one 32-row panel per wave while that tile's grid still is one round of the device, two
+// coati_head_grad's choice: at F = 64 and F = 128 one 32-row panel per wave while that tile's grid still is one round of the device, two
 // beyond; a panel's instruction sequence does not depend on the tile around it, so the results do not depend on that choice.
+#include "../../include/coati_acq.h"
 #include "head_dev.h"
 
 template <int F, int WAVES, int NP>
@@ -72,11 +73,12 @@ static int head_gp_grad_cus() {
   return cus;
 }
 
-int launch_head_gp_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr,
-                        const float* br, int D, int F, const bf16_t* w0t, const bf16_t* wrt, const bf16_t* z, const bf16_t* zt,
-                        const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
-                        const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, long long ldm,
-                        float* var, float* acq, float* g, long long ldg, hipStream_t s) {
+int coati_head_gp_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr,
+                       const float* br, int D, int F, const uint16_t* w0t, const uint16_t* wrt, const uint16_t* z, const uint16_t* zt,
+                       const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
+                       const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, int64_t ldm,
+                       float* var, float* acq, float* g, int64_t ldg, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x, "head_gp_grad: x is null");
   COATI_CHECK_ARG(w0, "head_gp_grad: w0 is null");
   COATI_CHECK_ARG(b0, "head_gp_grad: b0 is null");
@@ -100,10 +102,10 @@ int launch_head_gp_grad(const bf16_t* x, long long ldx, long long N, int E, cons
   COATI_CHECK_SHAPE(Mp == 32 || Mp == HEAD_GP_M_MAX, "head_gp_grad: Mp=%d is not 32 or %d", Mp, HEAD_GP_M_MAX);
   COATI_CHECK_SHAPE(mode == 0 || mode == 1, "head_gp_grad: mode=%d is not 0 (linear) or 1 (expected improvement)", mode);
   COATI_CHECK_SHAPE(mode == 0 || kappa > 0.f, "head_gp_grad: kappa=%g must be positive with mode=1", (double)kappa);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_gp_grad: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_gp_grad: ldx=%lld must be a multiple of 8 and >= E=%d", ldx, E);
-  COATI_CHECK_SHAPE(ldm >= P, "head_gp_grad: ldm=%lld < P=%d", ldm, P);
-  COATI_CHECK_SHAPE(ldg >= E && ldg % 4 == 0, "head_gp_grad: ldg=%lld must be a multiple of 4 and >= E=%d", ldg, E);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_gp_grad: N=%lld outside 1 .. 2^31 - 1", (long long)N);
+  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_gp_grad: ldx=%lld must be a multiple of 8 and >= E=%d", (long long)ldx, E);
+  COATI_CHECK_SHAPE(ldm >= P, "head_gp_grad: ldm=%lld < P=%d", (long long)ldm, P);
+  COATI_CHECK_SHAPE(ldg >= E && ldg % 4 == 0, "head_gp_grad: ldg=%lld must be a multiple of 4 and >= E=%d", (long long)ldg, E);
   COATI_CHECK_ARG(acq_aligned16(x) && acq_aligned16(w0) && acq_aligned16(b0) && acq_aligned16(wr) && acq_aligned16(br) && acq_aligned16(w0t) &&
                       acq_aligned16(wrt) && acq_aligned16(g),
                   "head_gp_grad: x, w0, b0, wr, br, w0t, wrt and g must start at 16-byte boundaries");
@@ -111,7 +113,7 @@ int launch_head_gp_grad(const bf16_t* x, long long ldx, long long N, int E, cons
                   "head_gp_grad: z, zt, zn, alpha and qs must start at 16-byte boundaries");
   const HeadGpGradArgs a = {x, ldx, N, E, w0, b0, wr, br, D, w0t, wrt, z, zt, zn, alpha, qs, c, inv2l2, s2, P, Mp,
                             wm, kappa, var_add, mode, best, rs, mean, ldm, var, acq, g, ldg};
-  // launch_head_grad's choice: narrow while the narrow tile's grid is one round of the device (F = 64 keeps two of its workgroups per CU)
+  // coati_head_grad's choice: narrow while the narrow tile's grid is one round of the device (F = 64 keeps two of its workgroups per CU)
   const bool narrow = cdiv(N, 128) <= head_gp_grad_cus() * (F == 64 ? 2 : 1);
   if (F == 64)
     return narrow ? head_gp_grad_launch<64, 4, 1>(a, s) : head_gp_grad_launch<64, 4, 2>(a, s);

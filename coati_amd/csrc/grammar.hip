@@ -4,6 +4,7 @@
 //
 // A streaming kernel over the row's V 8-byte entries ([2][V], shared by all rows, cache-resident): the mask does not depend on the
 // logits, so they are not read -- a lane loads four entries with two 16-byte loads and issues at most four predicated dword stores.
+#include "../../include/coati_grammar.h"
 #include "kernels.h"
 
 #define GR_INBR 1
@@ -102,16 +103,17 @@ __global__ __launch_bounds__(256) void grammar_step_kernel(float* __restrict__ l
   }
 }
 
-int launch_grammar_step(float* logits, long long ldl, int B, int V, const unsigned long long* table, const int* state_in, int* state_out,
-                        const long long* tok_prev, const int* parent, int remaining, int stop_token, hipStream_t s) {
+int coati_grammar_step(float* logits, int64_t ldl, int B, int V, const uint64_t* table, const int32_t* state_in, int32_t* state_out,
+                       const int64_t* tok_prev, const int32_t* parent, int remaining, int stop_token, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(logits && table && state_in && state_out, "grammar_step: null operand");
   COATI_CHECK_ARG(parent == nullptr || state_in != state_out, "grammar_step: with parent, state_in and state_out must differ (ping-pong)");
   COATI_CHECK_ARG((reinterpret_cast<unsigned long long>(table) & 7ull) == 0, "grammar_step: the table must start at an 8-byte boundary");
   COATI_CHECK_SHAPE(B >= 1 && V >= 1 && ldl >= V && remaining >= 1 && stop_token >= 0 && stop_token < V,
                     "grammar_step: unsupported shape B=%d V=%d ldl=%lld remaining=%d stop_token=%d (ldl >= V, remaining >= 1, 0 <= stop_token < V)",
-                    B, V, ldl, remaining, stop_token);
-  hipLaunchKernelGGL(grammar_step_kernel, dim3(B), dim3(256), 0, s, logits, ldl, B, V, table, state_in, state_out, tok_prev, parent,
-                     remaining, stop_token);
+                    B, V, (long long)ldl, remaining, stop_token);
+  hipLaunchKernelGGL(grammar_step_kernel, dim3(B), dim3(256), 0, s, logits, ldl, B, V, reinterpret_cast<const unsigned long long*>(table), state_in,
+                     state_out, LL(tok_prev), parent, remaining, stop_token);
   COATI_LAUNCH_CHECK("grammar_step");
   return COATI_OK;
 }

@@ -6,6 +6,7 @@
 // LDS is dynamic (the two weight buffers, then D layers of mask words: up to 136 KiB at F = 256, D = 16).  At F = 64 and F = 128 the
 // launcher picks a narrower tile (one 32-row panel per wave, not two) while that tile's grid still is one round of the device; a 32-row
 // panel's instruction sequence does not depend on the tile around it, so the results do not depend on that choice.
+#include "../../include/coati_guide.h"
 #include "head_dev.h"
 
 template <int F, int WAVES, int NP>
@@ -62,20 +63,21 @@ static int head_grad_cus() {
   return cus;
 }
 
-int launch_head_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
-                     int D, const float* wl, const float* bl, int P, int F, const bf16_t* w0t, const bf16_t* wrt, const float* cot,
-                     long long ldc, float* out, long long ldo, float* g, long long ldg, hipStream_t s) {
+int coati_head_grad(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
+                    int D, const float* wl, const float* bl, int P, int F, const uint16_t* w0t, const uint16_t* wrt, const float* cot,
+                    int64_t ldc, float* out, int64_t ldo, float* g, int64_t ldg, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x && w0 && b0 && wl && bl && w0t && cot && out && g, "head_grad: null operand");
   COATI_CHECK_SHAPE(D >= 0 && D <= HEAD_D_MAX, "head_grad: D=%d outside 0 .. %d", D, HEAD_D_MAX);
   COATI_CHECK_ARG(D == 0 || (wr && br && wrt), "head_grad: null residual weights with D=%d", D);
   COATI_CHECK_SHAPE(E >= 32 && E <= HEAD_E_MAX && E % 32 == 0, "head_grad: E=%d is not a multiple of 32 in 32 .. %d", E, HEAD_E_MAX);
   COATI_CHECK_SHAPE(F == 64 || F == 128 || F == 256, "head_grad: F=%d is not 64, 128 or 256", F);
   COATI_CHECK_SHAPE(P >= 1 && P <= HEAD_P_MAX, "head_grad: P=%d outside 1 .. %d", P, HEAD_P_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_grad: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_grad: ldx=%lld must be a multiple of 8 and >= E=%d", ldx, E);
-  COATI_CHECK_SHAPE(ldo >= P, "head_grad: ldo=%lld < P=%d", ldo, P);
-  COATI_CHECK_SHAPE(ldc >= P, "head_grad: ldc=%lld < P=%d", ldc, P);
-  COATI_CHECK_SHAPE(ldg >= E && ldg % 4 == 0, "head_grad: ldg=%lld must be a multiple of 4 and >= E=%d", ldg, E);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_grad: N=%lld outside 1 .. 2^31 - 1", (long long)N);
+  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_grad: ldx=%lld must be a multiple of 8 and >= E=%d", (long long)ldx, E);
+  COATI_CHECK_SHAPE(ldo >= P, "head_grad: ldo=%lld < P=%d", (long long)ldo, P);
+  COATI_CHECK_SHAPE(ldc >= P, "head_grad: ldc=%lld < P=%d", (long long)ldc, P);
+  COATI_CHECK_SHAPE(ldg >= E && ldg % 4 == 0, "head_grad: ldg=%lld must be a multiple of 4 and >= E=%d", (long long)ldg, E);
   COATI_CHECK_ARG(grad_aligned16(x) && grad_aligned16(w0) && grad_aligned16(b0) && grad_aligned16(wr) && grad_aligned16(br) && grad_aligned16(wl) &&
                       grad_aligned16(w0t) && grad_aligned16(wrt) && grad_aligned16(g),
                   "head_grad: x, w0, b0, wr, br, wl, w0t, wrt and g must start at 16-byte boundaries");

@@ -21,13 +21,14 @@
 // list_off -- a slot no item wrote is never read) become 64-bit keys (score key << 32 | ~row) in LDS, unique over the query since a row
 // lives in one list.  An 8-pass radix select finds the k-th largest key, the <= k survivors are ranked by counting.  Key descending is
 // score descending, original row ascending among equal scores.
+#include "../../include/coati_ivf.h"
 #include "search_host.h"
 
 #define IVF_E_MAX 512
 #define IVF_L_MAX 4096
 #define IVF_NPROBE_MAX 128
 #define IVF_MERGE_MAX 16384    // nprobe * segs * k: the merge's row of 64-bit keys in 128 KiB of LDS
-#define IVF_SEG_MIN 128        // rows of the shortest segment ivf_plan proposes
+#define IVF_SEG_MIN 128        // rows of the shortest segment coati_ivf_plan proposes
 #define IVF_GRID_MAX 2048
 
 template <int KSMAX>
@@ -190,9 +191,10 @@ int ivf_scan_grid(const char* what, long long M, int E, int L, int Q, long long 
   return (int)(blocks > 0 ? (blocks < most ? blocks : most) : (most < IVF_GRID_MAX ? most : IVF_GRID_MAX));
 }
 
-int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q, int Q,
-                    const int* pair_q, const int* pair_off, const int* item_off, long long P, int k, float alpha, int seg_rows, int segs,
-                    float* part_score, int* part_row, int blocks, hipStream_t s) {
+int coati_ivf_scan(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                   const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P, int k,
+                   float alpha, int seg_rows, int segs, float* part_score, int32_t* part_row, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "ivf_scan: lib is null");
   COATI_CHECK_ARG(ids, "ivf_scan: ids is null");
   COATI_CHECK_ARG(list_off, "ivf_scan: list_off is null");
@@ -216,8 +218,10 @@ int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const 
   return COATI_OK;
 }
 
-int launch_ivf_merge(const float* part_score, const int* part_row, const int* probes, const int* pair_slot, long long P, const int* list_off,
-                     int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, long long* out_row, hipStream_t s) {
+int coati_ivf_merge(const float* part_score, const int32_t* part_row, const int32_t* probes, const int32_t* pair_slot, int64_t P,
+                    const int32_t* list_off, int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, int64_t* out_row,
+                    void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(part_score, "ivf_merge: part_score is null");
   COATI_CHECK_ARG(part_row, "ivf_merge: part_row is null");
   COATI_CHECK_ARG(probes, "ivf_merge: probes is null");
@@ -225,22 +229,22 @@ int launch_ivf_merge(const float* part_score, const int* part_row, const int* pr
   COATI_CHECK_ARG(list_off, "ivf_merge: list_off is null");
   COATI_CHECK_ARG(out_score, "ivf_merge: out_score is null");
   COATI_CHECK_ARG(out_row, "ivf_merge: out_row is null");
-  COATI_CHECK_SHAPE(P >= 1 && P < (1ll << 31), "ivf_merge: P=%lld outside 1 .. 2^31 - 1", P);
+  COATI_CHECK_SHAPE(P >= 1 && P < (1ll << 31), "ivf_merge: P=%lld outside 1 .. 2^31 - 1", (long long)P);
   COATI_TRY(ivf_check_common("ivf_merge", L, Q, k, seg_rows, segs));
   COATI_CHECK_SHAPE(nprobe >= 1 && nprobe <= IVF_NPROBE_MAX, "ivf_merge: nprobe=%d outside 1 .. %d", nprobe, IVF_NPROBE_MAX);
   COATI_CHECK_SHAPE((long long)nprobe * segs * k <= IVF_MERGE_MAX, "ivf_merge: nprobe=%d lists of segs=%d segments of k=%d exceed nprobe * segs * k <= %d",
                     nprobe, segs, k, IVF_MERGE_MAX);
   COATI_TRY(max_dynamic_lds<ivf_merge_kernel>("ivf_merge", IVF_MERGE_MAX * (int)sizeof(topk_key_t)));
   hipLaunchKernelGGL(ivf_merge_kernel, dim3(Q), dim3(256), (size_t)nprobe * segs * k * sizeof(topk_key_t), s, part_score, part_row, probes,
-                     pair_slot, P, list_off, L, nprobe, k, seg_rows, segs, out_score, out_row);
+                     pair_slot, P, list_off, L, nprobe, k, seg_rows, segs, out_score, LL(out_row));
   COATI_LAUNCH_CHECK("ivf_merge");
   return COATI_OK;
 }
 
-// The seg_rows launch_ivf_scan is given by default: Q * nprobe pairs (at small Q every pair is a group of its own) times the segments of a
+// The seg_rows coati_ivf_scan is given by default: Q * nprobe pairs (at small Q every pair is a group of its own) times the segments of a
 // list should fill the device; no segment below IVF_SEG_MIN rows; nprobe * segs * k within the merge's row.  Host arithmetic only.
-long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k) {
-  COATI_CHECK_SHAPE(max_list_rows >= 1 && max_list_rows < (1ll << 31), "ivf_plan: max_list_rows=%lld outside 1 .. 2^31 - 1", max_list_rows);
+int64_t coati_ivf_plan(int64_t max_list_rows, int Q, int nprobe, int k) {
+  COATI_CHECK_SHAPE(max_list_rows >= 1 && max_list_rows < (1ll << 31), "ivf_plan: max_list_rows=%lld outside 1 .. 2^31 - 1", (long long)max_list_rows);
   COATI_CHECK_SHAPE(Q >= 1, "ivf_plan: Q=%d < 1", Q);
   COATI_CHECK_SHAPE(nprobe >= 1 && nprobe <= IVF_NPROBE_MAX, "ivf_plan: nprobe=%d outside 1 .. %d", nprobe, IVF_NPROBE_MAX);
   COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX, "ivf_plan: k=%d outside 1 .. %d", k, TOPK_MAX);
@@ -251,7 +255,7 @@ long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k) {
   segs = segs < by_merge ? segs : by_merge;
   long long seg_rows = ((max_list_rows + segs - 1) / segs + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT * TOPK_ROWS_IT;
   seg_rows = seg_rows > IVF_SEG_MIN ? seg_rows : IVF_SEG_MIN;
-  COATI_CHECK_SHAPE(seg_rows < (1ll << 31), "ivf_plan: max_list_rows=%lld in %lld segments: no multiple of %d below 2^31 holds a segment", max_list_rows,
-                    segs, TOPK_ROWS_IT);
+  COATI_CHECK_SHAPE(seg_rows < (1ll << 31), "ivf_plan: max_list_rows=%lld in %lld segments: no multiple of %d below 2^31 holds a segment",
+                    (long long)max_list_rows, segs, TOPK_ROWS_IT);
   return seg_rows;
 }

@@ -1,7 +1,7 @@
 // IVF approximate search over fp8 lists (include/coati_ivf8.h): the library stored list by list as OCP e4m3 bytes (lib8 [M, E] in list
 // order) with one power-of-two f32 scale per position (scale, ids, bias, list_off); a quantised query scores only the rows of the lists it
 // probes.  No score is ever written to memory, no result depends on the launch geometry.  The merge (ivf_merge_kernel of ivf.hip), the
-// plan (ivf_plan) and the exact re-scoring of the candidates (search_rescore_kernel of search8.hip) are used as they are.
+// plan (coati_ivf_plan) and the exact re-scoring of the candidates (search_rescore_kernel of search8.hip) are used as they are.
 //
 // ivf8_scan_kernel<TMAX>, 4 waves, one query panel of 16 pairs: ivf_scan_kernel's item loop (ivf.hip) around search8_topk_kernel's stream
 // (search8.hip).  The probe table arrives inverted: the (query, list) pairs sorted by (list, query).  A work item is (list l, group of <= 16
@@ -35,6 +35,7 @@
 // and stored = false.  The barrier after the write-out puts the next item's reset of the counts behind this item's reads of them.
 #include <type_traits>
 
+#include "../../include/coati_ivf8.h"
 #include "topk_stream_dev.h"
 
 // Positions [r_begin, r_end) of lib [M, E] e4m3 (both bounds workgroup-uniform; an empty range leaves empty lists) against the byte
@@ -198,9 +199,11 @@ __global__ __launch_bounds__(256) void ivf8_scan_kernel(const unsigned char* __r
   }
 }
 
-int launch_ivf8_scan(const unsigned char* lib, const float* scale, const int* ids, const float* bias, const int* list_off, long long M, int E,
-                     int L, const unsigned char* q, const float* qscale, int Q, const int* pair_q, const int* pair_off, const int* item_off,
-                     long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks, hipStream_t s) {
+int coati_ivf8_scan(const uint8_t* lib, const float* scale, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E,
+                    int L, const uint8_t* q, const float* qscale, int Q, const int32_t* pair_q, const int32_t* pair_off,
+                    const int32_t* item_off, int64_t P, int k, float alpha, int seg_rows, int segs, float* part_score, int32_t* part_row,
+                    int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "ivf8_scan: lib8 is null");
   COATI_CHECK_ARG(scale, "ivf8_scan: scale is null");
   COATI_CHECK_ARG(ids, "ivf8_scan: ids is null");

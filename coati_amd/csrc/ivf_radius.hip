@@ -36,6 +36,7 @@
 #include <climits>
 #include <type_traits>
 
+#include "../../include/coati_ivf_radius.h"
 #include "topk_stream_dev.h"
 
 __device__ __forceinline__ int ivf_radius_bytesum(unsigned x) { return (int)((x * 0x01010101u) >> 24); }   // (of four bytes that sum to < 256)
@@ -215,9 +216,11 @@ static int ivf_radius_launch(const char* what, int grid, const bf16_t* lib, cons
   return COATI_OK;
 }
 
-int launch_ivf_radius_count(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q,
-                            int Q, const int* pair_q, const int* pair_off, const int* item_off, long long P, float alpha, const float* sub,
-                            int clamp0, const float* thr, const int* row_hi, int seg_rows, int segs, int* counts, int blocks, hipStream_t s) {
+int coati_ivf_radius_count(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                           const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P,
+                           float alpha, const float* sub, int clamp0, const float* thr, const int32_t* row_hi, int seg_rows, int segs,
+                           int32_t* counts, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "ivf_radius_count: lib is null");
   COATI_CHECK_ARG(ids, "ivf_radius_count: ids is null");
   COATI_CHECK_ARG(list_off, "ivf_radius_count: list_off is null");
@@ -236,10 +239,11 @@ int launch_ivf_radius_count(const bf16_t* lib, const int* ids, const float* bias
                                       clamp0, thr, row_hi, seg_rows, segs, counts, nullptr, nullptr, nullptr, s);
 }
 
-int launch_ivf_radius_fill(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q,
-                           int Q, const int* pair_q, const int* pair_off, const int* item_off, long long P, float alpha, const float* sub,
-                           int clamp0, const float* thr, const int* row_hi, int seg_rows, int segs, const int* counts, const long long* offsets,
-                           float* out_score, long long* out_row, int blocks, hipStream_t s) {
+int coati_ivf_radius_fill(const uint16_t* lib, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                          const uint16_t* q, int Q, const int32_t* pair_q, const int32_t* pair_off, const int32_t* item_off, int64_t P,
+                          float alpha, const float* sub, int clamp0, const float* thr, const int32_t* row_hi, int seg_rows, int segs,
+                          const int32_t* counts, const int64_t* offsets, float* out_score, int64_t* out_row, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "ivf_radius_fill: lib is null");
   COATI_CHECK_ARG(ids, "ivf_radius_fill: ids is null");
   COATI_CHECK_ARG(list_off, "ivf_radius_fill: list_off is null");
@@ -256,7 +260,7 @@ int launch_ivf_radius_fill(const bf16_t* lib, const int* ids, const float* bias,
   if (grid < 0) return grid;
   if (E <= 256)
     return ivf_radius_launch<8, true>("ivf_radius_fill", grid, lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, alpha, sub,
-                                      clamp0, thr, row_hi, seg_rows, segs, counts, offsets, out_score, out_row, s);
+                                      clamp0, thr, row_hi, seg_rows, segs, counts, LL(offsets), out_score, LL(out_row), s);
   return ivf_radius_launch<16, true>("ivf_radius_fill", grid, lib, ids, bias, list_off, M, E, L, q, Q, pair_q, pair_off, item_off, P, alpha, sub,
-                                     clamp0, thr, row_hi, seg_rows, segs, counts, offsets, out_score, out_row, s);
+                                     clamp0, thr, row_hi, seg_rows, segs, counts, LL(offsets), out_score, LL(out_row), s);
 }

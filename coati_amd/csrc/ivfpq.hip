@@ -2,7 +2,7 @@
 // its list's centre -- codes [M, E / 8] in list order under ONE set of code books [E / 8][256][8] bf16 shared by all lists, the bf16 centres
 // [L, E] the coarse step already uses.  The row a position stands for is x_hat[p] = centre[l] + entry(codes[p]); a query scores only the
 // positions of the lists it probes.  No score is ever written to memory, no result depends on the launch geometry.  The merge
-// (ivf_merge_kernel of ivf.hip), the plan (ivf_plan) and the exact re-scoring (search_rescore_kernel of search8.hip) are used as they are.
+// (ivf_merge_kernel of ivf.hip), the plan (coati_ivf_plan) and the exact re-scoring (search_rescore_kernel of search8.hip) are used as they are.
 //
 // ivfpq_scan_kernel<KSMAX>, 4 waves, one query panel of 16 pairs: ivf_scan_kernel's item loop (ivf.hip) around pq_stream (pq_stream_dev.h)
 // with its START switch.  The probe table arrives inverted: the (query, list) pairs sorted by (list, query).  A work item is (list l, group
@@ -30,6 +30,7 @@
 // all threads or none; inside pq_stream the trip count is the segment's r_begin and r_end and whether to compact is read by all threads
 // from one LDS word behind a barrier.  A column without a query only has a zero fragment and stored = false.  The barrier after the
 // write-out puts the next item's reset of the counts behind this item's reads of them.
+#include "../../include/coati_ivfpq.h"
 #include "pq_stream_dev.h"
 #include "search_host.h"
 
@@ -101,7 +102,7 @@ static int ivfpq_check_E(const char* what, int E) {
 
 // The largest k of the scan at this E: 128 where the code book, the lists of 16 pairs at cap = k + 2 TOPK_ROWS_IT and the words fit the
 // CU's 160 KiB, else 64 (E = 256: 128 KiB + 24 KiB + 136 B); a negative code for an E outside the limits
-int ivfpq_k_max(int E) {
+int coati_ivfpq_k_max(int E) {
   COATI_TRY(ivfpq_check_E("ivfpq_k_max", E));
   for (int k = TOPK_MAX; k >= 64; k /= 2)
     if (ivfpq_lds(E, k) <= IVFPQ_LDS_BYTES) return k;
@@ -115,7 +116,7 @@ static int ivfpq_launch(const unsigned char* codes, const int* ids, const float*
                         const int* item_off, long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int grid,
                         hipStream_t s) {
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
-  const size_t lds = ivfpq_lds(E, k);     // <= IVFPQ_LDS_BYTES: k <= ivfpq_k_max(E)
+  const size_t lds = ivfpq_lds(E, k);     // <= IVFPQ_LDS_BYTES: k <= coati_ivfpq_k_max(E)
   COATI_TRY(max_dynamic_lds<ivfpq_scan_kernel<KSMAX>>("ivfpq_scan", IVFPQ_LDS_BYTES));
   hipLaunchKernelGGL((ivfpq_scan_kernel<KSMAX>), dim3(grid), dim3(256), lds, s, codes, ids, bias, list_off, M, E, L, centres, codebook, q, Q, pair_q,
                      pair_off, item_off, P, k, alpha, seg_rows, segs, cap, part_score, part_row);
@@ -123,10 +124,11 @@ static int ivfpq_launch(const unsigned char* codes, const int* ids, const float*
   return COATI_OK;
 }
 
-int launch_ivfpq_scan(const unsigned char* codes, const int* ids, const float* bias, const int* list_off, long long M, int E, int L,
-                      const bf16_t* centres, const bf16_t* codebook, const bf16_t* q, int Q, const int* pair_q, const int* pair_off,
-                      const int* item_off, long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks,
-                      hipStream_t s) {
+int coati_ivfpq_scan(const uint8_t* codes, const int32_t* ids, const float* bias, const int32_t* list_off, int64_t M, int E, int L,
+                     const uint16_t* centres, const uint16_t* codebook, const uint16_t* q, int Q, const int32_t* pair_q,
+                     const int32_t* pair_off, const int32_t* item_off, int64_t P, int k, float alpha, int seg_rows, int segs,
+                     float* part_score, int32_t* part_row, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(codes, "ivfpq_scan: codes is null");
   COATI_CHECK_ARG(ids, "ivfpq_scan: ids is null");
   COATI_CHECK_ARG(bias, "ivfpq_scan: bias is null");
@@ -142,7 +144,7 @@ int launch_ivfpq_scan(const unsigned char* codes, const int* ids, const float* b
   COATI_TRY(ivfpq_check_E("ivfpq_scan", E));
   int grid = ivf_scan_grid("ivfpq_scan", M, E, L, Q, P, k, seg_rows, segs, blocks);   // coati_ivf_scan's limits and grid
   if (grid < 0) return grid;
-  COATI_CHECK_SHAPE(k <= ivfpq_k_max(E), "ivfpq_scan: k=%d outside 1 .. %d at E=%d", k, ivfpq_k_max(E), E);
+  COATI_CHECK_SHAPE(k <= coati_ivfpq_k_max(E), "ivfpq_scan: k=%d outside 1 .. %d at E=%d", k, coati_ivfpq_k_max(E), E);
   if (blocks == 0 && grid > IVFPQ_GRID_MAX) grid = IVFPQ_GRID_MAX;
   if (E <= 128)
     return ivfpq_launch<4>(codes, ids, bias, list_off, M, E, L, centres, codebook, q, Q, pair_q, pair_off, item_off, P, k, alpha, seg_rows, segs,

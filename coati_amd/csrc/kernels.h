@@ -357,131 +357,18 @@ int launch_kv_cache_fill_rows(const bf16_t* qkv, bf16_t* cache, const int* row_s
 int launch_gather_last_rows(const float* x, const int* off, float* out, int B, int C, int R, hipStream_t s);
 // prompt prefill: the rotated k and the v of a padded [B, m] pass's qkv into one layer's cache [B][nh][Tmax][k|v], positions 0..m-1
 int launch_kv_cache_fill(const bf16_t* qkv, bf16_t* cache, int B, int m, int n_head, int head_size, int Tmax, hipStream_t s);
+// The entries of a feature header (include/coati_<x>.h) are defined by their unit itself, which includes that header: only what one unit
+// calls of another is declared here.
 // beam search (beam.hip, include/coati_beam.h)
 // launch_attn_decode with the records of t < pos read from cache row anc[b * Tmax + t] (int32 [B, Tmax], device)
 int launch_attn_decode_anc(const bf16_t* qkv, bf16_t* cache, bf16_t* y, int B, int n_head, int head_size, int Tmax, int pos,
                            const int* anc, hipStream_t s);
-// per row of [G * W, V] logits: its W best continuations (cum[b] + log_softmax, token), best first; 1 <= W <= 16
-int launch_beam_row_topk(const float* logits, long long ldl, int G, int W, int V, const float* cum, const int* fin, int pad_token,
-                         float* cand_score, int* cand_tok, hipStream_t s);
-// per group: the best W of its W * W candidates become its new rows (score, flags, lengths, ancestry and token history rows)
-int launch_beam_merge(const float* cand_score, const int* cand_tok, int G, int W, const float* cum_in, const int* fin_in, const int* len_in,
-                      const int* anc_in, const long long* hist_in, long long ldh, int Tmax, int pos, int n, int stop_token, float* cum_out,
-                      int* fin_out, int* len_out, int* anc_out, long long* hist_out, long long* tok_next, int* nfin, hipStream_t s);
-// embedding-library search (search.hip, include/coati_search.h): per query the k best rows of lib [N, E] bf16 by alpha * dot + bias,
-// score descending, row ascending; part_* are [Q, S, k] scratch
-int launch_search_topk(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, int k, float alpha, int S,
-                       float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s);
-int search_slices(long long N, int Q, int k);   // host only: the default S
-// syntax-constrained decoding (grammar.hip, include/coati_grammar.h): state_out[b] = state_in[parent ? parent[b] : b] advanced by
-// tok_prev[b], then -inf over the entries of logits row b that may not follow; table [2][V] of 8-byte entries, states int32 [B, 4]
-int launch_grammar_step(float* logits, long long ldl, int B, int V, const unsigned long long* table, const int* state_in, int* state_out,
-                        const long long* tok_prev, const int* parent, int remaining, int stop_token, hipStream_t s);
-// property heads (screen.hip, include/coati_screen.h): out [N, P] = the FC-ResNet head (w0, b0 | wr, br x D | wl, bl) on the bf16 rows x [N, E]
-int launch_head_eval(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
-                     int D, const float* wl, const float* bl, int P, int F, float* out, long long ldo, hipStream_t s);
-// the head's input gradient (guide.hip, include/coati_guide.h): out as launch_head_eval writes it, g [N, E] = d (cot . out) / dx; w0t [E, F] and
-// wrt [D, F, F] are w0 and wr[l] transposed
-int launch_head_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
-                     int D, const float* wl, const float* bl, int P, int F, const bf16_t* w0t, const bf16_t* wrt, const float* cot,
-                     long long ldc, float* out, long long ldo, float* g, long long ldg, hipStream_t s);
-// the GP head (gp.hip, include/coati_gp.h): launch_head_eval's forward (out only if wl is given), then mean [N, P] and var [N] of an RBF GP
-// on Mp inducing points z over the rounded last stream
-int launch_head_gp(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
-                   int D, int F, const float* wl, const float* bl, int P_lin, float* out, long long ldo, const bf16_t* z, const float* zn,
-                   const float* alpha, const float* q, const float* c, float inv2l2, float s2, int P, int Mp, float* mean, long long ldm,
-                   float* var, hipStream_t s);
-// the gradient of a GP acquisition with respect to the input rows (gp_grad.hip, include/coati_acq.h): launch_head_gp's mean and var, acq [N]
-// = a(wm . mean, var) and g [N, E] = rs * d acq / dx; qs is the symmetric part of q, zt [F, Mp] is z transposed
-int launch_head_gp_grad(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr,
-                        const float* br, int D, int F, const bf16_t* w0t, const bf16_t* wrt, const bf16_t* z, const bf16_t* zt,
-                        const float* zn, const float* alpha, const float* qs, const float* c, float inv2l2, float s2, int P, int Mp,
-                        const float* wm, float kappa, float var_add, int mode, float best, const float* rs, float* mean, long long ldm,
-                        float* var, float* acq, float* g, long long ldg, hipStream_t s);
-// library clustering (cluster.hip, include/coati_cluster.h): assign[n] = the centre of c [K, E] with the largest dot + cbias (lowest k among
-// equal scores; -1 where row_bias is -inf), best[n] = that score; sums [K, E] = the per-cluster sums of the rows listed in order / offsets,
-// through part [items_max, E] in chunks of cluster_chunk() rows.  blocks = 0: the default grid; no result depends on it
-int launch_cluster_assign(const bf16_t* lib, long long N, int E, const float* row_bias, const bf16_t* c, int K, const float* cbias, int* assign,
-                          float* best, int blocks, hipStream_t s);
-int launch_cluster_sums(const bf16_t* lib, long long N, int E, const int* order, long long M, const int* offsets, const int* item_off, int K,
-                        float* part, long long items_max, float* sums, int blocks, hipStream_t s);
-int cluster_chunk(void);                           // host only
-long long cluster_items_max(long long M, int K);   // host only
-// IVF approximate search (ivf.hip, include/coati_ivf.h): the scan of every (query, list) pair's rows -- lib [M, E] in list order, the pairs
-// sorted by (list, query), work items from item_off -- into part_* [P, segs, k], and the merge of a query's partial lists through pair_slot.
-// blocks = 0: the default grid; no result depends on it, nor on seg_rows
-int launch_ivf_scan(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q, int Q,
-                    const int* pair_q, const int* pair_off, const int* item_off, long long P, int k, float alpha, int seg_rows, int segs,
-                    float* part_score, int* part_row, int blocks, hipStream_t s);
-int launch_ivf_merge(const float* part_score, const int* part_row, const int* probes, const int* pair_slot, long long P, const int* list_off,
-                     int L, int Q, int nprobe, int k, int seg_rows, int segs, float* out_score, long long* out_row, hipStream_t s);
-long long ivf_plan(long long max_list_rows, int Q, int nprobe, int k);   // host only: the default seg_rows
-// host only: the scan's limits checked under the name `what`, then its grid (>= 1), or a negative code
-int ivf_scan_grid(const char* what, long long M, int E, int L, int Q, long long P, int k, int seg_rows, int segs, int blocks);
-// the same scan over fp8 lists (ivf8.hip, include/coati_ivf8.h): lib [M, E] e4m3 bytes with scale [M], queries q [Q, E] e4m3 with qscale [Q],
-// bias required; launch_search8_topk's score, launch_ivf_scan's tables, partial lists and limits
-int launch_ivf8_scan(const unsigned char* lib, const float* scale, const int* ids, const float* bias, const int* list_off, long long M, int E,
-                     int L, const unsigned char* q, const float* qscale, int Q, const int* pair_q, const int* pair_off, const int* item_off,
-                     long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks, hipStream_t s);
-// radius search (radius.hip, include/coati_radius.h): counts [Q, S] = the rows of every slice with alpha * dot + bias > -inf, that value - sub[q]
-// (min 0 with clamp0) >= thr[q] and row < row_hi[q]; the fill writes them at offsets (the caller's exclusive prefix sum of counts), row ascending
-int launch_radius_count(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,
-                        int clamp0, const float* thr, const int* row_hi, int S, int* counts, hipStream_t s);
-int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,
-                       int clamp0, const float* thr, const int* row_hi, int S, const int* counts, const long long* offsets, float* out_score,
-                       long long* out_row, hipStream_t s);
-int radius_slices(long long N, int Q);   // host only: the default S
-// radius search over inverted lists (ivf_radius.hip, include/coati_ivf_radius.h): launch_ivf_scan's operands, pairs and work items with
-// launch_radius_*'s filter; counts [P, segs] (zero-filled by the caller) per (pair, segment), the fill writes ids[position] and the value
-// at offsets [P, segs], position ascending.  blocks = 0: the default grid; no result depends on it, nor on seg_rows
-int launch_ivf_radius_count(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q,
-                            int Q, const int* pair_q, const int* pair_off, const int* item_off, long long P, float alpha, const float* sub,
-                            int clamp0, const float* thr, const int* row_hi, int seg_rows, int segs, int* counts, int blocks, hipStream_t s);
-int launch_ivf_radius_fill(const bf16_t* lib, const int* ids, const float* bias, const int* list_off, long long M, int E, int L, const bf16_t* q,
-                           int Q, const int* pair_q, const int* pair_off, const int* item_off, long long P, float alpha, const float* sub,
-                           int clamp0, const float* thr, const int* row_hi, int seg_rows, int segs, const int* counts, const long long* offsets,
-                           float* out_score, long long* out_row, int blocks, hipStream_t s);
-// quantised search (search8.hip, include/coati_search8.h): rows as e4m3 bytes + one power-of-two scale, the streaming stage over them
-// (partial lists as launch_search_topk's, merged by launch_search_merge of search.hip), and the candidates' exact scores from the bf16 rows
+// search.hip: the merge of the partial lists part_* [Q, V] that a streaming top-k stage leaves (coati_search_topk's, and those of search8.hip,
+// search4.hip and pq.hip, which write the same lists) into out_* [Q, k]
 int launch_search_merge(const float* part_score, const int* part_row, int Q, int V, int k, float* out_score, long long* out_row, hipStream_t s);
-int launch_quant_rows_fp8(const bf16_t* x, long long n, int E, unsigned char* out, float* scale, hipStream_t s);
-int launch_search8_topk(const unsigned char* lib, const float* scale, long long N, int E, const float* bias, const unsigned char* q,
-                        const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
-                        long long* out_row, hipStream_t s);
-int launch_search_rescore(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, const long long* cand, int R, int k,
-                          float alpha, float* out_score, long long* out_row, hipStream_t s);
-int search8_slices(long long N, int Q, int k);   // host only: the default S
-// product-quantised search (pq.hip, include/coati_pq.h): rows as E / 8 code bytes under codebook [E / 8][256][8] bf16; the encoder, and
-// the streaming stage over the codes with the code book in LDS (launch_search_topk's partial lists, merged by launch_search_merge)
-int launch_pq_encode(const bf16_t* x, long long n, int E, const bf16_t* codebook, unsigned char* codes, hipStream_t s);
-int launch_pq_topk(const unsigned char* codes, long long N, int E, const bf16_t* codebook, const float* bias, const bf16_t* q, int Q, int k,
-                   float alpha, int S, float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s);
-int pq_k_max(int E);                                   // host only: the largest k at this E
-int pq_slices(long long N, int E, int Q, int k);       // host only: the default S
-// IVF-PQ search (ivfpq.hip, include/coati_ivfpq.h): launch_ivf_scan's tables, partial lists and limits over positions stored as codes
-// of the residual against centres [L, E] under one codebook; the score is launch_ivf_scan's at width 2 E on [centre | entry] and [q | q]
-int launch_ivfpq_scan(const unsigned char* codes, const int* ids, const float* bias, const int* list_off, long long M, int E, int L,
-                      const bf16_t* centres, const bf16_t* codebook, const bf16_t* q, int Q, const int* pair_q, const int* pair_off,
-                      const int* item_off, long long P, int k, float alpha, int seg_rows, int segs, float* part_score, int* part_row, int blocks,
-                      hipStream_t s);
-int ivfpq_k_max(int E);                                // host only: the largest k at this E
-// four-bit search (search4.hip, include/coati_search4.h): rows as e2m1 nibbles [N, E4 / 2] + E8M0 block scales [N, E4 / 32]; the
-// quantiser, and the streaming stage over them (launch_search_topk's partial lists, merged by launch_search_merge)
-int launch_quant_rows_fp4(const bf16_t* x, long long n, int E, unsigned char* codes, unsigned char* scales, hipStream_t s);
-int launch_search4_topk(const unsigned char* codes, const unsigned char* scales, long long N, int E4, const float* bias, const unsigned char* q,
-                        const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
-                        long long* out_row, hipStream_t s);
-int search4_slices(long long N, int Q, int k);   // host only: the default S
-// embedding maps (tsne.hip, include/coati_tsne.h): the conditional probabilities over a kNN graph by a fixed-length bisection; the all-pairs
-// repulsive sums in chunks of tsne_chunk() points (through part [chunks][3][N] when given and the tiles are few; no result depends on it or
-// on blocks); one iteration's attraction over the CSR joint P, gradient and gains / momentum update
-int launch_tsne_affinities(const float* d2, const int* nbr, long long N, int k, float perplexity, int steps, float* p, float* beta, hipStream_t s);
-int launch_tsne_repulsion(const float* y, long long N, float* rep, float* z, float* part, long long part_floats, int blocks, hipStream_t s);
-int launch_tsne_step(const float* y, const float* rep, const float* zsum, const long long* offsets, const int* cols, const float* vals, long long N,
-                     float exaggeration, float momentum, float lr, float min_gain, float* update, float* gains, float* y_out, float* kl_rows,
-                     float* att, hipStream_t s);
-int tsne_chunk(void);                        // host only
-long long tsne_part_floats(long long N);     // host only
+// ivf.hip, host only: the limits of coati_ivf_scan checked under the name `what`, then its grid (>= 1), or a negative code; shared by the
+// scans of ivf8.hip, ivf_radius.hip and ivfpq.hip
+int ivf_scan_grid(const char* what, long long M, int E, int L, int Q, long long P, int k, int seg_rows, int segs, int blocks);
 // the owner of work item `item` in a table item_off [n + 1] of prefix sums (cluster.hip's clusters, ivf.hip's lists): the last i < n with
 // item_off[i] <= item (owners without items share their successor's entry), by bisection
 __device__ __forceinline__ int item_owner(const int* __restrict__ item_off, int n, long long item) {

@@ -14,6 +14,7 @@
 // (pq_stream_dev.h: topk_stream with the operand read from the code book) over its slice.  LDS, all of it dynamic: the code book
 // (512 E bytes), the lists [16 NP][cap] of 8-byte keys, then counts, thresholds and the two flags (PQ_WORDS_BYTES).  NP = 2 up to
 // E = 128 (a fragment read from LDS then feeds two MFMAs), NP = 1 above, where the code book leaves room for 16 lists only.
+#include "../../include/coati_pq.h"
 #include "pq_stream_dev.h"
 #include "search_host.h"
 
@@ -75,10 +76,11 @@ static int pq_check_E(const char* what, int E) {
   return COATI_OK;
 }
 
-int launch_pq_encode(const bf16_t* x, long long n, int E, const bf16_t* codebook, unsigned char* codes, hipStream_t s) {
+int coati_pq_encode(const uint16_t* x, int64_t n, int E, const uint16_t* codebook, uint8_t* codes, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x && codebook && codes, "pq_encode: null operand");
   COATI_TRY(pq_check_E("pq_encode", E));
-  COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "pq_encode: n=%lld outside 1 .. 2^31 - 1", n);
+  COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "pq_encode: n=%lld outside 1 .. 2^31 - 1", (long long)n);
   COATI_TRY(max_dynamic_lds<pq_encode_kernel>("pq_encode", 512 * PQ_E_MAX));
   const long long blocks = (n + PQ_ENCODE_ROWS - 1) / PQ_ENCODE_ROWS;
   hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), (size_t)512 * E, s, x, n, E, codebook, codes);
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(256) void pq_topk_kernel(const unsigned char* __res
 
 // The largest k of the scan at this E: 128 where the code book, the lists of 16 NP queries at cap = k + 2 TOPK_ROWS_IT and the words fit
 // the CU's 160 KiB, else 64 (E = 256: 128 KiB + 24 KiB + 136 B); a negative code for an E outside the limits
-int pq_k_max(int E) {
+int coati_pq_k_max(int E) {
   COATI_TRY(pq_check_E("pq_k_max", E));
   for (int k = TOPK_MAX; k >= 64; k /= 2)
     if (pq_lds(E, k) <= PQ_LDS_BYTES) return k;
@@ -137,7 +139,7 @@ int pq_k_max(int E) {
 
 static int pq_check(const char* what, long long N, int E, int Q, int k) {
   COATI_TRY(pq_check_E(what, E));
-  COATI_CHECK_SHAPE(k >= 1 && k <= pq_k_max(E), "%s: k=%d outside 1 .. %d at E=%d", what, k, pq_k_max(E), E);
+  COATI_CHECK_SHAPE(k >= 1 && k <= coati_pq_k_max(E), "%s: k=%d outside 1 .. %d at E=%d", what, k, coati_pq_k_max(E), E);
   COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "%s: N=%lld outside 1 .. 2^31 - 1", what, N);
   COATI_CHECK_SHAPE(Q >= 1, "%s: Q=%d < 1", what, Q);
   return COATI_OK;
@@ -147,7 +149,7 @@ template <int KSMAX, int NP>
 static int pq_launch(const unsigned char* codes, long long N, int E, const bf16_t* codebook, const float* bias, const bf16_t* q, int Q, int k,
                      float alpha, int S, float* part_score, int* part_row, hipStream_t s) {
   const int cap = k + 2 * TOPK_ROWS_IT;   // <= 256 = 4 candidates per lane of a compacting wave
-  const size_t lds = pq_lds(E, k);        // <= PQ_LDS_BYTES: k <= pq_k_max(E)
+  const size_t lds = pq_lds(E, k);        // <= PQ_LDS_BYTES: k <= coati_pq_k_max(E)
   COATI_TRY((max_dynamic_lds<pq_topk_kernel<KSMAX, NP>>("pq_topk", PQ_LDS_BYTES)));
   hipLaunchKernelGGL((pq_topk_kernel<KSMAX, NP>), dim3(cdiv(Q, 16 * NP), S), dim3(256), lds, s, codes, N, E, codebook, bias, q, Q, k, alpha, S,
                      topk_slice_rows(N, S), cap, part_score, part_row);
@@ -155,8 +157,9 @@ static int pq_launch(const unsigned char* codes, long long N, int E, const bf16_
   return COATI_OK;
 }
 
-int launch_pq_topk(const unsigned char* codes, long long N, int E, const bf16_t* codebook, const float* bias, const bf16_t* q, int Q, int k,
-                   float alpha, int S, float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s) {
+int coati_pq_topk(const uint8_t* codes, int64_t N, int E, const uint16_t* codebook, const float* bias, const uint16_t* q, int Q, int k,
+                  float alpha, int S, float* part_score, int32_t* part_row, float* out_score, int64_t* out_row, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(codes && codebook && q && part_score && part_row && out_score && out_row, "pq_topk: null operand");
   COATI_TRY(pq_check("pq_topk", N, E, Q, k));
   COATI_CHECK_SHAPE(S >= 1 && (long long)S * k <= TOPK_MERGE_MAX, "pq_topk: S=%d slices of k=%d exceed S * k <= %d", S, k, TOPK_MERGE_MAX);
@@ -164,12 +167,12 @@ int launch_pq_topk(const unsigned char* codes, long long N, int E, const bf16_t*
     COATI_TRY((pq_launch<4, 2>(codes, N, E, codebook, bias, q, Q, k, alpha, S, part_score, part_row, s)));
   else
     COATI_TRY((pq_launch<8, 1>(codes, N, E, codebook, bias, q, Q, k, alpha, S, part_score, part_row, s)));
-  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, out_row, s);
+  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, LL(out_row), s);
 }
 
-// The number of slices launch_pq_topk is given by default: enough workgroups to fill the device at this Q (as many per CU as their LDS
+// The number of slices coati_pq_topk is given by default: enough workgroups to fill the device at this Q (as many per CU as their LDS
 // allows), no slice shorter than PQ_SLICE_ROWS_MIN rows unless the library is, S * k within the merge's row.  Host arithmetic only.
-int pq_slices(long long N, int E, int Q, int k) {
+int coati_pq_slices(int64_t N, int E, int Q, int k) {
   COATI_TRY(pq_check("pq_slices", N, E, Q, k));
   const long long tiles = ((long long)Q + 16 * pq_np(E) - 1) / (16 * pq_np(E));
   const long long slots = 256 * (long long)(PQ_LDS_BYTES / pq_lds(E, k));

@@ -27,6 +27,7 @@
 #include <climits>
 #include <type_traits>
 
+#include "../../include/coati_radius.h"
 #include "search_host.h"
 
 #define RADIUS_E_MAX 512
@@ -231,8 +232,9 @@ static int radius_launch(const char* what, const bf16_t* lib, long long N, int E
   return COATI_OK;
 }
 
-int launch_radius_count(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,
-                        int clamp0, const float* thr, const int* row_hi, int S, int* counts, hipStream_t s) {
+int coati_radius_count(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
+                       int clamp0, const float* thr, const int32_t* row_hi, int S, int32_t* counts, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "radius_count: lib is null");
   COATI_CHECK_ARG(q, "radius_count: q is null");
   COATI_CHECK_ARG(thr, "radius_count: thr is null");
@@ -243,9 +245,10 @@ int launch_radius_count(const bf16_t* lib, long long N, int E, const float* bias
   return radius_launch<16, 2, false>("radius_count", lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, nullptr, nullptr, nullptr, s);
 }
 
-int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, float alpha, const float* sub,
-                       int clamp0, const float* thr, const int* row_hi, int S, const int* counts, const long long* offsets, float* out_score,
-                       long long* out_row, hipStream_t s) {
+int coati_radius_fill(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, float alpha, const float* sub,
+                      int clamp0, const float* thr, const int32_t* row_hi, int S, const int32_t* counts, const int64_t* offsets,
+                      float* out_score, int64_t* out_row, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib, "radius_fill: lib is null");
   COATI_CHECK_ARG(q, "radius_fill: q is null");
   COATI_CHECK_ARG(thr, "radius_fill: thr is null");
@@ -255,14 +258,16 @@ int launch_radius_fill(const bf16_t* lib, long long N, int E, const float* bias,
   COATI_CHECK_ARG(out_row, "radius_fill: out_row is null");
   COATI_TRY(radius_check("radius_fill", N, E, Q, S));
   if (E <= 256)
-    return radius_launch<8, 4, true>("radius_fill", lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, offsets, out_score, out_row, s);
-  return radius_launch<16, 2, true>("radius_fill", lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, offsets, out_score, out_row, s);
+    return radius_launch<8, 4, true>("radius_fill", lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, LL(offsets), out_score,
+                                     LL(out_row), s);
+  return radius_launch<16, 2, true>("radius_fill", lib, N, E, bias, q, Q, alpha, sub, clamp0, thr, row_hi, S, counts, LL(offsets), out_score,
+                                    LL(out_row), s);
 }
 
 // The number of slices the two passes are given by default: enough workgroups to fill the device at this Q (tiles of 64 queries), no
 // slice shorter than one workgroup iteration, within the grid's y limit.  There is no merge, so no merge bound.  Host arithmetic only.
-int radius_slices(long long N, int Q) {
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31) && Q >= 1, "radius_slices: N=%lld Q=%d out of range", N, Q);
+int coati_radius_slices(int64_t N, int Q) {
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31) && Q >= 1, "radius_slices: N=%lld Q=%d out of range", (long long)N, Q);
   const long long tiles = ((long long)Q + 63) / 64, by_rows = (N + TOPK_ROWS_IT - 1) / TOPK_ROWS_IT;
   long long S = (TOPK_DEVICE_SLOTS + tiles - 1) / tiles;
   S = S < by_rows ? S : by_rows;

@@ -4,6 +4,7 @@
 // head_eval_kernel<F, WAVES, NP> is head_body<F, WAVES, NP, HEAD_MODE_EVAL> of head_dev.h, where the layout is described: the body is shared with the
 // input-gradient kernel (guide.hip), which runs the same forward, instruction for instruction, before its backward.
 // No atomics, no workspace.
+#include "../../include/coati_screen.h"
 #include "head_dev.h"
 
 template <int F, int WAVES, int NP>
@@ -25,17 +26,18 @@ static void head_launch(const bf16_t* x, long long ldx, long long N, int E, cons
 
 static bool head_aligned16(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; }
 
-int launch_head_eval(const bf16_t* x, long long ldx, long long N, int E, const bf16_t* w0, const float* b0, const bf16_t* wr, const float* br,
-                     int D, const float* wl, const float* bl, int P, int F, float* out, long long ldo, hipStream_t s) {
+int coati_head_eval(const uint16_t* x, int64_t ldx, int64_t N, int E, const uint16_t* w0, const float* b0, const uint16_t* wr, const float* br,
+                    int D, const float* wl, const float* bl, int P, int F, float* out, int64_t ldo, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x && w0 && b0 && wl && bl && out, "head_eval: null operand");
   COATI_CHECK_SHAPE(D >= 0 && D <= HEAD_D_MAX, "head_eval: D=%d outside 0 .. %d", D, HEAD_D_MAX);
   COATI_CHECK_ARG(D == 0 || (wr && br), "head_eval: null residual weights with D=%d", D);
   COATI_CHECK_SHAPE(E >= 32 && E <= HEAD_E_MAX && E % 32 == 0, "head_eval: E=%d is not a multiple of 32 in 32 .. %d", E, HEAD_E_MAX);
   COATI_CHECK_SHAPE(F == 64 || F == 128 || F == 256, "head_eval: F=%d is not 64, 128 or 256", F);
   COATI_CHECK_SHAPE(P >= 1 && P <= HEAD_P_MAX, "head_eval: P=%d outside 1 .. %d", P, HEAD_P_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_eval: N=%lld outside 1 .. 2^31 - 1", N);
-  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_eval: ldx=%lld must be a multiple of 8 and >= E=%d", ldx, E);
-  COATI_CHECK_SHAPE(ldo >= P, "head_eval: ldo=%lld < P=%d", ldo, P);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "head_eval: N=%lld outside 1 .. 2^31 - 1", (long long)N);
+  COATI_CHECK_SHAPE(ldx >= E && ldx % 8 == 0, "head_eval: ldx=%lld must be a multiple of 8 and >= E=%d", (long long)ldx, E);
+  COATI_CHECK_SHAPE(ldo >= P, "head_eval: ldo=%lld < P=%d", (long long)ldo, P);
   COATI_CHECK_ARG(head_aligned16(x) && head_aligned16(w0) && head_aligned16(b0) && head_aligned16(wr) && head_aligned16(br) && head_aligned16(wl),
                   "head_eval: x, w0, b0, wr, br and wl must start at 16-byte boundaries");
   if (F == 64)

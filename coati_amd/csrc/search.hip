@@ -11,6 +11,7 @@
 //
 // search_merge_kernel, one workgroup per query: the samplers' radix select (decode_dev.h) over the query's S * k partial scores.
 // Candidate position order is (slice, rank) = ascending row index among equal scores, so the select's "index ascending" is the tie rule.
+#include "../../include/coati_search.h"
 #include "search_host.h"
 
 #define SEARCH_E_MAX 512
@@ -80,15 +81,16 @@ static int search_launch(const bf16_t* lib, long long N, int E, const float* bia
   return COATI_OK;
 }
 
-int launch_search_topk(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, int k, float alpha, int S,
-                       float* part_score, int* part_row, float* out_score, long long* out_row, hipStream_t s) {
+int coati_search_topk(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, int k, float alpha, int S,
+                      float* part_score, int32_t* part_row, float* out_score, int64_t* out_row, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib && q && part_score && part_row && out_score && out_row, "search_topk: null operand");
   COATI_TRY(search_check(N, E, Q, k, S));
   if (E <= 256)
     COATI_TRY((search_launch<8, 4>(lib, N, E, bias, q, Q, k, alpha, S, part_score, part_row, s)));
   else
     COATI_TRY((search_launch<16, 2>(lib, N, E, bias, q, Q, k, alpha, S, part_score, part_row, s)));
-  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, out_row, s);
+  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, LL(out_row), s);
 }
 
 // The merge alone, also for the stream kernels of other files that write the same partial lists (search8.hip, search4.hip, pq.hip):
@@ -102,5 +104,5 @@ int launch_search_merge(const float* part_score, const int* part_row, int Q, int
   return COATI_OK;
 }
 
-// The number of slices launch_search_topk is given by default (topk_default_slices).  Host arithmetic only.
-int search_slices(long long N, int Q, int k) { return topk_default_slices("search_slices", N, Q, k); }
+// The number of slices coati_search_topk is given by default (topk_default_slices).  Host arithmetic only.
+int coati_search_slices(int64_t N, int Q, int k) { return topk_default_slices("search_slices", N, Q, k); }

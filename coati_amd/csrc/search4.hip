@@ -38,6 +38,7 @@
 // past the slice's end are read at row N - 1 and dropped by the filter.
 #include <type_traits>
 
+#include "../../include/coati_search4.h"
 #include "search_host.h"
 
 #define SEARCH4_E_MAX 512
@@ -99,10 +100,11 @@ __global__ __launch_bounds__(256) void quant_rows_fp4_kernel(const bf16_t* __res
   }
 }
 
-int launch_quant_rows_fp4(const bf16_t* x, long long n, int E, unsigned char* codes, unsigned char* scales, hipStream_t s) {
+int coati_quant_rows_fp4(const uint16_t* x, int64_t n, int E, uint8_t* codes, uint8_t* scales, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x && codes && scales, "quant_rows_fp4: null operand");
   COATI_CHECK_SHAPE(E >= 32 && E <= SEARCH4_E_MAX && E % 32 == 0, "quant_rows_fp4: E=%d is not a multiple of 32 in 32 .. %d", E, SEARCH4_E_MAX);
-  COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "quant_rows_fp4: n=%lld outside 1 .. 2^31 - 1", n);
+  COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "quant_rows_fp4: n=%lld outside 1 .. 2^31 - 1", (long long)n);
   const int E4 = (E + 127) / 128 * 128;
   hipLaunchKernelGGL(quant_rows_fp4_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, x, n, E, E4, codes, scales);
   COATI_LAUNCH_CHECK("quant_rows_fp4");
@@ -280,9 +282,10 @@ static int search4_launch(const unsigned char* codes, const unsigned char* scale
   return COATI_OK;
 }
 
-int launch_search4_topk(const unsigned char* codes, const unsigned char* scales, long long N, int E4, const float* bias, const unsigned char* q,
-                        const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
-                        long long* out_row, hipStream_t s) {
+int coati_search4_topk(const uint8_t* codes, const uint8_t* scales, int64_t N, int E4, const float* bias, const uint8_t* q,
+                       const float* qscale, int Q, int k, float alpha, int S, float* part_score, int32_t* part_row, float* out_score,
+                       int64_t* out_row, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(codes && scales && bias && q && qscale && part_score && part_row && out_score && out_row, "search4_topk: null operand");
   COATI_TRY(search4_check(N, E4, Q, k, S));
   switch (E4 / 128) {
@@ -291,8 +294,8 @@ int launch_search4_topk(const unsigned char* codes, const unsigned char* scales,
     case 3: COATI_TRY((search4_launch<3, 2>(codes, scales, N, bias, q, qscale, Q, k, alpha, S, part_score, part_row, s))); break;
     default: COATI_TRY((search4_launch<4, 2>(codes, scales, N, bias, q, qscale, Q, k, alpha, S, part_score, part_row, s))); break;
   }
-  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, out_row, s);
+  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, LL(out_row), s);
 }
 
-// The number of slices launch_search4_topk is given by default: search_slices' (topk_default_slices).  Host arithmetic only.
-int search4_slices(long long N, int Q, int k) { return topk_default_slices("search4_slices", N, Q, k); }
+// The number of slices coati_search4_topk is given by default: coati_search_slices' (topk_default_slices).  Host arithmetic only.
+int coati_search4_slices(int64_t N, int Q, int k) { return topk_default_slices("search4_slices", N, Q, k); }

@@ -34,6 +34,7 @@
 // in LDS by topk_compact<true>: score descending, row ascending.
 #include <type_traits>
 
+#include "../../include/coati_search8.h"
 #include "search_host.h"
 
 #define SEARCH8_E_MAX 512
@@ -86,10 +87,11 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
   if (lane == 0) scale[row] = __uint_as_float((unsigned)(127 + j) << 23);
 }
 
-int launch_quant_rows_fp8(const bf16_t* x, long long n, int E, unsigned char* out, float* scale, hipStream_t s) {
+int coati_quant_rows_fp8(const uint16_t* x, int64_t n, int E, uint8_t* out, float* scale, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(x && out && scale, "quant_rows_fp8: null operand");
   COATI_CHECK_SHAPE(E >= 32 && E <= SEARCH8_E_MAX && E % 32 == 0, "quant_rows_fp8: E=%d is not a multiple of 32 in 32 .. %d", E, SEARCH8_E_MAX);
-  COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "quant_rows_fp8: n=%lld outside 1 .. 2^31 - 1", n);
+  COATI_CHECK_SHAPE(n >= 1 && n < (1ll << 31), "quant_rows_fp8: n=%lld outside 1 .. 2^31 - 1", (long long)n);
   hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, x, n, E, out, scale);
   COATI_LAUNCH_CHECK("quant_rows_fp8");
   return COATI_OK;
@@ -268,16 +270,17 @@ static int search8_launch(const unsigned char* lib, const float* scale, long lon
   return COATI_OK;
 }
 
-int launch_search8_topk(const unsigned char* lib, const float* scale, long long N, int E, const float* bias, const unsigned char* q,
-                        const float* qscale, int Q, int k, float alpha, int S, float* part_score, int* part_row, float* out_score,
-                        long long* out_row, hipStream_t s) {
+int coati_search8_topk(const uint8_t* lib, const float* scale, int64_t N, int E, const float* bias, const uint8_t* q, const float* qscale,
+                       int Q, int k, float alpha, int S, float* part_score, int32_t* part_row, float* out_score, int64_t* out_row,
+                       void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib && scale && bias && q && qscale && part_score && part_row && out_score && out_row, "search8_topk: null operand");
   COATI_TRY(search8_check(N, E, Q, k, S));
   if (E <= 256)
     COATI_TRY((search8_launch<4, 2>(lib, scale, N, E, bias, q, qscale, Q, k, alpha, S, part_score, part_row, s)));
   else
     COATI_TRY((search8_launch<8, 2>(lib, scale, N, E, bias, q, qscale, Q, k, alpha, S, part_score, part_row, s)));
-  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, out_row, s);
+  return launch_search_merge(part_score, part_row, Q, S * k, k, out_score, LL(out_row), s);
 }
 
 // ---- stage 2: the candidates' exact scores ----------------------------------------------------------------------------------------------
@@ -342,18 +345,19 @@ __global__ __launch_bounds__(256) void search_rescore_kernel(const bf16_t* __res
   }
 }
 
-int launch_search_rescore(const bf16_t* lib, long long N, int E, const float* bias, const bf16_t* q, int Q, const long long* cand, int R, int k,
-                          float alpha, float* out_score, long long* out_row, hipStream_t s) {
+int coati_search_rescore(const uint16_t* lib, int64_t N, int E, const float* bias, const uint16_t* q, int Q, const int64_t* cand, int R, int k,
+                         float alpha, float* out_score, int64_t* out_row, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(lib && q && cand && out_score && out_row, "search_rescore: null operand");
   COATI_CHECK_SHAPE(E >= 32 && E <= SEARCH8_E_MAX && E % 32 == 0, "search_rescore: E=%d is not a multiple of 32 in 32 .. %d", E, SEARCH8_E_MAX);
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "search_rescore: N=%lld outside 1 .. 2^31 - 1", N);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "search_rescore: N=%lld outside 1 .. 2^31 - 1", (long long)N);
   COATI_CHECK_SHAPE(Q >= 1, "search_rescore: Q=%d < 1", Q);
   COATI_CHECK_SHAPE(R >= 1 && R <= RESCORE_R_MAX, "search_rescore: R=%d outside 1 .. %d", R, RESCORE_R_MAX);
   COATI_CHECK_SHAPE(k >= 1 && k <= TOPK_MAX, "search_rescore: k=%d outside 1 .. %d", k, TOPK_MAX);
-  hipLaunchKernelGGL(search_rescore_kernel, dim3(Q), dim3(256), 0, s, lib, N, E, bias, q, cand, R, k, alpha, out_score, out_row);
+  hipLaunchKernelGGL(search_rescore_kernel, dim3(Q), dim3(256), 0, s, lib, N, E, bias, q, LL(cand), R, k, alpha, out_score, LL(out_row));
   COATI_LAUNCH_CHECK("search_rescore");
   return COATI_OK;
 }
 
-// The number of slices launch_search8_topk is given by default: search_slices' (topk_default_slices).  Host arithmetic only.
-int search8_slices(long long N, int Q, int k) { return topk_default_slices("search8_slices", N, Q, k); }
+// The number of slices coati_search8_topk is given by default: coati_search_slices' (topk_default_slices).  Host arithmetic only.
+int coati_search8_slices(int64_t N, int Q, int k) { return topk_default_slices("search8_slices", N, Q, k); }

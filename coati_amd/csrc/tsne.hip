@@ -19,6 +19,7 @@
 // butterfly, lane 0 forms the gradient and sklearn's gains / momentum update for the row's two coordinates.
 #include <float.h>
 
+#include "../../include/coati_tsne.h"
 #include "kernels.h"
 
 #define TS_J 1024          // points per chunk of the repulsion (the summation order hangs on it)
@@ -211,11 +212,13 @@ __global__ __launch_bounds__(256) void tsne_step_kernel(const float2* __restrict
   if (att) att[i] = float2{ax, ay};
 }
 
-int launch_tsne_affinities(const float* d2, const int* nbr, long long N, int k, float perplexity, int steps, float* p, float* beta, hipStream_t s) {
+int coati_tsne_affinities(const float* d2, const int32_t* nbr, int64_t N, int k, float perplexity, int steps, float* p, float* beta,
+                          void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(d2, "tsne_affinities: d2 is null");
   COATI_CHECK_ARG(nbr, "tsne_affinities: nbr is null");
   COATI_CHECK_ARG(p, "tsne_affinities: p is null");
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "tsne_affinities: N=%lld outside 1 .. 2^31 - 1", N);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "tsne_affinities: N=%lld outside 1 .. 2^31 - 1", (long long)N);
   COATI_CHECK_SHAPE(k >= 1 && k <= TS_K_MAX, "tsne_affinities: k=%d outside 1 .. %d", k, TS_K_MAX);
   COATI_CHECK_SHAPE(perplexity > 0.f && perplexity <= FLT_MAX, "tsne_affinities: perplexity=%g is not positive and finite", (double)perplexity);
   COATI_CHECK_SHAPE(steps >= 0 && steps <= 10000, "tsne_affinities: steps=%d outside 0 .. 10000", steps);
@@ -224,23 +227,24 @@ int launch_tsne_affinities(const float* d2, const int* nbr, long long N, int k, 
   return COATI_OK;
 }
 
-int tsne_chunk(void) { return TS_J; }
+int coati_tsne_chunk(void) { return TS_J; }
 
-long long tsne_part_floats(long long N) {
+int64_t coati_tsne_part_floats(int64_t N) {
   if (!(N >= 1 && N < (1ll << 31))) {
-    coati_set_error("tsne_part_floats: N=%lld outside 1 .. 2^31 - 1", N);
+    coati_set_error("tsne_part_floats: N=%lld outside 1 .. 2^31 - 1", (long long)N);
     return COATI_ESHAPE;
   }
   return 3 * N * ((N + TS_J - 1) / TS_J);
 }
 
-int launch_tsne_repulsion(const float* y, long long N, float* rep, float* z, float* part, long long part_floats, int blocks, hipStream_t s) {
+int coati_tsne_repulsion(const float* y, int64_t N, float* rep, float* z, float* part, int64_t part_floats, int blocks, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(y, "tsne_repulsion: y is null");
   COATI_CHECK_ARG(rep, "tsne_repulsion: rep is null");
   COATI_CHECK_ARG(z, "tsne_repulsion: z is null");
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "tsne_repulsion: N=%lld outside 1 .. 2^31 - 1", N);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "tsne_repulsion: N=%lld outside 1 .. 2^31 - 1", (long long)N);
   COATI_CHECK_SHAPE(blocks >= 0, "tsne_repulsion: blocks=%d < 0", blocks);
-  COATI_CHECK_SHAPE(part_floats >= 0, "tsne_repulsion: part_floats=%lld < 0", part_floats);
+  COATI_CHECK_SHAPE(part_floats >= 0, "tsne_repulsion: part_floats=%lld < 0", (long long)part_floats);
   const long long tiles = (N + TS_TI - 1) / TS_TI;
   const int nchunks = (int)((N + TS_J - 1) / TS_J);
   const bool split = part && nchunks > 1 && tiles < TS_SPLIT_BELOW && part_floats >= 3 * N * nchunks;
@@ -259,9 +263,10 @@ int launch_tsne_repulsion(const float* y, long long N, float* rep, float* z, flo
   return COATI_OK;
 }
 
-int launch_tsne_step(const float* y, const float* rep, const float* zsum, const long long* offsets, const int* cols, const float* vals, long long N,
-                     float exaggeration, float momentum, float lr, float min_gain, float* update, float* gains, float* y_out, float* kl_rows,
-                     float* att, hipStream_t s) {
+int coati_tsne_step(const float* y, const float* rep, const float* zsum, const int64_t* offsets, const int32_t* cols, const float* vals,
+                    int64_t N, float exaggeration, float momentum, float lr, float min_gain, float* update, float* gains, float* y_out,
+                    float* kl_rows, float* att, void* stream) {
+  hipStream_t s = S_(stream);
   COATI_CHECK_ARG(y, "tsne_step: y is null");
   COATI_CHECK_ARG(rep, "tsne_step: rep is null");
   COATI_CHECK_ARG(zsum, "tsne_step: zsum is null");
@@ -270,10 +275,10 @@ int launch_tsne_step(const float* y, const float* rep, const float* zsum, const 
   COATI_CHECK_ARG(gains, "tsne_step: gains is null");
   COATI_CHECK_ARG(y_out, "tsne_step: y_out is null");
   COATI_CHECK_ARG(y_out != y, "tsne_step: y_out is y (other rows read y: use two buffers in turn)");
-  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "tsne_step: N=%lld outside 1 .. 2^31 - 1", N);
+  COATI_CHECK_SHAPE(N >= 1 && N < (1ll << 31), "tsne_step: N=%lld outside 1 .. 2^31 - 1", (long long)N);
   // (cols and vals may be null when P has no entry at all: no row then reads them)
   hipLaunchKernelGGL(tsne_step_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const float2*>(y),
-                     reinterpret_cast<const float2*>(rep), zsum, offsets, cols, vals, N, exaggeration, momentum, lr, min_gain,
+                     reinterpret_cast<const float2*>(rep), zsum, LL(offsets), cols, vals, N, exaggeration, momentum, lr, min_gain,
                      reinterpret_cast<float2*>(update), reinterpret_cast<float2*>(gains), reinterpret_cast<float2*>(y_out), kl_rows,
                      reinterpret_cast<float2*>(att));
   COATI_LAUNCH_CHECK("tsne_step");
