@@ -33,10 +33,11 @@ FEATURE_HEADERS = [
     ("ivfpq", "IVF search over lists of residual PQ codes"),
     ("search4", "four-bit (MX fp4) search"),
     ("tsne", "embedding maps (exact t-SNE)"),
+    ("gmm", "library density (diagonal Gaussian mixtures)"),
 ]
-for _stem, _ in FEATURE_HEADERS:   # BEAM_HEADER ... TSNE_HEADER: the paths, as module attributes (_lib.py reads each through its attribute)
+for _stem, _ in FEATURE_HEADERS:   # BEAM_HEADER ... GMM_HEADER: the paths, as module attributes (_lib.py reads each through its attribute)
     globals()[f"{_stem.upper()}_HEADER"] = os.path.join(os.path.dirname(HERE), "include", f"coati_{_stem}.h")
-HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip", "guide.hip", "gp.hip", "gp_grad.hip", "cluster.hip", "ivf.hip", "radius.hip", "search8.hip", "ivf8.hip", "ivf_radius.hip", "pq.hip", "ivfpq.hip", "search4.hip", "tsne.hip"]
+HIP_UNITS = ["gemm.hip", "gemm_rb.hip", "gemm_rb16.hip", "gemm_ring.hip", "gemm_mx8.hip", "norm.hip", "attention.hip", "attention16.hip", "embed.hip", "gnn.hip", "loss.hip", "optim.hip", "batch.hip", "decode.hip", "beam.hip", "search.hip", "grammar.hip", "screen.hip", "guide.hip", "gp.hip", "gp_grad.hip", "cluster.hip", "ivf.hip", "radius.hip", "search8.hip", "ivf8.hip", "ivf_radius.hip", "pq.hip", "ivfpq.hip", "search4.hip", "tsne.hip", "gmm.hip"]
 CPP_UNITS = ["engine.cpp", "capi.cpp", "tokenizer.cpp", "comm.cpp"]
 # -amdgpu-mfma-vgpr-form: MFMA results in VGPRs (gfx950 has one unified register file).  Where the compiler picked the AGPR form
 # (the attention forward kernels) 13 % of the instructions were v_accvgpr_read / write moves in a VALU-bound kernel

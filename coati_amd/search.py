@@ -334,6 +334,35 @@ class EmbeddingIndex:
         out.rows = rows
         return out
 
+    def gmm(self, k, iters=50, seed=0, init="kmeans", rows=None, reg_covar=1e-6, tol=1e-4):
+        """A coati_amd.gmm.GaussianMixture of k diagonal Gaussians fitted to the live rows by EM on two fused kernels (an online
+        log-sum-exp E-step and a moment-accumulating M-step on the f32 matrix cores; no [N, K] matrix), reproducible bit for bit from
+        `seed`.  "cosine" or "l2" index; "dot" raises ValueError.  init: "kmeans" (kmeans(k, seed=seed)'s centres, the global variance)
+        or (weights, means, variances).  rows: fit this subset only.  The mixture answers log_prob / predict for any vectors and its
+        rsample is what a virtual screen draws from: sampled_virtual_screen(index.gmm(64), head, model, tokenizer, hit_thresh); its
+        draws are in the index's prepared space (of about unit norm on a "cosine" index)."""
+        from . import gmm
+        x16, bias, _ = self._cluster_operands("gmm", rows)
+        return gmm.fit_rows(x16, bias, k, iters=iters, seed=seed, init=init, reg_covar=reg_covar, tol=tol, dim=self.dim, metric=self.metric)
+
+    def log_density(self, gmm):
+        """[N] f32: log p of every stored row under a GaussianMixture, -inf for removed rows -- one pass of the E-step kernel over the
+        stored rows, nothing else allocated"""
+        from . import gmm as G
+        x16, bias, _ = self._cluster_operands("log_density")
+        if gmm.dim != self.dim:
+            raise ValueError(f"EmbeddingIndex.log_density: the mixture's dim={gmm.dim}, the index's dim={self.dim}")
+        par, cst = G.prepare_params(gmm.weights, gmm.means, gmm.variances, self.dim_padded)
+        return G.estep_call(x16, bias, par.to(self.device), cst.to(self.device), want_assign=False)[0]
+
+    def outliers(self, gmm, n):
+        """(log_density [n] f32, rows [n] int64): the n live rows of lowest density under the mixture, lowest first (torch.topk)"""
+        dens = self.log_density(gmm)
+        live = self.bias > float("-inf")
+        n = min(int(n), int(live.sum()))
+        vals, rows = torch.topk(torch.where(live, dens, torch.full_like(dens, float("inf"))), n, largest=False)
+        return vals, rows
+
     def ivf(self, nlist, iters=20, seed=0, centres=None, fp8=False, keep_rows=True):
         """A coati_amd.ivf.IVFIndex over the live rows: kmeans(nlist, iters, seed)'s clusters (or the nearest of `centres`) as inverted
         lists, for approximate search over the nprobe nearest lists of every query.  fp8=True: a coati_amd.ivf8.Ivf8Index instead -- the
